@@ -2,7 +2,7 @@
 """Benchmark of the SR hot path: training frames/s at BASELINE cfg2 (scale=2, feat=64, blocks=8,
 T=3, 540p -> 1080p), one process per GPU, weak scaling.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,10 @@ the timed region.  Rank 0 prints ONE JSON line (contract in the round prompt).  
 dominant kernel's algorithmic FLOP rate measured with HIP events around each of its launches in
 the timed region; `cpu_baseline` is the CPU oracle (a PyTorch-CPU restatement of the reference)
 timed on this host's cores on a bounded sample.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step computed as DIR/<name>.npy: the network's output(s), the
+loss and every parameter's gradient (dump_outputs below), so that two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -38,6 +42,30 @@ PEAK_HBM_GBS = 8000.0
 PEAK_BF16_MFMA_TFLOPS = 2500.0   # dense bf16 MFMA peak (same guide); ridge = 2500 / 8 = 312 FLOP/B
 # algorithmic bytes of one train step per clip in bf16 storage (3 x the forward's 16 566 planes at cfg2)
 ALGO_GB_PER_CLIP_STEP = {"cfg2": 51.53, "cfg4 (SR part)": 16.66}
+DUMP_BYTES = 64 * 2**20          # --dump-outputs: size of all files together
+
+
+def dump_outputs(directory: str, arrays: dict) -> int:
+    """Write every tensor of `arrays` as directory/<name>.npy and return the bytes written: a 0-d tensor as float64, any
+    other as float32.  The arrays share DUMP_BYTES evenly; one with more elements than its share is written as a fixed
+    sample of its flattened elements (positions drawn by a generator seeded with 0, sorted), the same positions for every
+    run with the same shapes."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // (4 * max(len(arrays), 1))
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() == 0:
+            a = t.to(torch.float64).cpu().numpy()
+        else:
+            if t.numel() > share:
+                pos = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=share))
+                t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+            a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        total += a.nbytes
+    return total
 
 
 def sources_sha() -> str:
@@ -234,7 +262,12 @@ def main():
                          "(SURVEY.md 8d)")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--detail", action="store_true", help="print a per-shape table of the conv launches to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output(s), loss and parameter gradients of the last timed step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MiB in all: a fixed seeded sample of a larger array)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))       # nothing above has initialised the GPU
@@ -291,14 +324,21 @@ def main():
         mask[:, :, cfg["H"] // 4:cfg["H"] // 4 + cfg["H"] // 2, cfg["W"] // 4:cfg["W"] // 4 + cfg["W"] // 2] = 1.0
         x_centre = x[:, cfg["T"] // 2].contiguous()
 
-    def step():
+    def step(keep=None):
+        """one train step; `keep` (a dict), when given, receives the network's output(s)"""
         opt.zero_grad()
         if engine is None:
-            loss = ops.mse_loss(net(x), y)      # nn.MSELoss of the reference loop as libnvq kernels
+            out = net(x)
+            if keep is not None:
+                keep["output"] = out
+            loss = ops.mse_loss(out, y)         # nn.MSELoss of the reference loop as libnvq kernels (SURVEY A12)
+            del out                             # unless kept, the output is freed as soon as the backward has used it
         else:
             # the second term is what gives the recovery head a gradient: its output does not feed the SR result
             # (reference enhancement_engine.py:143-148)
             res = engine(x, corruption_mask=mask)
+            if keep is not None:
+                keep.update(res)
             loss = ops.mse_loss(res["enhanced"], y) + ops.mse_loss(res["recovered"], x_centre)
         loss.backward()
         opt.step()
@@ -307,13 +347,14 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    def timed_pass():
+    def timed_pass(keep=None):
+        """args.steps steps; `keep` is handed to the last of them"""
         if world > 1:
             parallel.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = step()
+        for i in range(args.steps):
+            loss = step(keep if i == args.steps - 1 else None)
         torch.cuda.synchronize()
         if world > 1:
             parallel.barrier()
@@ -324,8 +365,10 @@ def main():
             dt = tt.item()
         return dt, loss
 
+    # --dump-outputs: the outputs of the last step of the last timed pass
+    kept = {} if args.dump_outputs else None
     # pass A: exactly K steps, nothing but the workload on the stream -> `value`
-    dt, loss = timed_pass()
+    dt, loss = timed_pass(kept if args.no_kernel_timer else None)
     # pass B: the same K steps again with a HIP event pair around every conv launch -> `roofline`
     # (the event records cost ~10 % of a step, so they are kept out of pass A)
     timer = None
@@ -333,7 +376,7 @@ def main():
     if not args.no_kernel_timer:
         timer = _nvq.KernelTimer()
         _nvq.TIMER = timer
-        dt_b, loss = timed_pass()
+        dt_b, loss = timed_pass(kept)
         _nvq.TIMER = None
     final_loss = loss.item()
 
@@ -341,6 +384,15 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
+
+    if kept is not None:
+        # the gradients of that step are still in place (the next zero_grad would clear them)
+        kept["loss"] = loss
+        kept["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                                   for p in model.parameters()])
+        nbytes = dump_outputs(args.dump_outputs, kept)
+        print(f"[bench] wrote {', '.join(kept)} of the last timed step to {args.dump_outputs} ({nbytes / 2**20:.1f} MiB)",
+              file=sys.stderr, flush=True)
 
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
