@@ -657,6 +657,275 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const float* __res
     }
 }
 
+// ---------------------------------------------------------------- deterministic mode (nvq_warp_backward_ex, flag bit 0)
+// The far sources of the overwrite mode without float atomics: a binned gather.  Behind the src pass (unchanged: it flags
+// the far sources and writes their flow gradient),
+//   count:  per far source, its corner geometry (NW corner in far_nw, masked weights in its otherwise unused rec_w slot) and
+//           one integer atomicAdd per destination tile its valid corners touch (at most 4 of the 8 x 32 tiles);
+//   scan:   one workgroup, exclusive scan of the per-tile counts -> bin offsets;
+//   place:  each far source appends its index to its bins (integer atomics: the order inside a bin is arbitrary);
+//   sort:   every bin sorted by source index (rank = number of smaller keys; a source is at most once in a bin);
+//   gather: warp_bwd_gather_det_kernel adds, per destination pixel and channel, the window list (as warp_bwd_gather_kernel),
+//           then the tile's bin in ascending source index, then the list overflow in scan order, in fp32 registers, and
+//           stores once.
+// Every pass leaves at once when the src pass flagged no far source (a device-side flag: no host read, capture-safe); the
+// buffers are sized for every source being far.  Integer atomics only: the result does not depend on the schedule.
+constexpr int WD_FK = 256;                      // entries of a tile's bin staged in LDS by the gather; the rest come from memory
+constexpr int WD_SORT = 2048;                   // keys per LDS chunk of the sort
+
+// destination tiles of the valid corners of a far source with NW corner (y0, x0), deduplicated; -1 = none
+__device__ __forceinline__ int4 far_tiles(int y0, int x0, int n, int H, int W, int tilesX, int tilesY) {
+    int t[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int y = y0 + (c >> 1), x = x0 + (c & 1);
+        t[c] = (y >= 0 && y < H && x >= 0 && x < W) ? (n * tilesY + y / WG_TH) * tilesX + x / WG_TW : -1;
+#pragma unroll
+        for (int j = 0; j < c; ++j)
+            if (t[j] == t[c]) t[c] = -1;
+    }
+    return make_int4(t[0], t[1], t[2], t[3]);
+}
+
+__global__ __launch_bounds__(256) void warp_det_count_kernel(const float* __restrict__ flow, int flow_ld, int H, int W,
+                                                             long npix, int tilesX, int tilesY, float4* __restrict__ rec_w,
+                                                             int* __restrict__ far_nw, int* __restrict__ count,
+                                                             const int* __restrict__ far_flag) {
+    if (*far_flag == 0) return;
+    for (long pix = blockIdx.x * 256L + threadIdx.x; pix < npix; pix += (long)gridDim.x * 256) {
+        const long rowi = idiv(pix, W, npix);
+        const int x = (int)(pix - rowi * W);
+        const long n = idiv(rowi, H, npix);
+        const int y = (int)(rowi - n * H);
+        // (the src pass's classification: same geometry, same test)
+        const WarpGeom g = warp_geom(flow[pix * flow_ld], flow[pix * flow_ld + 1], x, y, H, W);
+        const int ox = g.x0 - x, oy = g.y0 - y;
+        const bool any = g.vnw || g.vne || g.vsw || g.vse;
+        const bool near = ox >= -WG_R && ox <= WG_R - 1 && oy >= -WG_R && oy <= WG_R - 1;
+        int code = -1;
+        if (any && !near) {                                   // a valid corner: y0 in [-1, H), x0 in [-1, W)
+            rec_w[pix] = make_float4(g.vnw ? g.wnw : 0.f, g.vne ? g.wne : 0.f, g.vsw ? g.wsw : 0.f, g.vse ? g.wse : 0.f);
+            code = ((g.y0 + 1) << 16) | (g.x0 + 1);
+            const int4 t = far_tiles(g.y0, g.x0, (int)n, H, W, tilesX, tilesY);
+            if (t.x >= 0) atomicAdd(count + t.x, 1);
+            if (t.y >= 0) atomicAdd(count + t.y, 1);
+            if (t.z >= 0) atomicAdd(count + t.z, 1);
+            if (t.w >= 0) atomicAdd(count + t.w, 1);
+        }
+        far_nw[pix] = code;
+    }
+}
+
+__global__ __launch_bounds__(1024) void warp_det_scan_kernel(const int* __restrict__ count, int* __restrict__ offs,
+                                                             int* __restrict__ cursor, int ntiles,
+                                                             const int* __restrict__ far_flag) {
+    if (*far_flag == 0) return;
+    __shared__ int wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < ntiles; base += 1024) {
+        const int i = base + threadIdx.x;
+        const int v = i < ntiles ? count[i] : 0;
+        int s = v;                                            // inclusive scan over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(s, o, 64);
+            if (lane >= o) s += u;
+        }
+        if (lane == 63) wsum[wave] = s;
+        __syncthreads();
+        if (wave == 0) {
+            int t = lane < 16 ? wsum[lane] : 0;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const int u = __shfl_up(t, o, 64);
+                if (lane >= o) t += u;
+            }
+            if (lane < 16) wsum[lane] = t;
+        }
+        __syncthreads();
+        if (i < ntiles) {
+            offs[i] = carry + (wave ? wsum[wave - 1] : 0) + s - v;
+            cursor[i] = 0;
+        }
+        carry += wsum[15];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void warp_det_place_kernel(const int* __restrict__ far_nw, int H, int W, long npix, int tilesX,
+                                                             int tilesY, const int* __restrict__ offs, int* __restrict__ cursor,
+                                                             int* __restrict__ ent_raw, const int* __restrict__ far_flag) {
+    if (*far_flag == 0) return;
+    for (long pix = blockIdx.x * 256L + threadIdx.x; pix < npix; pix += (long)gridDim.x * 256) {
+        const int code = far_nw[pix];
+        if (code < 0) continue;
+        const int n = (int)idiv(pix, (long)H * W, npix);
+        const int4 t = far_tiles((code >> 16) - 1, (code & 0xffff) - 1, n, H, W, tilesX, tilesY);
+        if (t.x >= 0) ent_raw[offs[t.x] + atomicAdd(cursor + t.x, 1)] = (int)pix;
+        if (t.y >= 0) ent_raw[offs[t.y] + atomicAdd(cursor + t.y, 1)] = (int)pix;
+        if (t.z >= 0) ent_raw[offs[t.z] + atomicAdd(cursor + t.z, 1)] = (int)pix;
+        if (t.w >= 0) ent_raw[offs[t.w] + atomicAdd(cursor + t.w, 1)] = (int)pix;
+    }
+}
+
+// One workgroup per bin: key e goes to position (number of keys < key e).  O(m^2 / 256) per bin, keys streamed through LDS
+// in chunks of WD_SORT: a few hundred entries in the usual case; a bin of every source of an image is slow but exact.
+__global__ __launch_bounds__(256) void warp_det_sort_kernel(const int* __restrict__ count, const int* __restrict__ offs,
+                                                            const int* __restrict__ ent_raw, int* __restrict__ ent, int ntiles,
+                                                            const int* __restrict__ far_flag) {
+    if (*far_flag == 0) return;
+    __shared__ int sk[WD_SORT];
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int m = count[t];                               // (uniform over the workgroup)
+        if (m == 0) continue;
+        const int base = offs[t];
+        for (int e0 = 0; e0 < m; e0 += 256) {
+            const int e = e0 + threadIdx.x;
+            const int key = e < m ? ent_raw[base + e] : 0;
+            int rank = 0;
+            for (int c0 = 0; c0 < m; c0 += WD_SORT) {
+                const int lim = m - c0 < WD_SORT ? m - c0 : WD_SORT;
+                __syncthreads();
+                for (int i = threadIdx.x; i < lim; i += 256) sk[i] = ent_raw[base + c0 + i];
+                __syncthreads();
+                for (int i = 0; i < lim; ++i) rank += sk[i] < key ? 1 : 0;
+            }
+            if (e < m) ent[base + rank] = key;
+        }
+        __syncthreads();
+    }
+}
+
+// warp_bwd_gather_kernel in the overwrite mode with the far sources and the list overflow folded into the accumulators: one
+// fp32 sum per (pixel, channel) - window list, bin (ascending source index), overflow (scan order) - and one store.
+template <bool DB, bool FB16>                                 // DB: dout is bf16; FB16: dfeat is bf16
+__global__ __launch_bounds__(256) void warp_bwd_gather_det_kernel(const float* __restrict__ dout, int dout_ld, int dout_coff,
+                                                                  const float4* __restrict__ rec_w,
+                                                                  const int* __restrict__ rec_code, int C, int H, int W,
+                                                                  int tilesX, int tilesY, float* __restrict__ dfeat,
+                                                                  int dfeat_ld, const int* __restrict__ far_count,
+                                                                  const int* __restrict__ far_offs,
+                                                                  const int* __restrict__ far_ent,
+                                                                  const int* __restrict__ far_nw) {
+    constexpr int dout_bf16 = DB;
+    __shared__ float4 lw[WG_HH * WG_HW];
+    __shared__ int lc[WG_HH * WG_HW];
+    __shared__ int hit_n[WG_TH * WG_TW];                     // sources found by the window scan (the list holds WG_MAXHIT)
+    __shared__ unsigned char hit_p[WG_TH * WG_TW * WG_MAXHIT];   // (sy + R) << 4 | (sx + R) <= 136: a byte (LDS: 4 workgroups per CU)
+    __shared__ float hit_w[WG_TH * WG_TW * WG_MAXHIT];
+    __shared__ float4 fs_w[WD_FK];                           // bin entries: weights, NW corner relative to the tile, source
+    __shared__ int fs_yx[WD_FK], fs_src[WD_FK];
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    int bt = tile;
+    const int tx = bt % tilesX; bt /= tilesX;
+    const int ty = bt % tilesY;
+    const int n = bt / tilesY;
+    for (int i = threadIdx.x; i < WG_HH * WG_HW; i += 256) {
+        const int hy = i / WG_HW, hx = i - hy * WG_HW;
+        const int gy = ty * WG_TH + hy - WG_R, gx = tx * WG_TW + hx - WG_R;
+        const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const long pp = ok ? (long)(n * H + gy) * W + gx : 0;
+        lc[i] = ok ? rec_code[pp] : -1;
+        lw[i] = ok ? rec_w[pp] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int fm = far_count[tile];                           // 0 when no source is far (zeroed before the src pass)
+    const int fbase = fm ? far_offs[tile] : 0;
+    // relative NW corner, packed (ry + 1) << 8 | (rx + 1): ry in [-1, WG_TH), rx in [-1, WG_TW) for an entry of this bin
+    const int rel = ((ty * WG_TH) << 16) + tx * WG_TW;
+    auto far_yx = [&](int code) {
+        const int d = code - rel;                            // (ry + 1) << 16 | (rx + 1), both parts >= 0
+        return ((d >> 16) << 8) | (d & 0xffff);
+    };
+    for (int i = threadIdx.x; i < (fm < WD_FK ? fm : WD_FK); i += 256) {
+        const int s = far_ent[fbase + i];
+        fs_src[i] = s;
+        fs_yx[i] = far_yx(far_nw[s]);
+        fs_w[i] = rec_w[s];
+    }
+    __syncthreads();
+    auto scan = [&](int ly, int lx, auto&& hit) {             // as warp_bwd_gather_kernel
+        int cnt = 0;
+        for (int sy = -WG_R; sy <= WG_R; ++sy)
+            for (int sx = -WG_R; sx <= WG_R; ++sx) {
+                const int hi = (ly + WG_R + sy) * WG_HW + lx + WG_R + sx;
+                const int code = lc[hi];
+                if (code < 0) continue;
+                const int a = -sy - ((code >> 4) - WG_R), b = -sx - ((code & 15) - WG_R);
+                if ((unsigned)a > 1u || (unsigned)b > 1u) continue;
+                const float4 w4 = lw[hi];
+                const float wgt = a == 0 ? (b == 0 ? w4.x : w4.y) : (b == 0 ? w4.z : w4.w);
+                if (wgt == 0.f) continue;
+                hit(cnt, sy, sx, wgt);
+                ++cnt;
+            }
+        return cnt;
+    };
+    {
+        const int ly1 = threadIdx.x / WG_TW, lx1 = threadIdx.x % WG_TW;
+        int total1 = 0;
+        if (ty * WG_TH + ly1 < H && tx * WG_TW + lx1 < W)
+            total1 = scan(ly1, lx1, [&](int k, int sy, int sx, float wgt) {
+                if (k < WG_MAXHIT) {
+                    hit_p[threadIdx.x * WG_MAXHIT + k] = (unsigned char)(((sy + WG_R) << 4) | (sx + WG_R));
+                    hit_w[threadIdx.x * WG_MAXHIT + k] = wgt;
+                }
+            });
+        hit_n[threadIdx.x] = total1;
+    }
+    __syncthreads();
+    const int c4 = threadIdx.x & 15;
+    for (int qi = threadIdx.x >> 4; qi < WG_TH * WG_TW; qi += 16) {
+        const int total = hit_n[qi];
+        const int cnt = total < WG_MAXHIT ? total : WG_MAXHIT;
+        const int ly = qi / WG_TW, lx = qi % WG_TW;
+        const int qy = ty * WG_TH + ly, qx = tx * WG_TW + lx;
+        if (qy >= H || qx >= W) continue;                     // (uniform over the 16 lanes of the pixel)
+        const long qpix = (long)(n * H + qy) * W + qx;
+        for (int ch = 4 * c4; ch < C; ch += 64) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int k0 = 0; k0 < cnt; k0 += 4) {             // the window list, exactly as warp_bwd_gather_kernel
+                float4 v[4];
+                float wv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool in = k0 + u < cnt;
+                    const int hp = hit_p[qi * WG_MAXHIT + (in ? k0 + u : 0)];
+                    wv[u] = in ? hit_w[qi * WG_MAXHIT + k0 + u] : 0.f;
+                    const int sy = (hp >> 4) - WG_R, sx = (hp & 15) - WG_R;
+                    v[u] = ldx4(dout, ((size_t)(n * H + qy + sy) * W + qx + sx) * dout_ld + dout_coff + ch, dout_bf16);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc.x += wv[u] * v[u].x; acc.y += wv[u] * v[u].y; acc.z += wv[u] * v[u].z; acc.w += wv[u] * v[u].w;
+                }
+            }
+            for (int e = 0; e < fm; ++e) {                    // the far sources, ascending source index
+                int s, yx;
+                float4 w4;
+                if (e < WD_FK) {
+                    s = fs_src[e]; yx = fs_yx[e]; w4 = fs_w[e];
+                } else {
+                    s = far_ent[fbase + e]; yx = far_yx(far_nw[s]); w4 = rec_w[s];
+                }
+                const int a = ly - ((yx >> 8) - 1), b = lx - ((yx & 0xff) - 1);
+                if ((unsigned)a > 1u || (unsigned)b > 1u) continue;
+                const float wgt = a == 0 ? (b == 0 ? w4.x : w4.y) : (b == 0 ? w4.z : w4.w);
+                if (wgt == 0.f) continue;
+                const float4 v = ldx4(dout, (size_t)s * dout_ld + dout_coff + ch, dout_bf16);
+                acc.x += wgt * v.x; acc.y += wgt * v.y; acc.z += wgt * v.z; acc.w += wgt * v.w;
+            }
+            if (total > WG_MAXHIT)                            // the list overflow (a strongly contracting flow), scan order
+                scan(ly, lx, [&](int k, int sy, int sx, float wgt) {
+                    if (k < WG_MAXHIT) return;
+                    const float4 v = ldx4(dout, ((size_t)(n * H + qy + sy) * W + qx + sx) * dout_ld + dout_coff + ch, dout_bf16);
+                    acc.x += wgt * v.x; acc.y += wgt * v.y; acc.z += wgt * v.z; acc.w += wgt * v.w;
+                });
+            stx4(dfeat, (size_t)qpix * dfeat_ld + ch, FB16, acc);
+        }
+    }
+}
+
 // NVQ_MATH_BF16 variants (corr_mfma.hip)
 bool corr_mfma_supported(int C);
 int corr_forward_mfma(const float* x1, int x1_ld, const float* x2, int x2_ld, int x2_images, int C, int N, int H, int W,
@@ -790,6 +1059,80 @@ if (dfeat_bf16) {
     hipLaunchKernelGGL(warp_bwd_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dout, dout_ld,
                        dout_coff, feat, feat_ld, flow, flow_ld, C, H, W, dfeat, dfeat_ld, dflow, dflow_ld, total);
     return check_launch("warp_backward");
+}
+
+size_t nvq_warp_backward_workspace_bytes(int N, int H, int W, int flags) {
+    if (!(flags & NVQ_WARP_DETERMINISTIC)) return 0;
+    const long npix = (long)N * H * W;
+    const long ntiles = (long)N * ((H + WG_TH - 1) / WG_TH) * ((W + WG_TW - 1) / WG_TW);
+    return (size_t)(3 * ntiles + 9 * npix) * sizeof(int);
+}
+
+int nvq_warp_backward_ex(const float* dout, int dout_ld, int dout_coff, const float* feat, int feat_ld,
+                         const float* flow, int flow_ld, int C, int N, int H, int W, float* dfeat, int dfeat_ld,
+                         float* dflow, int dflow_ld, float* records, size_t records_bytes, int feat_bf16, int dout_bf16,
+                         int overwrite, int dfeat_bf16, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_WARP_DETERMINISTIC) == 0, "warp_backward_ex: unknown flags 0x%x", flags);
+    if (!(flags & NVQ_WARP_DETERMINISTIC))
+        return nvq_warp_backward(dout, dout_ld, dout_coff, feat, feat_ld, flow, flow_ld, C, N, H, W, dfeat, dfeat_ld, dflow,
+                                 dflow_ld, records, records_bytes, feat_bf16, dout_bf16, overwrite, dfeat_bf16, stream);
+    NVQ_REQUIRE(records && overwrite,
+                "warp_backward_ex: the deterministic mode exists for the gather form (records != NULL) in the overwrite mode only");
+    NVQ_REQUIRE(C >= 4 && C <= 1024 && (C & (C - 1)) == 0, "warp_backward_ex: C %d must be a power of two >= 4", C);
+    NVQ_REQUIRE(flow_ld >= 2 && dflow_ld >= 2, "warp_backward_ex: flow ld");
+    NVQ_REQUIRE(H >= 2 && W >= 2 && H < 32767 && W < 32767, "warp_backward_ex: H %d W %d", H, W);
+    const long npix = (long)N * H * W;
+    NVQ_REQUIRE(npix < ((long)1 << 29), "warp_backward_ex: too many pixels (4 bin entries per pixel must fit an int)");
+    NVQ_REQUIRE(records_bytes >= (size_t)npix * 20 + 16 && aligned16(records),
+                "warp_backward_ex: records buffer needs 20 B per pixel + 16 B");
+    NVQ_REQUIRE(workspace && workspace_bytes >= nvq_warp_backward_workspace_bytes(N, H, W, flags) &&
+                    (reinterpret_cast<uintptr_t>(workspace) & 3) == 0,
+                "warp_backward_ex: workspace needs nvq_warp_backward_workspace_bytes() = %zu bytes, 4-byte aligned",
+                nvq_warp_backward_workspace_bytes(N, H, W, flags));
+    NVQ_REQUIRE(dout_ld % 4 == 0 && dout_coff % 4 == 0 && feat_ld % 4 == 0 && dfeat_ld % 4 == 0 && aligned16(dout) &&
+                    aligned16(feat) && aligned16(dfeat),
+                "warp_backward_ex: alignment");
+    hipStream_t s = (hipStream_t)stream;
+    float4* rec_w = reinterpret_cast<float4*>(records);
+    int* rec_code = reinterpret_cast<int*>(rec_w + npix);
+    int* far_flag = rec_code + npix;
+    const int tilesX = (W + WG_TW - 1) / WG_TW, tilesY = (H + WG_TH - 1) / WG_TH;
+    const int ntiles = tilesX * tilesY * N;
+    int* count = static_cast<int*>(workspace);
+    int* offs = count + ntiles;
+    int* cursor = offs + ntiles;
+    int* far_nw = cursor + ntiles;
+    int* ent_raw = far_nw + npix;
+    int* ent = ent_raw + 4 * npix;
+    if (hipMemsetAsync(far_flag, 0, sizeof(int), s) != hipSuccess || hipMemsetAsync(count, 0, sizeof(int) * ntiles, s) != hipSuccess)
+        return check_launch("warp_backward_ex(memset)");
+    const dim3 tgrid((unsigned)ntiles);
+#define NVQ_WS(F_, D_) hipLaunchKernelGGL((warp_bwd_src_kernel<F_, D_>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, feat, \
+                                          feat_ld, flow, flow_ld, C, H, W, dfeat, dfeat_ld, dflow, dflow_ld, rec_w, rec_code,      \
+                                          tilesX, tilesY, far_flag)
+    if (feat_bf16) { if (dout_bf16) NVQ_WS(true, true); else NVQ_WS(true, false); }
+    else { if (dout_bf16) NVQ_WS(false, true); else NVQ_WS(false, false); }
+#undef NVQ_WS
+    int rc = check_launch("warp_backward_ex(src)");
+    if (rc) return rc;
+    const int pgrid = ceil_div(npix, 256) < 2048 ? ceil_div(npix, 256) : 2048;
+    hipLaunchKernelGGL(warp_det_count_kernel, dim3(pgrid), dim3(256), 0, s, flow, flow_ld, H, W, npix, tilesX, tilesY, rec_w,
+                       far_nw, count, (const int*)far_flag);
+    hipLaunchKernelGGL(warp_det_scan_kernel, dim3(1), dim3(1024), 0, s, (const int*)count, offs, cursor, ntiles,
+                       (const int*)far_flag);
+    hipLaunchKernelGGL(warp_det_place_kernel, dim3(pgrid), dim3(256), 0, s, (const int*)far_nw, H, W, npix, tilesX, tilesY,
+                       (const int*)offs, cursor, ent_raw, (const int*)far_flag);
+    hipLaunchKernelGGL(warp_det_sort_kernel, dim3(ntiles < 2048 ? ntiles : 2048), dim3(256), 0, s, (const int*)count,
+                       (const int*)offs, (const int*)ent_raw, ent, ntiles, (const int*)far_flag);
+    rc = check_launch("warp_backward_ex(bins)");
+    if (rc) return rc;
+#define NVQ_WG(D_, F_) hipLaunchKernelGGL((warp_bwd_gather_det_kernel<D_, F_>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, \
+                                          rec_w, rec_code, C, H, W, tilesX, tilesY, dfeat, dfeat_ld, (const int*)count,          \
+                                          (const int*)offs, (const int*)ent, (const int*)far_nw)
+    if (dout_bf16) { if (dfeat_bf16) NVQ_WG(true, true); else NVQ_WG(true, false); }
+    else { if (dfeat_bf16) NVQ_WG(false, true); else NVQ_WG(false, false); }
+#undef NVQ_WG
+    return check_launch("warp_backward_ex(gather)");
 }
 
 }  // extern "C"

@@ -392,8 +392,10 @@ def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, m
     return out
 
 
-def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor]) -> None:
-    """Write the gradient of every parameter into G[name] (each exactly once, overwrite)."""
+def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
+             deterministic: bool = False) -> None:
+    """Write the gradient of every parameter into G[name] (each exactly once, overwrite).  deterministic: the warp gradient
+    without float atomics for any flow (every other kernel of the backward sums in a fixed order already)."""
     if sv.feat0 is None:
         raise RuntimeError("forward(features=...) is an inference path: its result cannot be differentiated")
     g = sv.g
@@ -533,8 +535,12 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
         for j in range(1, T):
             t = g.slots[j]
             lo, hi = (j - 1) * B, j * B
-            K.warp_backward(Sl(daligned, F, t * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
-                            Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True)
+            if deterministic:
+                K.warp_backward(Sl(daligned, F, t * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
+                                Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True, deterministic=True)
+            else:
+                K.warp_backward(Sl(daligned, F, t * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
+                                Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True)
         acts = sv.flow_acts          # [corr(96), f1(128), f2(64), f3(32), flow(4)]
         chans = [81, 128, 64, 32, 2]
         dy_t, dy_c = dflow, 2

@@ -50,6 +50,7 @@ class _Entry:
         self.sv = None
         self.gen = 0                 # replays of the forward graph so far
         self.pending = None          # weakref to the token of the forward whose backward has not run yet
+        self.deterministic = False   # the backward graph's warp gradient mode (part of the key)
         self.eager_calls = 0
 
 
@@ -66,11 +67,12 @@ class StepGraphs:
         self.eager_fallbacks = 0
 
     # ------------------------------------------------------------------ forward
-    def forward(self, net, frames: torch.Tensor, need_grad: bool, act_dtype):
+    def forward(self, net, frames: torch.Tensor, need_grad: bool, act_dtype, deterministic: bool = False):
         """-> (out, entry, token, gen) or None when this call has to run eagerly."""
         if _nvq.TIMER is not None:
             return None
-        key = (tuple(frames.shape), bool(net.training), net.math_mode, act_dtype, bool(need_grad), frames.device.index)
+        key = (tuple(frames.shape), bool(net.training), net.math_mode, act_dtype, bool(need_grad), frames.device.index,
+               bool(deterministic))
         P = net._tensor_dict()
         ptrs = tuple(t.data_ptr() for t in P.values())
         e = self.entries.get(key)
@@ -84,6 +86,7 @@ class StepGraphs:
                 self.eager_fallbacks += 1
                 return None
             e = self.entries[key] = _Entry()
+            e.deterministic = bool(deterministic)
         if e.fwd is None:
             if e.eager_calls < self.WARMUP:
                 e.eager_calls += 1
@@ -128,7 +131,7 @@ class StepGraphs:
             torch.cuda.synchronize()
             with torch.cuda.graph(g, pool=e.pool):
                 flat, views = net._new_grad_bucket()
-                _engine.backward(net._tensor_dict(), e.sv, e.static_dout, views)
+                _engine.backward(net._tensor_dict(), e.sv, e.static_dout, views, deterministic=e.deterministic)
             e.bwd, e.flat = g, flat
             e.sv = None                                        # the graphs own the state now
         else:

@@ -113,6 +113,9 @@ SIGNATURES = {
     "nvq_correlation_backward": (ci, [ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp]),
     "nvq_warp_forward": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp]),
     "nvq_warp_backward": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, sz, ci, ci, ci, ci, vp]),
+    "nvq_warp_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "nvq_warp_backward_ex": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, sz, ci, ci, ci, ci, ci, vp, sz,
+                                  vp]),
     "nvq_tsum_blocks": (ci, [ci, ci]),
     "nvq_tsum_forward": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, ci, ci, vp]),
     "nvq_tsum_backward": (ci, [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, vp]),
@@ -754,12 +757,27 @@ def warp_forward(feat: Sl, flow: torch.Tensor, out: Sl):
                                  out.ld, out.coff, feat.bf16, out.bf16, stream()), "nvq_warp_forward")
 
 
+WARP_DETERMINISTIC = 1
+
+
 def warp_backward(dout: Sl, feat: Sl, flow: torch.Tensor, dfeat: Sl, dflow: torch.Tensor, gather: bool = True,
-                  overwrite: bool = False):
+                  overwrite: bool = False, deterministic: bool = False):
     """gather=True: atomics-free two-pass form (needs 20 B of scratch per pixel, allocated here); False: scatter form.
-    overwrite: dfeat is written instead of added to (gather form): no zero fill before, no read-modify-write here."""
+    overwrite: dfeat is written instead of added to (gather form): no zero fill before, no read-modify-write here.
+    deterministic (gather form, overwrite mode): no float atomics for any flow either (nvq_warp_backward_ex: the far sources
+    are binned and gathered; a bf16 dfeat is rounded once); its workspace is allocated here too."""
     N, H, W, _ = feat.t.shape
     rec = torch.empty(N * H * W * 5 + 4, dtype=torch.float32, device=flow.device) if gather else None
+    if deterministic:
+        nbytes = int(lib().nvq_warp_backward_workspace_bytes(N, H, W, WARP_DETERMINISTIC))
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=flow.device)
+        check(lib().nvq_warp_backward_ex(ptr(dout.t), dout.ld, dout.coff, feat.base(), feat.ld, ptr(flow),
+                                         flow.shape[-1], feat.c, N, H, W, dfeat.base(), dfeat.ld, ptr(dflow),
+                                         dflow.shape[-1], ptr(rec), rec.numel() * 4 if rec is not None else 0, feat.bf16,
+                                         dout.bf16, int(overwrite), dfeat.bf16, WARP_DETERMINISTIC, ptr(ws), ws.numel() * 4,
+                                         stream()),
+              "nvq_warp_backward_ex")
+        return
     check(lib().nvq_warp_backward(ptr(dout.t), dout.ld, dout.coff, feat.base(), feat.ld, ptr(flow),
                                   flow.shape[-1], feat.c, N, H, W, dfeat.base(), dfeat.ld, ptr(dflow),
                                   dflow.shape[-1], ptr(rec), rec.numel() * 4 if rec is not None else 0, feat.bf16, dout.bf16,

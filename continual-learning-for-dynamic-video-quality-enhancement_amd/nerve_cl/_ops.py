@@ -826,14 +826,16 @@ class SoftmaxWeightedSum(torch.autograd.Function):
 
 class Warp(torch.autograd.Function):
     """warp_features (super_resolution.py:104-143): bilinear sampling of `feat` at (x + flow_x, y + flow_y), zero padding,
-    align_corners=True; gradients to the features and to the flow.  feat [N,H,W,ld] (C channels), flow [N,H,W,4]."""
+    align_corners=True; gradients to the features and to the flow.  feat [N,H,W,ld] (C channels), flow [N,H,W,4].
+    deterministic: the backward uses no float atomics for any flow (nvq_warp_backward_ex)."""
 
     @staticmethod
-    def forward(ctx, feat, flow, C: int):
+    def forward(ctx, feat, flow, C: int, deterministic: bool = False):
         out = _new(feat, *feat.shape, zero=feat.shape[-1] > C)
         K.warp_forward(Sl(feat, C), flow, Sl(out, C))
         ctx.save_for_backward(feat, flow)
         ctx.C = C
+        ctx.deterministic = bool(deterministic)
         return out
 
     @staticmethod
@@ -841,8 +843,11 @@ class Warp(torch.autograd.Function):
         feat, flow = ctx.saved_tensors
         dout = dout.contiguous()
         dfeat, dflow = torch.empty_like(feat), torch.empty_like(flow)
-        K.warp_backward(Sl(dout, ctx.C), Sl(feat, ctx.C), flow, Sl(dfeat, ctx.C), dflow, overwrite=True)
-        return dfeat, dflow, None
+        if ctx.deterministic:
+            K.warp_backward(Sl(dout, ctx.C), Sl(feat, ctx.C), flow, Sl(dfeat, ctx.C), dflow, overwrite=True, deterministic=True)
+        else:
+            K.warp_backward(Sl(dout, ctx.C), Sl(feat, ctx.C), flow, Sl(dfeat, ctx.C), dflow, overwrite=True)
+        return dfeat, dflow, None, None
 
 
 # ----------------------------------------------------------------------------- functional helpers used by the modules

@@ -139,17 +139,30 @@ class ResidualDenseBlock(_Holder):
         return _nchw_call(self.forward_nhwc, x, self.num_features)
 
 
-def warp_features(features: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
+def _env_deterministic() -> Optional[bool]:
+    """NVQ_DETERMINISTIC=1: the deterministic mode for unmodified caller scripts (None: not set)."""
+    return True if os.environ.get("NVQ_DETERMINISTIC", "0").lower() in ("1", "on", "true") else None
+
+
+def resolve_deterministic(mode: Optional[bool]) -> bool:
+    """True / False force the mode; None follows torch.are_deterministic_algorithms_enabled() (read at every call)."""
+    return torch.are_deterministic_algorithms_enabled() if mode is None else bool(mode)
+
+
+def warp_features(features: torch.Tensor, flow: torch.Tensor, deterministic: Optional[bool] = None) -> torch.Tensor:
     """Reference super_resolution.py:104-143: sample `features` (N, C, H, W) at pixel coordinates (x + flow[:, 0],
-    y + flow[:, 1]) - bilinear, zeros outside the image, align_corners=True.  Differentiable w.r.t. both arguments."""
+    y + flow[:, 1]) - bilinear, zeros outside the image, align_corners=True.  Differentiable w.r.t. both arguments.
+    deterministic: the gradient without float atomics for any flow, bit-identical from run to run (None: NVQ_DETERMINISTIC=1,
+    else torch.are_deterministic_algorithms_enabled())."""
     _nvq.require_device(features, "features")
     _nvq.require_device(flow, "flow")
     if features.dim() != 4 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != features.shape[0] \
             or flow.shape[2:] != features.shape[2:]:
         raise RuntimeError(f"expected (N,C,H,W) features and (N,2,H,W) flow, got {tuple(features.shape)} and {tuple(flow.shape)}")
     C = features.shape[1]
+    det = resolve_deterministic(_env_deterministic() if deterministic is None else deterministic)
     with _nvq.device_guard(features.device):
-        return _ops.ToNCHW.apply(_ops.Warp.apply(_ops.ToNHWC.apply(features), _ops.ToNHWC.apply(flow), C), C)
+        return _ops.ToNCHW.apply(_ops.Warp.apply(_ops.ToNHWC.apply(features), _ops.ToNHWC.apply(flow), C, det), C)
 
 
 class _SRFunction(torch.autograd.Function):
@@ -162,10 +175,11 @@ class _SRFunction(torch.autograd.Function):
         need_grad = any(ctx.needs_input_grad[3:])
         ctx.net = net
         ctx.graph = ctx.token = None
+        ctx.deterministic = resolve_deterministic(net.deterministic)
         if need_grad:
             net._mark_awaiting(ctx)
         if net._graphs_wanted(frames) and not want_inter:
-            hit = net._step_graphs.forward(net, frames, need_grad, act)
+            hit = net._step_graphs.forward(net, frames, need_grad, act, ctx.deterministic)
             if hit is not None:
                 out, entry, ctx.token, gen = hit
                 ctx.graph = (entry, gen) if need_grad else None
@@ -189,7 +203,7 @@ class _SRFunction(torch.autograd.Function):
                                    "the same forward needs net.retain_backward_state = True, the analogue of retain_graph)")
             flat, views = net._new_grad_bucket()
             with torch.cuda.device(dout.device):
-                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), views)
+                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), views, deterministic=ctx.deterministic)
             # A custom Function cannot see retain_graph, and the state of a 540p step is tens of GB that must not outlive
             # the backward (autograd frees its own saved tensors here too), so it is dropped unless the module asks to keep it.
             if not getattr(net, "retain_backward_state", False):
@@ -243,6 +257,10 @@ class SuperResolutionNet(BucketedNet):
         env = os.environ.get("NVQ_GRAPH", "0").lower()
         self.use_hip_graphs = True if env in ("1", "on", "true") else "auto" if env == "auto" else False
         self._step_graphs = _graphs.StepGraphs()
+        # Deterministic training (the warp gradient without float atomics, nvq_warp_backward_ex; every other kernel of the
+        # step sums in a fixed order already): None follows torch.are_deterministic_algorithms_enabled() at every forward,
+        # True / False force it.  NVQ_DETERMINISTIC=1 sets True for unmodified caller scripts.
+        self.deterministic: Optional[bool] = _env_deterministic()
 
     GRAPH_AUTO_MAX_PIXELS = 8 * 3 * 128 * 128     # B*T*H*W up to which a step is launch-bound on MI355X
 

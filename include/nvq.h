@@ -357,6 +357,22 @@ int nvq_warp_backward(const float* dout, int dout_ld, int dout_coff, const float
                       float* dfeat, int dfeat_ld, float* dflow, int dflow_ld,
                       float* records, size_t records_bytes, int feat_bf16, int dout_bf16, int overwrite, int dfeat_bf16,
                       void* stream);
+/* nvq_warp_backward with a flags word.  flags == 0: exactly nvq_warp_backward (workspace unused).
+ * NVQ_WARP_DETERMINISTIC (gather form in the overwrite mode only; anything else is NVQ_EINVAL): no float atomics - the
+ * sources that move 4 px or more are binned by destination tile and gathered, so that every element of dfeat is one fp32
+ * sum (window sources in scan order, then those far sources in ascending source-pixel index, then the window sources past
+ * the per-pixel list, in scan order) stored once: bit-identical from run to run and independent of the other images of the
+ * batch; a bf16 dfeat is rounded once.  dflow is bit-identical to nvq_warp_backward's.  workspace: device memory of
+ * nvq_warp_backward_workspace_bytes(N, H, W, flags) = 4 * (3 * tiles + 9 * N*H*W) bytes with tiles =
+ * N * ceil(H/8) * ceil(W/32) (0 without the flag), 4-byte aligned, no initialisation needed; sized for every source being
+ * far, no host synchronisation (graph-capturable).  N*H*W < 2^29, H and W < 32767. */
+#define NVQ_WARP_DETERMINISTIC 1
+size_t nvq_warp_backward_workspace_bytes(int N, int H, int W, int flags);
+int nvq_warp_backward_ex(const float* dout, int dout_ld, int dout_coff, const float* feat,
+                         int feat_ld, const float* flow, int flow_ld, int C, int N, int H, int W,
+                         float* dfeat, int dfeat_ld, float* dflow, int dflow_ld,
+                         float* records, size_t records_bytes, int feat_bf16, int dout_bf16, int overwrite,
+                         int dfeat_bf16, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ temporal aggregation
  * TemporalAggregator.forward softmax + weighted sum, super_resolution.py:174,203-204:
