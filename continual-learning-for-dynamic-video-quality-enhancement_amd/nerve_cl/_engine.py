@@ -393,9 +393,11 @@ def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, m
 
 
 def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
-             deterministic: bool = False) -> None:
+             deterministic: bool = False, dframes: Optional[torch.Tensor] = None) -> None:
     """Write the gradient of every parameter into G[name] (each exactly once, overwrite).  deterministic: the warp gradient
-    without float atomics for any flow (every other kernel of the backward sums in a fixed order already)."""
+    without float atomics for any flow (every other kernel of the backward sums in a fixed order already).
+    dframes (B,T,Cimg,H,W) fp32: also write the gradient w.r.t. the input frames (overwrite) - two launches behind the
+    parameter gradients, which stay exactly what they are without it."""
     if sv.feat0 is None:
         raise RuntimeError("forward(features=...) is an inference path: its result cannot be differentiated")
     g = sv.g
@@ -645,6 +647,15 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
                      G["feature_extractor.head.0.bias"], ws, dout2=dfeat_all)
     if small:
         wq.flush()
+    if dframes is not None:
+        # the head conv's input gradient for all T frames (same operands as its weight gradient above), then the bicubic
+        # skip's adjoint onto the centre frame, masked by the clamp
+        wh = P["feature_extractor.head.0.weight"]
+        if sv.img8 is not None:
+            K.head_dgrad(dcur, wh, B, g.slots, dframes)
+        else:
+            K.head_dgrad(dcur, wh, B, g.slots, dframes, act=sv.feat0, dout2=dfeat_all)
+        K.bicubic_adjoint(dout, sv.passmask, g.s, c, 1.0, dframes, accumulate=True)
 
 
 # ----------------------------------------------------------------------------- LightweightSuperResolution
@@ -698,7 +709,9 @@ def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, train
     return out, sv
 
 
-def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor]) -> None:
+def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
+                   dframes: Optional[torch.Tensor] = None) -> None:
+    """dframes (B,1,3,H,W) fp32: also write the gradient w.r.t. the input image (overwrite)."""
     dev = dout.device
     B, _, Cimg, H, W = sv.frames.shape
     F, math, act_dtype = LIGHT_F, sv.math, sv.act_dtype
@@ -723,6 +736,9 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
         K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
         dcur = dx
     K.head_wgrad(sv.frames, [0], dcur, sv.feat0, G["net.0.weight"], G["net.0.bias"], ws)
+    if dframes is not None:
+        K.head_dgrad(dcur, P["net.0.weight"], B, [0], dframes, act=sv.feat0)
+        K.bicubic_adjoint(dout, sv.passmask, sv.scale, 0, 1.0, dframes, accumulate=True)
 
 
 def nhwc_to_nchw(t: torch.Tensor, c: Optional[int] = None, coff: int = 0) -> torch.Tensor:

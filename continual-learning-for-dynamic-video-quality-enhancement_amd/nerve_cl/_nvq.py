@@ -130,6 +130,8 @@ SIGNATURES = {
     "nvq_shuffle_bicubic_clamp": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
     "nvq_shuffle_clamp_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp]),
     "nvq_bicubic_blend": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp]),
+    "nvq_head_dgrad": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, _IP, ci, vp, ci, vp]),
+    "nvq_bicubic_adjoint": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, vp]),
     "nvq_nchw_to_nhwc": (ci, [vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp]),
     "nvq_nhwc_to_nchw": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, cl, vp]),
     "nvq_bn2_workspace_bytes": (sz, [ci]),
@@ -887,6 +889,28 @@ def bicubic_blend(sr: torch.Tensor, frames: torch.Tensor, t_center: int, s: int,
     B, T, Cimg, H, W = frames.shape
     check(lib().nvq_bicubic_blend(ptr(sr), ptr(frames), B, T, t_center, Cimg, H, W, s, float(strength), ptr(out),
                                   stream()), "nvq_bicubic_blend")
+
+
+def head_dgrad(dout: torch.Tensor, weight, B: int, slots: Sequence[int], dframes: torch.Tensor,
+               act: Optional[torch.Tensor] = None, dout2: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """dframes (B,T,Cin,H,W) (+)= input gradient of the head conv for the images of `dout` ([len(slots)*B,H,W,ld], slot
+    order).  act None: dout is the ReLU-masked gradient; else (dout + dout2) masked by act > 0."""
+    _, T, Cin, H, W = dframes.shape
+    F = weight.shape[0]
+    check(lib().nvq_head_dgrad(ptr(dout), dout.shape[-1], is_bf16(dout), ptr(dout2),
+                               dout2.shape[-1] if dout2 is not None else 0, ptr(act), act.shape[-1] if act is not None else 0,
+                               is_bf16(act), ptr(weight), F, B, T, Cin, H, W, int_array(slots), len(slots), ptr(dframes),
+                               int(accumulate), stream()), "nvq_head_dgrad")
+
+
+def bicubic_adjoint(dout: torch.Tensor, passmask: Optional[torch.Tensor], s: int, t_center: int, coef: float,
+                    dframes: torch.Tensor, accumulate: bool = False):
+    """dframes[:, t_center] (+)= coef * bicubic_s^T(dout * passmask); dout (B,C,H*s,W*s), dframes (B,T,C,H,W)."""
+    B, T, Cimg, H, W = dframes.shape
+    assert tuple(dout.shape) == (B, Cimg, H * s, W * s) and dout.dtype == torch.float32
+    assert passmask is None or (passmask.shape == dout.shape and passmask.dtype == torch.uint8)
+    check(lib().nvq_bicubic_adjoint(ptr(dout), ptr(passmask), B, Cimg, H, W, s, T, t_center, float(coef), ptr(dframes),
+                                    int(accumulate), stream()), "nvq_bicubic_adjoint")
 
 
 # ----------------------------------------------------------------------------- helpers

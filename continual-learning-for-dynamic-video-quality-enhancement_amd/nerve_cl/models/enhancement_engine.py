@@ -21,18 +21,25 @@ from nerve_cl.models.super_resolution import LightweightSuperResolution, SuperRe
 
 
 class _BlendFn(torch.autograd.Function):
-    """strength * sr + (1 - strength) * bicubic(frame): one kernel; the frame carries no gradient."""
+    """strength * sr + (1 - strength) * bicubic(frame): one kernel; the frames' gradient is (1 - strength) times the bicubic
+    adjoint of g at t_center (nvq_bicubic_adjoint), zero for the other frames."""
 
     @staticmethod
     def forward(ctx, sr, frames, t_center, scale, strength):
         out = torch.empty_like(sr)
         _nvq.bicubic_blend(sr.contiguous(), frames, t_center, scale, strength, out)
-        ctx.strength = strength
+        ctx.strength, ctx.t_center, ctx.scale = strength, t_center, scale
+        ctx.frames_shape = frames.shape
         return out
 
     @staticmethod
     def backward(ctx, g):
-        return g * ctx.strength, None, None, None, None
+        dframes = None
+        if ctx.needs_input_grad[1]:
+            dframes = torch.zeros(ctx.frames_shape, dtype=torch.float32, device=g.device)
+            with _nvq.device_guard(g.device):
+                _nvq.bicubic_adjoint(g.contiguous().float(), None, ctx.scale, ctx.t_center, 1.0 - ctx.strength, dframes)
+        return g * ctx.strength, dframes, None, None, None
 
 
 @dataclass
@@ -108,7 +115,7 @@ class EnhancementEngine(nn.Module):
         strength = enhancement_strength if enhancement_strength is not None else self.enhancement_strength.item()
         if strength < 1.0 and "super_resolved" in results:
             # blend with the bicubic-upsampled original (reference :172-180)
-            current = _BlendFn.apply(current, frames.detach().to(torch.float32).contiguous(), center_idx,
+            current = _BlendFn.apply(current, frames.to(torch.float32).contiguous(), center_idx,
                                      self.config.scale_factor, float(strength))
         results["enhanced"] = current
         return results

@@ -172,13 +172,16 @@ class _SRFunction(torch.autograd.Function):
     def forward(ctx, net: "SuperResolutionNet", frames: torch.Tensor, want_inter: bool, *params):
         P = net._tensor_dict()
         act = torch.bfloat16 if (net.bf16_activations and net.math_mode == _nvq.MATH_BF16) else torch.float32
-        need_grad = any(ctx.needs_input_grad[3:])
+        # the frames' gradient (input saliency, a trained stage in front of the net) needs the saved state too, also with frozen
+        # parameters
+        need_grad = any(ctx.needs_input_grad[3:]) or ctx.needs_input_grad[1]
         ctx.net = net
         ctx.graph = ctx.token = None
         ctx.deterministic = resolve_deterministic(net.deterministic)
         if need_grad:
             net._mark_awaiting(ctx)
-        if net._graphs_wanted(frames) and not want_inter:
+        # (a step whose frames need a gradient runs eagerly: the captured graphs compute no input gradient)
+        if net._graphs_wanted(frames) and not want_inter and not ctx.needs_input_grad[1]:
             hit = net._step_graphs.forward(net, frames, need_grad, act, ctx.deterministic)
             if hit is not None:
                 out, entry, ctx.token, gen = hit
@@ -195,6 +198,7 @@ class _SRFunction(torch.autograd.Function):
     def backward(ctx, dout):
         net, sv = ctx.net, ctx.sv
         names = net._param_names
+        dframes = None
         if ctx.graph is not None:
             flat, views = net._step_graphs.backward(net, ctx.graph[0], ctx.graph[1], dout)
         else:
@@ -202,15 +206,18 @@ class _SRFunction(torch.autograd.Function):
                 raise RuntimeError("SuperResolutionNet backward called without saved forward state (a second backward through "
                                    "the same forward needs net.retain_backward_state = True, the analogue of retain_graph)")
             flat, views = net._new_grad_bucket()
+            dframes = torch.empty_like(sv.frames) if ctx.needs_input_grad[1] else None
             with torch.cuda.device(dout.device):
-                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), views, deterministic=ctx.deterministic)
+                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), views, deterministic=ctx.deterministic,
+                                 dframes=dframes)
             # A custom Function cannot see retain_graph, and the state of a 540p step is tens of GB that must not outlive
             # the backward (autograd frees its own saved tensors here too), so it is dropped unless the module asks to keep it.
             if not getattr(net, "retain_backward_state", False):
                 ctx.sv = None
-        # data-parallel all-reduce of the whole bucket (nerve_cl.parallel), then the deferred EWC penalty gradient
+        # data-parallel all-reduce of the whole bucket (nerve_cl.parallel), then the deferred EWC penalty gradient; the frames'
+        # gradient is local to the rank and stays out of the bucket
         net._finish_bucket(flat)
-        return (None, None, None) + tuple(views[n] for n in names)
+        return (None, dframes, None) + tuple(views[n] for n in names)
 
 
 class SuperResolutionNet(BucketedNet):
@@ -282,7 +289,8 @@ class SuperResolutionNet(BucketedNet):
             raise RuntimeError(f"expected {self._Cimg} image channels, got {C}")
         if H < 2 or W < 2:
             raise RuntimeError("frames must be at least 2x2 (grid_sample normalisation divides by size-1)")
-        frames = lr_frames.detach().to(torch.float32).contiguous()
+        # (not detached: autograd chains the cast / copy back to the caller's tensor when it needs a gradient)
+        frames = lr_frames.to(torch.float32).contiguous()
         params = [p for _, p in named]
         with torch.cuda.device(frames.device):      # the kernels launch on the CURRENT device's stream
             out = _SRFunction.apply(self, frames, bool(return_intermediate), *params)
@@ -346,7 +354,7 @@ class _LightFunction(torch.autograd.Function):
         act = torch.bfloat16 if (net.bf16_activations and net.math_mode == _nvq.MATH_BF16) else torch.float32
         out, sv = _engine.light_forward(net._tensor_dict(), x, net.scale_factor, net.training, net.math_mode, act)
         ctx.net = net
-        ctx.sv = sv if any(ctx.needs_input_grad[2:]) else None
+        ctx.sv = sv if (any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[1]) else None
         if ctx.sv is not None:
             net._mark_awaiting(ctx)
         return out
@@ -357,12 +365,14 @@ class _LightFunction(torch.autograd.Function):
         if sv is None:
             raise RuntimeError("LightweightSuperResolution backward called without saved forward state")
         flat, views = net._new_grad_bucket()
+        dframes = torch.empty_like(sv.frames) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(dout.device):
-            _engine.light_backward(net._tensor_dict(), sv, dout.contiguous().float(), views)
+            _engine.light_backward(net._tensor_dict(), sv, dout.contiguous().float(), views, dframes=dframes)
         if not getattr(net, "retain_backward_state", False):
             ctx.sv = None
         net._finish_bucket(flat)
-        return (None, None) + tuple(views[n] for n in net._param_names)
+        dx = dframes.view(dframes.shape[0], *dframes.shape[2:]) if dframes is not None else None
+        return (None, dx) + tuple(views[n] for n in net._param_names)
 
 
 class LightweightSuperResolution(BucketedNet):
@@ -392,4 +402,4 @@ class LightweightSuperResolution(BucketedNet):
             raise RuntimeError(f"expected (B,3,H,W), got {tuple(x.shape)}")
         params = [p for _, p in named]
         with torch.cuda.device(x.device):
-            return _LightFunction.apply(self, x.detach().to(torch.float32).contiguous(), *params)
+            return _LightFunction.apply(self, x.to(torch.float32).contiguous(), *params)

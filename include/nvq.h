@@ -456,6 +456,24 @@ int nvq_bicubic_blend(const float* sr, const float* frames, int B, int T, int t_
 int nvq_shuffle_clamp_backward(const float* dout, const uint8_t* pass, int B, int Cimg, int H,
                                int W, int s, float* du, int du_ld, void* stream);
 
+/* ------------------------------------------------------------------ input gradients (frames)
+ * Input gradient of FeatureExtractor.head / LightweightSuperResolution net.0 (3x3 conv, F -> Cin, Cin in {1, 3}):
+ * dframes[b, t, ci, y, x] (+= if accumulate) = sum_{f,ky,kx} g[slot*B+b, y+1-ky, x+1-kx, f] * weight[f, ci, ky, kx],
+ * frame t = t_of_slot[slot], dframes fp32 (B,T,Cin,H,W) contiguous.  g: dout as given when act == NULL (the pre-masked
+ * gradient of the bf16 path), else (dout + dout2) where act > 0 (dout2 may be NULL), the operands nvq_head_wgrad takes.
+ * dout / act: fp32 or bf16 (*_bf16) NHWC [nslots*B][H][W][ld], dout2 fp32; ld % 8 == 0, 16-B aligned; F % 16 == 0, <= 256.
+ * Every output element is summed by one thread in a fixed order (no atomics): bit-reproducible. */
+int nvq_head_dgrad(const float* dout, int dout_ld, int dout_bf16, const float* dout2, int dout2_ld,
+                   const float* act, int act_ld, int act_bf16, const float* weight, int F,
+                   int B, int T, int Cin, int H, int W, const int* t_of_slot_host, int nslots,
+                   float* dframes, int accumulate, void* stream);
+/* Adjoint of the bicubic skip (F.interpolate(frames[:, t_center], scale_factor=s, bicubic, align_corners=False)):
+ * dframes[b, t_center, c] (+= if accumulate) = coef * B^T (dout * pass); dout fp32 (B,Cimg,H*s,W*s), pass uint8 of the same
+ * layout or NULL (no mask), dframes fp32 (B,T,Cimg,H,W).  Gather form, every LR pixel summed by one thread in a fixed
+ * order, clamped border taps included (no atomics).  s in 1..4. */
+int nvq_bicubic_adjoint(const float* dout, const uint8_t* pass, int B, int Cimg, int H, int W, int s,
+                        int T, int t_center, float coef, float* dframes, int accumulate, void* stream);
+
 /* nn.PixelShuffle(s) alone (stand-alone PixelShuffleUpsampler, efficient_layers.py:101-106):
  * img[b,c,h*s+i,w*s+j] = u[b,h,w,c*s*s+i*s+j] (backward != 0: the other direction, padding channels of u zeroed) */
 int nvq_pixel_shuffle(float* u, int u_ld, int B, int C, int H, int W, int s, float* img, int backward,
