@@ -1,6 +1,8 @@
 // Input gradients of the SR networks: the head conv's input gradient (nvq_head_dgrad) and the adjoint of the bicubic skip
-// (nvq_bicubic_adjoint).  Both are gather kernels: every output element is owned by one thread and summed in a fixed order
-// (no atomics), so the frames' gradient is bit-identical from run to run.
+// (nvq_bicubic_adjoint); of FrameRecoveryNet: the first temporal conv's input gradient in the time-in-channels layout
+// (nvq_head_dgrad_tc), the 7x7 stride-2 stem's input gradient (nvq_stem7_dgrad) and the blend's frame / mask gradient
+// (nvq_mask_blend_backward_ex).  All are gather kernels: every output element is owned by one thread and summed in a fixed
+// order (no atomics), so the inputs' gradient is bit-identical from run to run.
 #include "common.h"
 
 namespace nvq {
@@ -15,7 +17,8 @@ constexpr int DG_TW = 32, DG_TH = 8;
 constexpr int DG_HW = DG_TW + 2, DG_HH = DG_TH + 2, DG_HP = DG_HW * DG_HH;   // halo tile: 34 x 10 = 340 pixels
 constexpr int DG_CC = 16;                                                     // channels per LDS chunk
 
-struct DgSlots { int t[NVQ_MAX_T]; };
+// slot s: frame t[s] of dframes, read from images s * slot_images + b of g at channel offset c[s]
+struct DgSlots { int t[NVQ_MAX_T]; int c[NVQ_MAX_T]; };
 
 // 8 channels at element `idx` (16-B aligned in either storage type) as fp32
 __device__ __forceinline__ void ld8(const float* base, size_t idx, int is_bf16, float v[8]) {
@@ -34,8 +37,8 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const float* __restrict
                                                          const float* __restrict__ dout2, int dout2_ld,
                                                          const float* __restrict__ act, int act_ld, int act_bf16,
                                                          const float* __restrict__ weight, int F, int B, int T, int H,
-                                                         int W, DgSlots sm, float* __restrict__ dframes, int accumulate,
-                                                         int tilesX) {
+                                                         int W, DgSlots sm, int slot_images, float* __restrict__ dframes,
+                                                         int accumulate, int tilesX) {
     __shared__ float gs[DG_CC][DG_HP];
     __shared__ float ws[DG_CC][CIN][9];
     const int tid = threadIdx.x;
@@ -46,7 +49,8 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const float* __restrict
     float acc[CIN];
 #pragma unroll
     for (int c = 0; c < CIN; ++c) acc[c] = 0.f;
-    const size_t pix0 = (size_t)img * H * W;
+    const size_t pix0 = ((size_t)slot * slot_images + b) * H * W;
+    const int cofs = sm.c[slot];
     for (int f0 = 0; f0 < F; f0 += DG_CC) {
         __syncthreads();                         // the previous chunk's readers are done
         // stage: unit = (halo pixel, 8-channel half of the chunk); 680 units over 256 threads
@@ -59,7 +63,7 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const float* __restrict
             for (int k = 0; k < 8; ++k) v[k] = 0.f;
             if (y >= 0 && y < H && x >= 0 && x < W) {
                 const size_t q = pix0 + (size_t)y * W + x;
-                ld8(dout, q * dout_ld + f0 + h8, dout_bf16, v);
+                ld8(dout, q * dout_ld + cofs + f0 + h8, dout_bf16, v);
                 if (act) {
                     float a[8];
                     ld8(act, q * act_ld + f0 + h8, act_bf16, a);
@@ -187,9 +191,143 @@ __global__ __launch_bounds__(256) void bicubic_adjoint_kernel(const float* __res
     *o = accumulate ? *o + coef * acc : coef * acc;
 }
 
+// ------------------------------------------------------------------ FrameRecoveryNet: stem input gradient
+// Adjoint of nn.Conv2d(4, Co, 7, 2, 3): dx[n, iy, ix, ci] = sum_{co, ky, kx} dy[n, oy, ox, co] * w[co, ci, ky, kx] over
+// oy = (iy + 3 - ky) / 2, ox = (ix + 3 - kx) / 2 where those are integers in range, i.e. only the taps with
+// ky = iy + 3 (mod 2) (3 or 4 per dimension).
+// One workgroup: an SD_TH x SD_TW input tile of one image, one thread per input pixel (all 4 channels).  dy is staged chunk
+// by chunk (SD_CC channels) with its halo in LDS, channel-major; the chunk's weights sit in LDS as [f][tap] float4s (the 4
+// input channels) and are read as broadcasts.  Lanes are mapped so that every wave owns pixels of one (row, column)
+// parity: the tap loops are then the same for all lanes of a wave.  Sum order: chunks ascending, f, ky, kx.
+constexpr int SD_TW = 32, SD_TH = 8;
+constexpr int SD_HW = SD_TW / 2 + 3, SD_HH = SD_TH / 2 + 3, SD_HP = SD_HW * SD_HH;   // halo tile: 19 x 7 = 133 pixels
+constexpr int SD_CC = 16;
+
+__global__ __launch_bounds__(256) void stem7_dgrad_kernel(const float* __restrict__ dy, int dy_ld, int dy_bf16,
+                                                          const float* __restrict__ weight, int Co, int H, int W, int OH,
+                                                          int OW, float* __restrict__ dframe, float* __restrict__ dmask,
+                                                          int accumulate, int tilesX) {
+    __shared__ float gs[SD_CC][SD_HP];
+    __shared__ float4 ws[SD_CC][49];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int n = blockIdx.y;
+    const int ix0 = (blockIdx.x % tilesX) * SD_TW, iy0 = (blockIdx.x / tilesX) * SD_TH;
+    const int oy0 = iy0 / 2 - 1, ox0 = ix0 / 2 - 1;            // halo origin (iy0, ix0 even)
+    const int ty = 2 * (lane >> 4) + (wave >> 1), tx = 2 * (lane & 15) + (wave & 1);
+    const int kyp = ((wave >> 1) + 1) & 1, kxp = ((wave & 1) + 1) & 1;   // first tap of the pixel's parity (wave-uniform)
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const size_t pix0 = (size_t)n * OH * OW;
+    for (int f0 = 0; f0 < Co; f0 += SD_CC) {
+        __syncthreads();                         // the previous chunk's readers are done
+        // stage: unit = (halo pixel, 8-channel half of the chunk); 266 units over 256 threads
+        for (int u = tid; u < SD_HP * 2; u += 256) {
+            const int p = u >> 1, h8 = (u & 1) * 8;
+            const int hy = p / SD_HW, hx = p - hy * SD_HW;
+            const int oy = oy0 + hy, ox = ox0 + hx;
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = 0.f;
+            if (oy >= 0 && oy < OH && ox >= 0 && ox < OW) ld8(dy, (pix0 + (size_t)oy * OW + ox) * dy_ld + f0 + h8, dy_bf16, v);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gs[h8 + k][p] = v[k];
+        }
+        for (int e = tid; e < SD_CC * 49; e += 256) {
+            const int f = e / 49, t = e - f * 49;
+            const float* wr = weight + (size_t)(f0 + f) * 196 + t;
+            ws[f][t] = make_float4(wr[0], wr[49], wr[98], wr[147]);
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int f = 0; f < SD_CC; ++f) {
+#pragma unroll
+            for (int jy = 0; jy < 4; ++jy) {
+                const int ky = kyp + 2 * jy;
+                if (ky < 7) {
+                    const int ry = (ty + 5 - ky) >> 1;
+#pragma unroll
+                    for (int jx = 0; jx < 4; ++jx) {
+                        const int kx = kxp + 2 * jx;
+                        if (kx < 7) {
+                            const float gv = gs[f][ry * SD_HW + ((tx + 5 - kx) >> 1)];
+                            const float4 w4 = ws[f][ky * 7 + kx];
+                            acc[0] = fmaf(gv, w4.x, acc[0]);
+                            acc[1] = fmaf(gv, w4.y, acc[1]);
+                            acc[2] = fmaf(gv, w4.z, acc[2]);
+                            acc[3] = fmaf(gv, w4.w, acc[3]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const int iy = iy0 + ty, ix = ix0 + tx;
+    if (iy < H && ix < W) {
+        const size_t hw = (size_t)H * W, q = (size_t)iy * W + ix;
+        if (dframe) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float* o = dframe + ((size_t)n * 3 + c) * hw + q;
+                *o = accumulate ? *o + acc[c] : acc[c];
+            }
+        }
+        if (dmask) {
+            float* o = dmask + (size_t)n * hw + q;
+            *o = accumulate ? *o + acc[3] : acc[3];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ FrameRecoveryNet: blend backward with input gradients
+// out = frame * (1 - m) + rec * m: drec[n, p, c] = dout * m (channels [C, ld) = 0), dframe = dout * (1 - m),
+// dmask[n, p] = sum_c dout * (rec - frame) (c ascending, one thread per pixel)
+__global__ __launch_bounds__(256) void mask_blend_bwd_ex_kernel(const float* __restrict__ dout, const float* __restrict__ frame,
+                                                                const float* __restrict__ rec, const float* __restrict__ mask,
+                                                                int C, long HW, long total, float* __restrict__ drec, int ld,
+                                                                float* __restrict__ dframe, float* __restrict__ dmask) {
+    const long gid = blockIdx.x * 256L + threadIdx.x;
+    if (gid >= total) return;                       // total = N * HW
+    const long n = gid / HW, p = gid % HW;
+    const float m = mask[gid];
+    float dm = 0.f;
+    for (int c = 0; c < ld; ++c) {
+        if (c < C) {
+            const long e = (n * C + c) * HW + p;
+            const float d = dout[e];
+            drec[gid * ld + c] = d * m;
+            if (dframe) dframe[e] = d * (1.f - m);
+            if (dmask) dm = fmaf(d, rec[gid * ld + c] - frame[e], dm);
+        } else {
+            drec[gid * ld + c] = 0.f;
+        }
+    }
+    if (dmask) dmask[gid] = dm;
+}
+
 }  // namespace nvq
 
 using namespace nvq;
+
+namespace {
+
+int launch_head_dgrad(const char* what, const float* dout, int dout_ld, int dout_bf16, const float* dout2, int dout2_ld,
+                      const float* act, int act_ld, int act_bf16, const float* weight, int F, int B, int T, int Cin, int H,
+                      int W, const DgSlots& sm, int nslots, int slot_images, float* dframes, int accumulate, void* stream) {
+    const int tilesX = (W + DG_TW - 1) / DG_TW, tilesY = (H + DG_TH - 1) / DG_TH;
+    const long ntiles = (long)tilesX * tilesY, nimg = (long)nslots * B;
+    NVQ_REQUIRE(ntiles < ((long)1 << 31) && nimg <= 65535, "%s: grid too large", what);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)ntiles, (unsigned)nimg);
+    if (Cin == 3)
+        hipLaunchKernelGGL((head_dgrad_kernel<3>), grid, dim3(256), 0, s, dout, dout_ld, dout_bf16, dout2, dout2_ld, act,
+                           act_ld, act_bf16, weight, F, B, T, H, W, sm, slot_images, dframes, accumulate, tilesX);
+    else
+        hipLaunchKernelGGL((head_dgrad_kernel<1>), grid, dim3(256), 0, s, dout, dout_ld, dout_bf16, dout2, dout2_ld, act,
+                           act_ld, act_bf16, weight, F, B, T, H, W, sm, slot_images, dframes, accumulate, tilesX);
+    return check_launch(what);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -209,20 +347,61 @@ int nvq_head_dgrad(const float* dout, int dout_ld, int dout_bf16, const float* d
     DgSlots sm;
     for (int i = 0; i < NVQ_MAX_T; ++i) {
         sm.t[i] = i < nslots ? t_of_slot_host[i] : 0;
+        sm.c[i] = 0;
         NVQ_REQUIRE(sm.t[i] >= 0 && sm.t[i] < T, "head_dgrad: slot %d maps to frame %d of %d", i, sm.t[i], T);
     }
-    const int tilesX = (W + DG_TW - 1) / DG_TW, tilesY = (H + DG_TH - 1) / DG_TH;
-    const long ntiles = (long)tilesX * tilesY, nimg = (long)nslots * B;
-    NVQ_REQUIRE(ntiles < ((long)1 << 31) && nimg <= 65535, "head_dgrad: grid too large");
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)ntiles, (unsigned)nimg);
-    if (Cin == 3)
-        hipLaunchKernelGGL((head_dgrad_kernel<3>), grid, dim3(256), 0, s, dout, dout_ld, dout_bf16, dout2, dout2_ld, act,
-                           act_ld, act_bf16, weight, F, B, T, H, W, sm, dframes, accumulate, tilesX);
-    else
-        hipLaunchKernelGGL((head_dgrad_kernel<1>), grid, dim3(256), 0, s, dout, dout_ld, dout_bf16, dout2, dout2_ld, act,
-                           act_ld, act_bf16, weight, F, B, T, H, W, sm, dframes, accumulate, tilesX);
-    return check_launch("head_dgrad");
+    return launch_head_dgrad("head_dgrad", dout, dout_ld, dout_bf16, dout2, dout2_ld, act, act_ld, act_bf16, weight, F, B,
+                             T, Cin, H, W, sm, nslots, B, dframes, accumulate, stream);
+}
+
+int nvq_head_dgrad_tc(const float* dout, int dout_ld, int dout_bf16, const float* weight, int F, int B, int T, int Cin,
+                      int H, int W, const int* t_of_slot_host, const int* coff_of_slot_host, int nslots, int slot_images,
+                      float* dframes, int accumulate, void* stream) {
+    NVQ_REQUIRE(Cin == 3 || Cin == 1, "head_dgrad_tc: in_channels %d not supported (1 or 3)", Cin);
+    NVQ_REQUIRE(F >= DG_CC && F <= 256 && F % DG_CC == 0, "head_dgrad_tc: F %d (a multiple of %d in [16, 256])", F, DG_CC);
+    NVQ_REQUIRE(B >= 1 && H >= 1 && W >= 1, "head_dgrad_tc: B %d H %d W %d", B, H, W);
+    NVQ_REQUIRE(nslots >= 1 && nslots <= NVQ_MAX_T && T >= 1 && T <= NVQ_MAX_T, "head_dgrad_tc: T %d slots %d", T, nslots);
+    NVQ_REQUIRE(slot_images == 0 || slot_images == B, "head_dgrad_tc: slot_images %d (0 or B = %d)", slot_images, B);
+    NVQ_REQUIRE(dout && weight && dframes, "head_dgrad_tc: NULL dout / weight / dframes");
+    NVQ_REQUIRE(dout_ld % 8 == 0 && aligned16(dout), "head_dgrad_tc: dout ld %d / alignment", dout_ld);
+    DgSlots sm;
+    for (int i = 0; i < NVQ_MAX_T; ++i) {
+        sm.t[i] = i < nslots ? t_of_slot_host[i] : 0;
+        sm.c[i] = i < nslots ? coff_of_slot_host[i] : 0;
+        NVQ_REQUIRE(sm.t[i] >= 0 && sm.t[i] < T, "head_dgrad_tc: slot %d maps to frame %d of %d", i, sm.t[i], T);
+        NVQ_REQUIRE(sm.c[i] >= 0 && sm.c[i] % 8 == 0 && sm.c[i] + F <= dout_ld,
+                    "head_dgrad_tc: slot %d channel offset %d (a multiple of 8, + F %d <= ld %d)", i, sm.c[i], F, dout_ld);
+    }
+    return launch_head_dgrad("head_dgrad_tc", dout, dout_ld, dout_bf16, nullptr, 0, nullptr, 0, 0, weight, F, B, T, Cin, H,
+                             W, sm, nslots, slot_images, dframes, accumulate, stream);
+}
+
+int nvq_stem7_dgrad(const float* dy, int dy_ld, int dy_bf16, const float* weight, int N, int H, int W, int Co,
+                    float* dframe, float* dmask, int accumulate, void* stream) {
+    NVQ_REQUIRE(Co >= SD_CC && Co <= 64 && Co % SD_CC == 0, "stem7_dgrad: Co %d (a multiple of %d in [16, 64])", Co, SD_CC);
+    NVQ_REQUIRE(N >= 1 && N <= 65535 && H >= 1 && W >= 1, "stem7_dgrad: N %d H %d W %d", N, H, W);
+    NVQ_REQUIRE(dy && weight, "stem7_dgrad: NULL dy / weight");
+    NVQ_REQUIRE(dframe || dmask, "stem7_dgrad: NULL dframe and dmask (nothing to write)");
+    NVQ_REQUIRE(dy_ld >= Co && dy_ld % 8 == 0 && aligned16(dy), "stem7_dgrad: dy ld %d / alignment", dy_ld);
+    const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+    const int tilesX = (W + SD_TW - 1) / SD_TW, tilesY = (H + SD_TH - 1) / SD_TH;
+    const long ntiles = (long)tilesX * tilesY;
+    NVQ_REQUIRE(ntiles < ((long)1 << 31), "stem7_dgrad: grid too large");
+    hipLaunchKernelGGL(stem7_dgrad_kernel, dim3((unsigned)ntiles, (unsigned)N), dim3(256), 0, (hipStream_t)stream, dy, dy_ld,
+                       dy_bf16, weight, Co, H, W, OH, OW, dframe, dmask, accumulate, tilesX);
+    return check_launch("stem7_dgrad");
+}
+
+int nvq_mask_blend_backward_ex(const float* dout, const float* frame, const float* rec, int rec_ld, const float* mask, int N,
+                               int C, int H, int W, float* drec, float* dframe, float* dmask, void* stream) {
+    NVQ_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1 && C <= rec_ld, "mask_blend_backward_ex: N %d C %d H %d W %d ld %d", N,
+                C, H, W, rec_ld);
+    NVQ_REQUIRE(dout && mask && drec, "mask_blend_backward_ex: NULL dout / mask / drec");
+    NVQ_REQUIRE(!dmask || (frame && rec), "mask_blend_backward_ex: dmask needs frame and rec");
+    const long HW = (long)H * W, total = (long)N * HW;
+    hipLaunchKernelGGL(mask_blend_bwd_ex_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dout, frame,
+                       rec, mask, C, HW, total, drec, rec_ld, dframe, dmask);
+    return check_launch("mask_blend_backward_ex");
 }
 
 int nvq_bicubic_adjoint(const float* dout, const uint8_t* pass, int B, int Cimg, int H, int W, int s, int T, int t_center,

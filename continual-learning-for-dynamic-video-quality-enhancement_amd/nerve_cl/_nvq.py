@@ -132,6 +132,9 @@ SIGNATURES = {
     "nvq_bicubic_blend": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp]),
     "nvq_head_dgrad": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, _IP, ci, vp, ci, vp]),
     "nvq_bicubic_adjoint": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, vp]),
+    "nvq_head_dgrad_tc": (ci, [vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, _IP, _IP, ci, ci, vp, ci, vp]),
+    "nvq_stem7_dgrad": (ci, [vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, ci, vp]),
+    "nvq_mask_blend_backward_ex": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
     "nvq_nchw_to_nhwc": (ci, [vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp]),
     "nvq_nhwc_to_nchw": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, cl, vp]),
     "nvq_bn2_workspace_bytes": (sz, [ci]),
@@ -911,6 +914,36 @@ def bicubic_adjoint(dout: torch.Tensor, passmask: Optional[torch.Tensor], s: int
     assert passmask is None or (passmask.shape == dout.shape and passmask.dtype == torch.uint8)
     check(lib().nvq_bicubic_adjoint(ptr(dout), ptr(passmask), B, Cimg, H, W, s, T, t_center, float(coef), ptr(dframes),
                                     int(accumulate), stream()), "nvq_bicubic_adjoint")
+
+
+def head_dgrad_tc(dout: torch.Tensor, weight, B: int, slots: Sequence[int], coffs: Sequence[int], slot_images: int,
+                  dframes: torch.Tensor, accumulate: bool = False):
+    """dframes (B,T,Cin,H,W) (+)= input gradient of a 3x3 conv (weight [F,Cin,3,3]) for the pre-masked gradient `dout`
+    ([N,H,W,ld]): slot s = frame slots[s], read from images s * slot_images + b at channels coffs[s] .. + F."""
+    _, T, Cin, H, W = dframes.shape
+    check(lib().nvq_head_dgrad_tc(ptr(dout), dout.shape[-1], is_bf16(dout), ptr(weight), weight.shape[0], B, T, Cin, H, W,
+                                  int_array(slots), int_array(coffs), len(slots), slot_images, ptr(dframes), int(accumulate),
+                                  stream()), "nvq_head_dgrad_tc")
+
+
+def stem7_dgrad(dy: torch.Tensor, weight, dframe: Optional[torch.Tensor], dmask: Optional[torch.Tensor], H: int, W: int,
+                accumulate: bool = False):
+    """input gradient of nn.Conv2d(4, Co, 7, 2, 3) (weight [Co,4,7,7]) for dy [N,OH,OW,ld]: channels 0..2 (+)= into
+    dframe (N,3,H,W), channel 3 into dmask (N,1,H,W); either may be None"""
+    N = dy.shape[0]
+    for t, c in ((dframe, 3), (dmask, 1)):
+        assert t is None or (tuple(t.shape) == (N, c, H, W) and t.dtype == torch.float32)
+    check(lib().nvq_stem7_dgrad(ptr(dy), dy.shape[-1], is_bf16(dy), ptr(weight), N, H, W, weight.shape[0], ptr(dframe),
+                                ptr(dmask), int(accumulate), stream()), "nvq_stem7_dgrad")
+
+
+def mask_blend_backward_ex(dout: torch.Tensor, frame: torch.Tensor, rec: torch.Tensor, mask: torch.Tensor, drec: torch.Tensor,
+                           dframe: Optional[torch.Tensor], dmask: Optional[torch.Tensor]):
+    """backward of out = frame * (1 - m) + rec * m: drec [N,H,W,ld] = dout * m, dframe = dout * (1 - m),
+    dmask = sum_c dout * (rec - frame) (dframe / dmask None: not written)"""
+    N, C, H, W = dout.shape
+    check(lib().nvq_mask_blend_backward_ex(ptr(dout), ptr(frame), ptr(rec), rec.shape[-1], ptr(mask), N, C, H, W, ptr(drec),
+                                           ptr(dframe), ptr(dmask), stream()), "nvq_mask_blend_backward_ex")
 
 
 # ----------------------------------------------------------------------------- helpers

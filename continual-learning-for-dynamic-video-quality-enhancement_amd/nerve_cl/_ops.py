@@ -41,6 +41,16 @@ def _bf(t: torch.Tensor) -> int:
     return int(t.dtype == torch.bfloat16)
 
 
+class InputGradSink:
+    """Where the backward of the ops at FrameRecoveryNet's edge writes the gradient of the network's image inputs (each
+    fp32, NCHW, or None when that input needs none): MaskBlend writes dframe / dmask, Stem7 adds its share to them (it runs
+    after MaskBlend: its gradient comes through the blend), the first temporal conv writes drefs (B,T,3,H,W)."""
+    __slots__ = ("dframe", "drefs", "dmask")
+
+    def __init__(self, dframe: Optional[torch.Tensor], drefs: Optional[torch.Tensor], dmask: Optional[torch.Tensor]):
+        self.dframe, self.drefs, self.dmask = dframe, drefs, dmask
+
+
 def cast_slice_(dst: torch.Tensor, src: torch.Tensor, C: int, dst_coff: int = 0, src_coff: int = 0, alpha: float = 1.0,
                 accumulate: bool = False) -> None:
     """dst[..., dst_coff:+C] (+)= alpha * src[..., src_coff:+C]; either side fp32 or bf16"""
@@ -123,7 +133,7 @@ class Conv(torch.autograd.Function):
     weight [Co, Ci, k, k] with Ci <= x.ld; output [N,H,W,pad4(Co)]."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu: bool, math: int, out_dtype=None):
+    def forward(ctx, x, weight, bias, relu: bool, math: int, out_dtype=None, sink: Optional[InputGradSink] = None):
         N, H, W, ld = x.shape
         Co, Ci, k, _ = weight.shape
         dt = x.dtype if out_dtype is None else out_dtype
@@ -133,6 +143,9 @@ class Conv(torch.autograd.Function):
         K.conv_forward(Sl(x), wp, bias, Sl(y, Co), k, relu=relu, cout_store=y.shape[-1], math=math)
         ctx.save_for_backward(x, weight, y if relu else None)
         ctx.relu, ctx.math, ctx.has_bias = relu, math, bias is not None
+        # sink (FrameRecoveryNet's first temporal conv, time-major references [T*B,H,W,4]): the input gradient goes to
+        # sink.drefs (B,T,3,H,W) instead of dx
+        ctx.sink = sink if sink is not None and sink.drefs is not None else None
         return y
 
     @staticmethod
@@ -148,11 +161,15 @@ class Conv(torch.autograd.Function):
             g = dy
         dw, db = _wgrad(x, Ci, g, Co, weight.shape, ctx.has_bias, k, ctx.math)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.sink is not None:
+            drefs = ctx.sink.drefs
+            B, T = drefs.shape[:2]
+            K.head_dgrad(g, weight, B, list(range(T)), drefs)
+        elif ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             wt = K.conv_pack(weight, True, g.shape[-1], Ci, math=ctx.math)
             K.conv_forward(Sl(g), wt, None, Sl(dx, Ci), k, cout_store=ld, math=ctx.math)
-        return dx, dw, db, None, None, None
+        return dx, dw, db, None, None, None, None
 
 
 class DwConv(torch.autograd.Function):
@@ -243,7 +260,7 @@ class SpatialConvTC(torch.autograd.Function):
     every frame, reading / writing the frames' channel slices in place."""
 
     @staticmethod
-    def forward(ctx, x, weight, T: int, math: int, out_dtype=None):
+    def forward(ctx, x, weight, T: int, math: int, out_dtype=None, sink: Optional[InputGradSink] = None):
         B, H, W, ld = x.shape
         Cpi = ld // T
         Co, Ci = weight.shape[:2]
@@ -255,6 +272,8 @@ class SpatialConvTC(torch.autograd.Function):
             K.conv_forward(Sl(x, Cpi, t * Cpi), wp, None, Sl(y, Co, t * Cpo), 3, cout_store=Cpo, math=math)
         ctx.save_for_backward(x, weight)
         ctx.T, ctx.math = T, math
+        # sink (FrameRecoveryNet's first temporal conv): the input gradient goes to sink.drefs (B,T,3,H,W) instead of dx
+        ctx.sink = sink if sink is not None and sink.drefs is not None else None
         return y
 
     @staticmethod
@@ -271,12 +290,15 @@ class SpatialConvTC(torch.autograd.Function):
         for t in range(T):
             K.conv_wgrad(Sl(x, Cpi, t * Cpi), Ci, Sl(dy, Cg, t * Cpo), full, None, ws, 3, accumulate=t > 0, math=math)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.sink is not None:
+            # frame t of the gradient sits at channel offset t * Cpo of every image
+            K.head_dgrad_tc(dy, weight, B, list(range(T)), [t * Cpo for t in range(T)], 0, ctx.sink.drefs)
+        elif ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             wt = K.conv_pack(weight, True, Cpo, Ci, math=math)
             for t in range(T):
                 K.conv_forward(Sl(dy, Cpo, t * Cpo), wt, None, Sl(dx, Ci, t * Cpi), 3, cout_store=Cpi, math=math)
-        return dx, full[:Co], None, None, None
+        return dx, full[:Co], None, None, None, None
 
 
 def _tconv_cat(weight, Cp: int, k0: int, nk: int, transpose: bool) -> torch.Tensor:
@@ -423,10 +445,11 @@ class ConvT(torch.autograd.Function):
 
 
 class Stem7(torch.autograd.Function):
-    """nn.Conv2d(4, Co, 7, 2, 3, bias=False) on a 4-channel NHWC image (frame_recovery.py:42-44); the image carries no gradient"""
+    """nn.Conv2d(4, Co, 7, 2, 3, bias=False) on a 4-channel NHWC image x4 = [frame | mask] (frame_recovery.py:42-44).  The
+    image's gradient goes to a sink (channels 0..2 added to sink.dframe, channel 3 to sink.dmask, both NCHW), never to x4."""
 
     @staticmethod
-    def forward(ctx, x4, weight, out_dtype=torch.float32):
+    def forward(ctx, x4, weight, out_dtype=torch.float32, sink: Optional[InputGradSink] = None):
         N, H, W, c = x4.shape
         Co = weight.shape[0]
         assert c == 4 and tuple(weight.shape[1:]) == (4, 7, 7) and Co % 8 == 0
@@ -435,6 +458,9 @@ class Stem7(torch.autograd.Function):
         check(lib().nvq_stem7_forward(ptr(x4), ptr(weight), N, H, W, Co, ptr(y), Co, _bf(y), stream()), "nvq_stem7_forward")
         ctx.save_for_backward(x4)
         ctx.wshape = weight.shape
+        ctx.sink = sink if sink is not None and (sink.dframe is not None or sink.dmask is not None) else None
+        if ctx.sink is not None:
+            ctx.weight = weight
         return y
 
     @staticmethod
@@ -446,7 +472,9 @@ class Stem7(torch.autograd.Function):
         ws = _ws(x4)
         check(lib().nvq_stem7_wgrad(ptr(x4), ptr(dy), dy.shape[-1], N, H, W, ctx.wshape[0], ptr(dw), ptr(ws), ws.numel() * 4,
                                     _bf(dy), stream()), "nvq_stem7_wgrad")
-        return None, dw, None
+        if ctx.sink is not None:
+            K.stem7_dgrad(dy, ctx.weight, ctx.sink.dframe, ctx.sink.dmask, H, W, accumulate=True)
+        return None, dw, None, None
 
 
 # ----------------------------------------------------------------------------- BatchNorm (+ residual) (+ ReLU)
@@ -714,25 +742,34 @@ class Tanh(torch.autograd.Function):
 
 class MaskBlend(torch.autograd.Function):
     """frame * (1 - mask) + rec * mask (frame_recovery.py:439-440): frame (N,C,H,W) and mask (N,1,H,W) are data, rec is
-    [N,H,W,ld]; returns (N,C,H,W)."""
+    [N,H,W,ld]; returns (N,C,H,W).  With a sink the backward also writes (overwrites) sink.dframe = dout * (1 - mask) and
+    sink.dmask = sum_c dout * (rec - frame)."""
 
     @staticmethod
-    def forward(ctx, frame, rec, mask):
+    def forward(ctx, frame, rec, mask, sink: Optional[InputGradSink] = None):
         N, C, H, W = frame.shape
         out = torch.empty_like(frame)
         check(lib().nvq_mask_blend(ptr(frame), ptr(rec), rec.shape[-1], ptr(mask), N, C, H, W, ptr(out), stream()), "nvq_mask_blend")
-        ctx.save_for_backward(mask)
+        ctx.sink = sink if sink is not None and (sink.dframe is not None or sink.dmask is not None) else None
+        if ctx.sink is None:
+            ctx.save_for_backward(mask)
+        else:
+            ctx.save_for_backward(mask, frame, rec)
         ctx.args = (N, C, H, W, rec.shape[-1])
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        (mask,) = ctx.saved_tensors
         N, C, H, W, ld = ctx.args
         drec = _new(dout, N, H, W, ld)
+        if ctx.sink is not None:
+            mask, frame, rec = ctx.saved_tensors
+            K.mask_blend_backward_ex(dout.contiguous(), frame, rec, mask, drec, ctx.sink.dframe, ctx.sink.dmask)
+            return None, drec, None, None
+        (mask,) = ctx.saved_tensors
         check(lib().nvq_mask_blend_backward(ptr(dout.contiguous()), ptr(mask), N, C, H, W, ptr(drec), ld, stream()),
               "nvq_mask_blend_backward")
-        return None, drec, None
+        return None, drec, None, None
 
 
 class PixelShuffleNCHW(torch.autograd.Function):

@@ -45,8 +45,9 @@ class SpatialEncoder(_Holder):
         layers += [ResidualBlock(cout) for _ in range(num_blocks)]
         return Stack(*layers)
 
-    def forward_nhwc(self, x4: torch.Tensor, math: int, act_dtype=torch.float32) -> "Tuple[torch.Tensor, List[torch.Tensor]]":
-        y = _ops.Stem7.apply(x4, self.stem[0].weight, act_dtype)
+    def forward_nhwc(self, x4: torch.Tensor, math: int, act_dtype=torch.float32,
+                     sink: "Optional[_ops.InputGradSink]" = None) -> "Tuple[torch.Tensor, List[torch.Tensor]]":
+        y = _ops.Stem7.apply(x4, self.stem[0].weight, act_dtype, sink)
         y = _ops.bn(y, self.stem[1], self.training, relu=True)
         y = _ops.MaxPool.apply(y, 3, 2, 1)
         skips = [y]
@@ -74,15 +75,15 @@ class TemporalEncoder(_Holder):
         self.conv3 = TemporalConv3D(128, out_channels, temporal_kernel=3)
         self.temporal_pool = Act()
 
-    def forward_nhwc(self, frames: torch.Tensor, T: int, math: int, act_dtype=torch.float32) -> torch.Tensor:
+    def forward_nhwc(self, frames: torch.Tensor, T: int, math: int, act_dtype=torch.float32, sink=None) -> torch.Tensor:
         """frames: time-major image batch [T*B, H, W, 4]"""
-        y = _ops.MaxPool.apply(self.conv1.forward_nhwc(frames, T, math, act_dtype), 2, 2, 0)
+        y = _ops.MaxPool.apply(self.conv1.forward_nhwc(frames, T, math, act_dtype, sink), 2, 2, 0)
         y = _ops.MaxPool.apply(self.conv2.forward_nhwc(y, T, math), 2, 2, 0)
         return _ops.GroupMean.apply(self.conv3.forward_nhwc(y, T, math), T, self.conv3.out_channels)   # fp32 out
 
-    def forward_tc(self, frames_tc: torch.Tensor, T: int, math: int, act_dtype=torch.float32) -> torch.Tensor:
+    def forward_tc(self, frames_tc: torch.Tensor, T: int, math: int, act_dtype=torch.float32, sink=None) -> torch.Tensor:
         """frames_tc: time-in-channels tensor [B, H, W, T*4] (frame t = channels 4t..4t+2); T >= 2"""
-        y = _ops.MaxPool.apply(self.conv1.forward_tc(frames_tc, T, math, act_dtype), 2, 2, 0)
+        y = _ops.MaxPool.apply(self.conv1.forward_tc(frames_tc, T, math, act_dtype, sink), 2, 2, 0)
         y = _ops.MaxPool.apply(self.conv2.forward_tc(y, T, math), 2, 2, 0)
         return _ops.GroupMeanTC.apply(self.conv3.forward_tc(y, T, math), T, self.conv3.out_channels)    # fp32 out
 
@@ -133,23 +134,33 @@ class Decoder(_Holder):
 
 class _FRFunction(torch.autograd.Function):
     """One autograd node for the whole network: runs the layer graph (an inner autograd graph over the libnvq ops), keeps
-    it, and on backward collects its parameter gradients into the flat bucket."""
+    it, and on backward collects its parameter gradients into the flat bucket.  The image inputs' gradients (frame, refs,
+    mask) are written by the ops at the network's edge into an _ops.InputGradSink: they stay out of the bucket (local to
+    the rank)."""
 
     @staticmethod
     def forward(ctx, net: "FrameRecoveryNet", frame, refs, mask, *params):
-        need_grad = any(ctx.needs_input_grad[4:])
+        need_params = any(ctx.needs_input_grad[4:])
+        want = ctx.needs_input_grad[1:4]                 # frame, refs, mask
         ctx.net = net
-        if not need_grad:
+        # the layer graph sees the inputs as data: their gradients come out of the sink, not out of the inner graph
+        frame, refs, mask = frame.detach(), refs.detach(), mask.detach()
+        if not need_params and not any(want):
             ctx.inner = None
             with torch.no_grad():
                 return net._graph(frame, refs, mask)
+        sink = None
+        if any(want):
+            sink = _ops.InputGradSink(*(torch.empty_like(t) if w else None for t, w in zip((frame, refs, mask), want)))
         # Function.forward runs with autograd switched off: switch it back on for the layer graph, whose leaves are the
-        # real parameters (torch.autograd.grad in backward reads their gradients without touching .grad)
+        # real parameters (torch.autograd.grad in backward reads their gradients without touching .grad).  With every
+        # parameter frozen the leaves are the network's NHWC input images instead, so that the graph is still recorded.
         with torch.enable_grad():
-            out = net._graph(frame, refs, mask)
-            leaves = list(params)
-        ctx.inner = (out, leaves)
-        net._mark_awaiting(ctx)
+            leaves = list(params) if need_params else []
+            out = net._graph(frame, refs, mask, sink, None if need_params else leaves)
+        ctx.inner = (out, leaves, sink, need_params)
+        if need_params:
+            net._mark_awaiting(ctx)
         return out.detach()
 
     @staticmethod
@@ -157,10 +168,14 @@ class _FRFunction(torch.autograd.Function):
         net = ctx.net
         if ctx.inner is None:
             raise RuntimeError("FrameRecoveryNet backward called twice (or without saved state)")
-        out, leaves = ctx.inner
+        out, leaves, sink, need_params = ctx.inner
         ctx.inner = None
+        dinputs = (sink.dframe, sink.drefs, sink.dmask) if sink is not None else (None, None, None)
         with _nvq.device_guard(dout.device):
             grads = torch.autograd.grad(out, leaves, dout.contiguous(), allow_unused=True)
+            if not need_params:
+                # frozen parameters: the input gradients alone, no bucket (nothing to all-reduce or finish)
+                return (None,) + dinputs + (None,) * len(net._param_names)
             lay, total = net._bucket_layout()
             pieces, off = [], 0
             for (name, (o, k)), g, leaf in zip(lay.items(), grads, leaves):
@@ -173,7 +188,7 @@ class _FRFunction(torch.autograd.Function):
             flat = torch.cat(pieces)
             net._finish_bucket(flat)
         views = net._bucket_views(flat)
-        return (None, None, None, None) + tuple(views[n] for n in net._param_names)
+        return (None,) + dinputs + tuple(views[n] for n in net._param_names)
 
 
 class FrameRecoveryNet(BucketedNet):
@@ -207,7 +222,10 @@ class FrameRecoveryNet(BucketedNet):
         self._init_bucket()
 
     # ------------------------------------------------------------------ the layer graph (NHWC, libnvq ops)
-    def _graph(self, frame: torch.Tensor, refs: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    def _graph(self, frame: torch.Tensor, refs: torch.Tensor, mask: torch.Tensor,
+               sink: "Optional[_ops.InputGradSink]" = None, input_leaves: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+        """sink: where the backward writes the inputs' gradients; input_leaves (frozen parameters): a list that receives the
+        NHWC input images whose gradient the sink takes, made grad-requiring so that the layer graph is recorded"""
         B, C, H, W = frame.shape
         T = refs.shape[1]
         math = self.math_mode
@@ -215,22 +233,28 @@ class FrameRecoveryNet(BucketedNet):
         x4 = torch.empty(B, H, W, 4, dtype=torch.float32, device=frame.device)
         _ops.nchw_to_nhwc_(frame, C * H * W, B, C, H, W, x4, 0)
         _ops.nchw_to_nhwc_(mask, H * W, B, 1, H, W, x4, C)
-        sp, _skips = self.spatial_encoder.forward_nhwc(x4, math, act)
+        if input_leaves is not None and (sink.dframe is not None or sink.dmask is not None):
+            input_leaves.append(x4.requires_grad_())
+        sp, _skips = self.spatial_encoder.forward_nhwc(x4, math, act, sink)
         if T >= 2 and self.time_in_channels:
             # frames side by side in the channel dimension: the (3,1,1) convolutions become single 1x1 convolutions
             r = torch.empty(B, H, W, T * 4, dtype=torch.float32, device=frame.device)
             for t in range(T):
                 _ops.nchw_to_nhwc_(refs, T * C * H * W, B, C, H, W, r, 4 * t, czero=4, src_offset=t * C * H * W)
-            tp = self.temporal_encoder.forward_tc(r, T, math, act)
+            if input_leaves is not None and sink.drefs is not None:
+                input_leaves.append(r.requires_grad_())
+            tp = self.temporal_encoder.forward_tc(r, T, math, act, sink)
         else:
             r = torch.empty(T * B, H, W, 4, dtype=torch.float32, device=frame.device)
             for t in range(T):                                    # time-major image batch, channel 3 = 0
                 _ops.nchw_to_nhwc_(refs, T * C * H * W, B, C, H, W, r[t * B:(t + 1) * B], 0, czero=4, src_offset=t * C * H * W)
-            tp = self.temporal_encoder.forward_nhwc(r, T, math, act)
+            if input_leaves is not None and sink.drefs is not None:
+                input_leaves.append(r.requires_grad_())
+            tp = self.temporal_encoder.forward_nhwc(r, T, math, act, sink)
         rec = self.decoder.forward_nhwc(self.fusion.forward_nhwc(sp, tp, math), math, act)
         if rec.shape[1:3] != (H, W):
             rec = _ops.Resize.apply(rec, H, W)
-        return _ops.MaskBlend.apply(frame, rec, mask)
+        return _ops.MaskBlend.apply(frame, rec, mask, sink)
 
     # ------------------------------------------------------------------ reference API
     def forward(self, corrupted_frame: torch.Tensor, reference_frames: torch.Tensor,
@@ -245,12 +269,13 @@ class FrameRecoveryNet(BucketedNet):
             raise RuntimeError(f"reference_frames must be (B,T,{C},{H},{W}), got {tuple(reference_frames.shape)}")
         if H < 32 or W < 32:
             raise RuntimeError("frames must be at least 32x32 (the encoder downsamples by 16)")
-        frame = corrupted_frame.detach().to(torch.float32).contiguous()
-        refs = reference_frames.detach().to(torch.float32).contiguous()
+        # (not detached: autograd chains the cast / copy back to the caller's tensors when they need a gradient)
+        frame = corrupted_frame.to(torch.float32).contiguous()
+        refs = reference_frames.to(torch.float32).contiguous()
         if corruption_mask is None:
             mask = torch.zeros(B, 1, H, W, dtype=torch.float32, device=frame.device)
         else:
-            mask = corruption_mask.detach().to(frame.device, torch.float32).contiguous()
+            mask = corruption_mask.to(frame.device, torch.float32).contiguous()
         params = [p for _, p in named]
         with torch.cuda.device(frame.device):
             return _FRFunction.apply(self, frame, refs, mask, *params)

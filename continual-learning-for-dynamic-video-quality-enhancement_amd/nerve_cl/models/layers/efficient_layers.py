@@ -185,19 +185,20 @@ class TemporalConv3D(_Holder):
                               nn.BatchNorm3d(out_channels), Act())
         self.math_mode = MATH_F32
 
-    def forward_nhwc(self, x: torch.Tensor, T: int, math: int = MATH_F32, act_dtype=None) -> torch.Tensor:
-        """x: time-major image batch [T*B, H, W, ld]; act_dtype: storage type of the block's activations (default: x's)"""
+    def forward_nhwc(self, x: torch.Tensor, T: int, math: int = MATH_F32, act_dtype=None, sink=None) -> torch.Tensor:
+        """x: time-major image batch [T*B, H, W, ld]; act_dtype: storage type of the block's activations (default: x's);
+        sink: an _ops.InputGradSink that takes x's gradient (FrameRecoveryNet's reference frames)"""
         w = self.spatial[0].weight
-        y = _ops.Conv.apply(x, w.view(w.shape[0], w.shape[1], 3, 3), None, False, math, act_dtype)
+        y = _ops.Conv.apply(x, w.view(w.shape[0], w.shape[1], 3, 3), None, False, math, act_dtype, sink)
         y = _ops.bn(y, self.spatial[1], self.training, relu=True)
         y = _ops.TemporalConv.apply(y, self.temporal[0].weight, T, math)
         return _ops.bn(y, self.temporal[1], self.training, relu=True)
 
-    def forward_tc(self, x: torch.Tensor, T: int, math: int = MATH_F32, act_dtype=None) -> torch.Tensor:
+    def forward_tc(self, x: torch.Tensor, T: int, math: int = MATH_F32, act_dtype=None, sink=None) -> torch.Tensor:
         """x: time-in-channels tensor [B, H, W, T * Cp] (see nerve_cl._ops); T >= 2.  Every activation is read and written
-        once: no accumulating passes over memory for the temporal taps."""
+        once: no accumulating passes over memory for the temporal taps.  sink: as forward_nhwc."""
         w = self.spatial[0].weight
-        y = _ops.SpatialConvTC.apply(x, w.view(w.shape[0], w.shape[1], 3, 3), T, math, act_dtype)
+        y = _ops.SpatialConvTC.apply(x, w.view(w.shape[0], w.shape[1], 3, 3), T, math, act_dtype, sink)
         y = _ops.bn_tc(y, self.spatial[1], T, self.training, relu=True)
         y = _ops.TemporalConvTC.apply(y, self.temporal[0].weight, T, math)
         return _ops.bn_tc(y, self.temporal[1], T, self.training, relu=True)

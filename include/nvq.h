@@ -473,6 +473,27 @@ int nvq_head_dgrad(const float* dout, int dout_ld, int dout_bf16, const float* d
  * order, clamped border taps included (no atomics).  s in 1..4. */
 int nvq_bicubic_adjoint(const float* dout, const uint8_t* pass, int B, int Cimg, int H, int W, int s,
                         int T, int t_center, float coef, float* dframes, int accumulate, void* stream);
+/* nvq_head_dgrad's pre-masked form for a gradient laid out by slot in either dimension: slot s reads images
+ * s*slot_images + b (slot_images = B: time-major batch [nslots*B][H][W][ld]; 0: one image per b, [B][H][W][ld]) at
+ * channels coff_of_slot[s] .. + F (a multiple of 8, + F <= ld).  FrameRecoveryNet's first temporal conv in the
+ * time-in-channels layout: frame t at channel offset t*Cp.  Same kernel as nvq_head_dgrad (bit-identical results for
+ * slot_images = B, offsets 0). */
+int nvq_head_dgrad_tc(const float* dout, int dout_ld, int dout_bf16, const float* weight, int F,
+                      int B, int T, int Cin, int H, int W, const int* t_of_slot_host,
+                      const int* coff_of_slot_host, int nslots, int slot_images, float* dframes,
+                      int accumulate, void* stream);
+/* Input gradient of FrameRecoveryNet's stem nn.Conv2d(4, Co, 7, 2, 3, bias=False) on x4 = [frame | mask] (NHWC):
+ * dx = stem^T(dy); channels 0..2 go to dframe (N,3,H,W) fp32 NCHW, channel 3 to dmask (N,1,H,W); either may be NULL (not
+ * both); += if accumulate.  dy fp32 or bf16 (dy_bf16) [N][OH][OW][dy_ld], OH = (H-1)/2+1, dy_ld % 8 == 0, 16-B aligned;
+ * w [Co,4,7,7]; Co in {16, 32, 48, 64}.  Gather form, fixed sum order (no atomics): bit-reproducible. */
+int nvq_stem7_dgrad(const float* dy, int dy_ld, int dy_bf16, const float* w, int N, int H, int W, int Co,
+                    float* dframe, float* dmask, int accumulate, void* stream);
+/* FrameRecoveryNet blend backward with its inputs' gradients: drec as nvq_mask_blend_backward (ld rec_ld, channels
+ * [C, ld) zeroed), dframe (N,C,H,W) = dout*(1-m), dmask (N,1,H,W) = sum_c dout*(rec-frame) (overwrite); dframe / dmask
+ * may be NULL, frame and rec are read only for dmask. */
+int nvq_mask_blend_backward_ex(const float* dout, const float* frame, const float* rec, int rec_ld,
+                               const float* mask, int N, int C, int H, int W, float* drec,
+                               float* dframe, float* dmask, void* stream);
 
 /* nn.PixelShuffle(s) alone (stand-alone PixelShuffleUpsampler, efficient_layers.py:101-106):
  * img[b,c,h*s+i,w*s+j] = u[b,h,w,c*s*s+i*s+j] (backward != 0: the other direction, padding channels of u zeroed) */
