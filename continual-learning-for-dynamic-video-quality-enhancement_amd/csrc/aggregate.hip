@@ -283,7 +283,9 @@ __global__ __launch_bounds__(256) void cbam_bwd_pre_kernel(const float* __restri
     }
 }
 
-// dsm = conv7x7^T(dpre); per-tile partial of dw7. grid (tiles, N); part[(n*tiles + tile)][98]
+// dsm = conv7x7^T(dpre); per-tile partial of dw7. grid (tiles, N); part[(n*tiles + tile)][98].  WG = false
+// (NVQ_NO_WGRAD): dsm alone, sm is not staged
+template <bool WG>
 __global__ __launch_bounds__(256) void cbam_bwd_conv_kernel(const float* __restrict__ dpre,
                                                             const float* __restrict__ sm,
                                                             const float* __restrict__ w7, int H, int W, int tilesX,
@@ -301,12 +303,16 @@ __global__ __launch_bounds__(256) void cbam_bwd_conv_kernel(const float* __restr
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
             const size_t pix = (size_t)(n * H + gy) * W + gx;
             d = dpre[pix];
-            a = sm[pix * 2];
-            b = sm[pix * 2 + 1];
+            if constexpr (WG) {
+                a = sm[pix * 2];
+                b = sm[pix * 2 + 1];
+            }
         }
         dtile[hy][hx] = d;
-        stile[0][hy][hx] = a;
-        stile[1][hy][hx] = b;
+        if constexpr (WG) {
+            stile[0][hy][hx] = a;
+            stile[1][hy][hx] = b;
+        }
     }
     __syncthreads();
     const int py = threadIdx.x / SP_T, px = threadIdx.x % SP_T;
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(256) void cbam_bwd_conv_kernel(const float* __restr
         dsm[pix * 2 + 1] = s1;
     }
     // dw7[ch][ky][kx] partial = sum_{p in tile} sm[p + (ky-3,kx-3)][ch] * dpre[p]
-    if (threadIdx.x < 98) {
+    if (WG && threadIdx.x < 98) {
         const int ch = threadIdx.x / 49, ky = (threadIdx.x % 49) / 7, kx = threadIdx.x % 7;
         float s = 0.f;
         for (int yy = 0; yy < SP_T; ++yy)
@@ -373,7 +379,8 @@ __global__ __launch_bounds__(256) void cbam_bwd_scale_kernel(const float* __rest
         st4(dca_partial + ((size_t)n * gridDim.x + blockIdx.x) * C + 4 * c4, r);
 }
 
-// single block; loops over images so that dw1/dw2 are summed in a fixed order
+// single block; loops over images so that dw1/dw2 are summed in a fixed order.  WG = false (NVQ_NO_WGRAD): dgap_pix alone
+template <bool WG>
 __global__ __launch_bounds__(256) void cbam_bwd_channel_kernel(const float* __restrict__ dca_partial, int nblk, int C,
                                                                int R, int N, long HW, const float* __restrict__ w1,
                                                                const float* __restrict__ w2, const float* __restrict__ gap,
@@ -423,14 +430,16 @@ __global__ __launch_bounds__(256) void cbam_bwd_channel_kernel(const float* __re
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (r < R) {
-                    a2[r] += z * sh[r];          // dw2[c][r]
-                    a1[r] += dz1[r] * gv;        // dw1[r][c]
+                    if constexpr (WG) {
+                        a2[r] += z * sh[r];      // dw2[c][r]
+                        a1[r] += dz1[r] * gv;    // dw1[r][c]
+                    }
                     dg += w1[r * C + c] * dz1[r];
                 }
             dgap_pix[(size_t)n * C + c] = dg / (float)HW;
         }
     }
-    if (c < C) {
+    if (WG && c < C) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             if (r < R) {
@@ -543,17 +552,29 @@ int nvq_cbam_bwd_spatial_pre(const float* dout, int dout_ld, int dout_coff, cons
     return check_launch("cbam_bwd_spatial_pre");
 }
 
-int nvq_cbam_bwd_spatial_conv(const float* dpre, const float* sm, const float* w7, int N, int H, int W, float* dsm,
-                              float* dw7, float* workspace, size_t workspace_bytes, int accumulate, void* stream) {
+int nvq_cbam_bwd_spatial_conv_ex(const float* dpre, const float* sm, const float* w7, int N, int H, int W, float* dsm,
+                                 float* dw7, float* workspace, size_t workspace_bytes, int accumulate, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "cbam_bwd_spatial_conv_ex: flags %d", flags);
+    const bool wg = !(flags & NVQ_NO_WGRAD);
     const int tilesX = (W + SP_T - 1) / SP_T, tilesY = (H + SP_T - 1) / SP_T;
     const int nblk = tilesX * tilesY * N;
-    if ((size_t)nblk * 98 * sizeof(float) > workspace_bytes) { set_error("cbam_bwd_spatial_conv: workspace"); return NVQ_EWORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cbam_bwd_conv_kernel, dim3(tilesX * tilesY, N), dim3(256), 0, s, dpre, sm, w7, H, W, tilesX, dsm,
+    if (!wg) {
+        hipLaunchKernelGGL(cbam_bwd_conv_kernel<false>, dim3(tilesX * tilesY, N), dim3(256), 0, s, dpre, sm, w7, H, W, tilesX,
+                           dsm, workspace);
+        return check_launch("cbam_bwd_spatial_conv");
+    }
+    if ((size_t)nblk * 98 * sizeof(float) > workspace_bytes) { set_error("cbam_bwd_spatial_conv: workspace"); return NVQ_EWORKSPACE; }
+    hipLaunchKernelGGL(cbam_bwd_conv_kernel<true>, dim3(tilesX * tilesY, N), dim3(256), 0, s, dpre, sm, w7, H, W, tilesX, dsm,
                        workspace);
     int rc = check_launch("cbam_bwd_spatial_conv");
     if (rc) return rc;
     return launch_reduce_partials(workspace, nblk, 98, 1.f, dw7, accumulate, s);
+}
+
+int nvq_cbam_bwd_spatial_conv(const float* dpre, const float* sm, const float* w7, int N, int H, int W, float* dsm,
+                              float* dw7, float* workspace, size_t workspace_bytes, int accumulate, void* stream) {
+    return nvq_cbam_bwd_spatial_conv_ex(dpre, sm, w7, N, H, W, dsm, dw7, workspace, workspace_bytes, accumulate, 0, stream);
 }
 
 int nvq_cbam_bwd_scale(const float* dout, int dout_ld, int dout_coff, const float* x, int x_ld, const float* ca,
@@ -570,13 +591,24 @@ int nvq_cbam_bwd_scale(const float* dout, int dout_ld, int dout_coff, const floa
     return check_launch("cbam_bwd_scale");
 }
 
+int nvq_cbam_bwd_channel_ex(const float* dca_partial, int nblk, int C, int R, int N, int HW, const float* w1,
+                            const float* w2, const float* gap, const float* hid, const float* ca, float* dw1,
+                            float* dw2, float* dgap_pix, int accumulate, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "cbam_bwd_channel_ex: flags %d", flags);
+    NVQ_REQUIRE(C <= 256 && R >= 1 && R <= 16, "cbam_bwd_channel: C %d R %d", C, R);
+    if (flags & NVQ_NO_WGRAD)
+        hipLaunchKernelGGL(cbam_bwd_channel_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, dca_partial, nblk, C, R, N,
+                           (long)HW, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix, accumulate);
+    else
+        hipLaunchKernelGGL(cbam_bwd_channel_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, dca_partial, nblk, C, R, N,
+                           (long)HW, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix, accumulate);
+    return check_launch("cbam_bwd_channel");
+}
+
 int nvq_cbam_bwd_channel(const float* dca_partial, int nblk, int C, int R, int N, int HW, const float* w1,
                          const float* w2, const float* gap, const float* hid, const float* ca, float* dw1,
                          float* dw2, float* dgap_pix, int accumulate, void* stream) {
-    NVQ_REQUIRE(C <= 256 && R >= 1 && R <= 16, "cbam_bwd_channel: C %d R %d", C, R);
-    hipLaunchKernelGGL(cbam_bwd_channel_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dca_partial, nblk, C, R, N,
-                       (long)HW, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix, accumulate);
-    return check_launch("cbam_bwd_channel");
+    return nvq_cbam_bwd_channel_ex(dca_partial, nblk, C, R, N, HW, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix, accumulate, 0, stream);
 }
 
 }  // extern "C"

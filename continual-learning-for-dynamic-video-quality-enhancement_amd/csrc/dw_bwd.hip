@@ -55,7 +55,9 @@ __device__ __forceinline__ float4 unpack4(u32x2 v) {
 // sum g and sum g xhat over the group, g = dx where relu(bn(x)) > 0 - as per-workgroup partials: the kernel holds both operands
 // (x is the BatchNorm input, dx its activation's gradient), so the separate reduce pass over them (bn_bwd_reduce) is not needed.
 // x is then staged RAW and the transform applied by the thread that uses the value (which also needs xhat).
-template <bool HAS_BN, bool HAS_EPI, bool STATS>
+// WG = false (nvq_dwconv_backward_ex, NVQ_NO_WGRAD): dx' alone - no weight-gradient accumulators or partials, and the x tile is
+// staged only for STATS; dx' is formed by the same instructions in the same order as with WG.
+template <bool HAS_BN, bool HAS_EPI, bool STATS, bool WG>
 __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
     static_assert(!STATS || HAS_BN, "the sums belong to the input transform");
     __shared__ __attribute__((aligned(16))) __bf16 gs[FNPIX * FC];        // dd halo tile, 128 B per pixel
@@ -108,6 +110,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
             okm |= (ok ? 1u : 0u) << k;
             v[k] = *reinterpret_cast<const u32x4*>(a.dd + (ok ? ((size_t)(n * a.H + gy) * a.W + gx) * a.dd_ld + 8 * q : 0));
         }
+        if constexpr (WG || STATS)
 #pragma unroll
         for (int k = 0; k < XPER; ++k) {
             const int item = tid_o + k * FT;
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
             for (int e = 0; e < 4; ++e) o[e] = (okm >> k) & 1 ? v[k][e] : 0u;
             if (item < FNPIX * 8) *reinterpret_cast<u32x4*>(gs + (item >> 3) * FC + 8 * (item & 7)) = o;
         }
-        if constexpr (HAS_BN && !STATS) {
+        if constexpr (HAS_BN && !STATS && WG) {
             // same expression and the same single bf16 rounding as bn_apply_relu_kernel (pointwise.hip)
             const int c0 = 8 * (tid & 7);
             float m[8], is[8], ga[8], be[8];
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
                 xv[k] = o;
             }
         }
+        if constexpr (WG || STATS)
 #pragma unroll
         for (int k = 0; k < XPER; ++k) {
             const int item = tid + k * FT;
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
 #pragma unroll
             for (int ri = 0; ri < RUK; ++ri) {
                 const int rr = r0 + ri;
-                if (rr < FH) {
+                if (rr < FH && (WG || STATS)) {
                     X0 = unpack4(*reinterpret_cast<const u32x2*>(xs + (rr * FW + x) * FC + 4 * c4));
                     if constexpr (STATS) {                    // raw x -> relu(bn(x)), the expression and rounding of the staging form
                         const bool ok = ty * FH + rr < a.H && gx < a.W;
@@ -209,17 +213,17 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
                     if (rr < FH) {
                         const float4 ww = wf[b]; float4& s = wacc[b];
                         a0.x = __builtin_fmaf(vv.x, ww.x, a0.x); a0.y = __builtin_fmaf(vv.y, ww.y, a0.y); a0.z = __builtin_fmaf(vv.z, ww.z, a0.z); a0.w = __builtin_fmaf(vv.w, ww.w, a0.w);
-                        s.x += vv.x * X0.x; s.y += vv.y * X0.y; s.z += vv.z * X0.z; s.w += vv.w * X0.w;
+                        if constexpr (WG) { s.x += vv.x * X0.x; s.y += vv.y * X0.y; s.z += vv.z * X0.z; s.w += vv.w * X0.w; }
                     }
                     if (rr >= 1 && rr <= FH) {
                         const float4 ww = wf[3 + b]; float4& s = wacc[3 + b];
                         a1.x = __builtin_fmaf(vv.x, ww.x, a1.x); a1.y = __builtin_fmaf(vv.y, ww.y, a1.y); a1.z = __builtin_fmaf(vv.z, ww.z, a1.z); a1.w = __builtin_fmaf(vv.w, ww.w, a1.w);
-                        s.x += vv.x * X1.x; s.y += vv.y * X1.y; s.z += vv.z * X1.z; s.w += vv.w * X1.w;
+                        if constexpr (WG) { s.x += vv.x * X1.x; s.y += vv.y * X1.y; s.z += vv.z * X1.z; s.w += vv.w * X1.w; }
                     }
                     if (rr >= 2) {
                         const float4 ww = wf[6 + b]; float4& s = wacc[6 + b];
                         a2.x = __builtin_fmaf(vv.x, ww.x, a2.x); a2.y = __builtin_fmaf(vv.y, ww.y, a2.y); a2.z = __builtin_fmaf(vv.z, ww.z, a2.z); a2.w = __builtin_fmaf(vv.w, ww.w, a2.w);
-                        s.x += vv.x * X2.x; s.y += vv.y * X2.y; s.z += vv.z * X2.z; s.w += vv.w * X2.w;
+                        if constexpr (WG) { s.x += vv.x * X2.x; s.y += vv.y * X2.y; s.z += vv.z * X2.z; s.w += vv.w * X2.w; }
                     }
                 }
                 if (rr >= 2) {
@@ -266,6 +270,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
     // LDS); wacc[t] belongs to tap 8 - t
     float* red = reinterpret_cast<float*>(gs);                // [4 waves][16 c4][36]
     const int wave = tid >> 6, lane = tid & 63;
+    if constexpr (WG) {
 #pragma unroll
     for (int t9 = 0; t9 < 9; ++t9) {
         float s[4] = {wacc[t9].x, wacc[t9].y, wacc[t9].z, wacc[t9].w};
@@ -283,6 +288,7 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
         const float s = red[(0 * 16 + ci) * 36 + k] + red[(1 * 16 + ci) * 36 + k] + red[(2 * 16 + ci) * 36 + k] +
                         red[(3 * 16 + ci) * 36 + k];
         prow[(4 * ci + (k & 3)) * 9 + (k >> 2)] = s;
+    }
     }
     if constexpr (STATS) {                                    // the same reduction for the 2 x 4 BatchNorm sums per thread
         __syncthreads();
@@ -307,10 +313,12 @@ __global__ __launch_bounds__(FT, 2) void dw_bwd_kernel(const DwBwdArgs a) {
 
 using namespace nvq;
 
-extern "C" int nvq_dwconv_backward(const float* x, int x_ld, const nvq_bn_input* bn, const float* dy, int dy_ld,
-                                   const float* weight, float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W,
-                                   float* dweight, float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace,
-                                   size_t workspace_bytes, void* stream) {
+static int dwconv_backward_impl(const float* x, int x_ld, const nvq_bn_input* bn, const float* dy, int dy_ld,
+                                const float* weight, float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W,
+                                float* dweight, float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace,
+                                size_t workspace_bytes, int flags, void* stream) {
+    const bool wg = !(flags & NVQ_NO_WGRAD);
+    NVQ_REQUIRE(!wg || dweight, "dwconv_backward: dweight");
     NVQ_REQUIRE(!bn_sums || (bn && !epi && bn_dgamma && bn_dbeta),
                 "dwconv_backward: the BatchNorm-backward sums need the input transform (and its dgamma / dbeta), no epilogue");
     NVQ_REQUIRE(!bn || (bn->group_images > 0 && N % bn->group_images == 0 && N / bn->group_images <= NVQ_MAX_T),
@@ -329,7 +337,7 @@ extern "C" int nvq_dwconv_backward(const float* x, int x_ld, const nvq_bn_input*
     int nwg = FMAXWG / G;
     if (nwg > tpg) nwg = tpg;
     if (nwg >= 8) nwg &= ~7;                                  // multiple of the XCD count, see xcd_tile()
-    const size_t part_floats = (size_t)G * nwg * FC * 9, part2_floats = bn_sums ? (size_t)G * nwg * 2 * FC : 0;
+    const size_t part_floats = wg ? (size_t)G * nwg * FC * 9 : 0, part2_floats = bn_sums ? (size_t)G * nwg * 2 * FC : 0;
     if ((part_floats + part2_floats) * sizeof(float) > workspace_bytes) { set_error("dwconv_backward: workspace"); return NVQ_EWORKSPACE; }
     DwBwdArgs a{reinterpret_cast<const __bf16*>(x), x_ld, reinterpret_cast<const __bf16*>(dy), dy_ld, weight,
                 reinterpret_cast<__bf16*>(dx), dx_ld, bn ? bn->mean : nullptr, bn ? bn->invstd : nullptr,
@@ -337,16 +345,36 @@ extern "C" int nvq_dwconv_backward(const float* x, int x_ld, const nvq_bn_input*
                 epi ? reinterpret_cast<const __bf16*>(epi->mask) : nullptr, epi ? epi->mask_ld : 0, workspace,
                 workspace + part_floats, H, W, tilesX, tilesY, group_images, tpg};
     hipStream_t s = (hipStream_t)stream;
-#define NVQ_DWBWD(B_, E_, S_) hipLaunchKernelGGL((dw_bwd_kernel<B_, E_, S_>), dim3(nwg, G), dim3(FT), 0, s, a)
-    if (bn_sums) NVQ_DWBWD(true, false, true);
-    else if (bn && epi) NVQ_DWBWD(true, true, false);
-    else if (bn) NVQ_DWBWD(true, false, false);
-    else if (epi) NVQ_DWBWD(false, true, false);
-    else NVQ_DWBWD(false, false, false);
+#define NVQ_DWBWD(B_, E_, S_, W_) hipLaunchKernelGGL((dw_bwd_kernel<B_, E_, S_, W_>), dim3(nwg, G), dim3(FT), 0, s, a)
+#define NVQ_DWBWD_ALL(W_)                                          \
+    if (bn_sums) NVQ_DWBWD(true, false, true, W_);                 \
+    else if (bn && epi) NVQ_DWBWD(true, true, false, W_);          \
+    else if (bn) NVQ_DWBWD(true, false, false, W_);                \
+    else if (epi) NVQ_DWBWD(false, true, false, W_);               \
+    else NVQ_DWBWD(false, false, false, W_);
+    if (wg) { NVQ_DWBWD_ALL(true) } else { NVQ_DWBWD_ALL(false) }
+#undef NVQ_DWBWD_ALL
 #undef NVQ_DWBWD
     int rc = check_launch("dwconv_backward");
     if (rc) return rc;
-    rc = launch_reduce_partials(workspace, G * nwg, FC * 9, 1.f, dweight, 0, s);
+    if (wg) rc = launch_reduce_partials(workspace, G * nwg, FC * 9, 1.f, dweight, 0, s);
     if (rc || !bn_sums) return rc;
     return bn_bwd_finalize_launch(workspace + part_floats, nwg, FC, G, bn_sums, bn_dgamma, bn_dbeta, s);
+}
+
+extern "C" int nvq_dwconv_backward(const float* x, int x_ld, const nvq_bn_input* bn, const float* dy, int dy_ld,
+                                   const float* weight, float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W,
+                                   float* dweight, float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    return dwconv_backward_impl(x, x_ld, bn, dy, dy_ld, weight, dx, dx_ld, epi, N, H, W, dweight, bn_sums, bn_dgamma, bn_dbeta,
+                                workspace, workspace_bytes, 0, stream);
+}
+
+extern "C" int nvq_dwconv_backward_ex(const float* x, int x_ld, const nvq_bn_input* bn, const float* dy, int dy_ld,
+                                      const float* weight, float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W,
+                                      float* dweight, float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace,
+                                      size_t workspace_bytes, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "dwconv_backward_ex: flags %d", flags);
+    return dwconv_backward_impl(x, x_ld, bn, dy, dy_ld, weight, dx, dx_ld, epi, N, H, W, dweight, bn_sums, bn_dgamma, bn_dbeta,
+                                workspace, workspace_bytes, flags, stream);
 }

@@ -47,7 +47,9 @@ struct PwBwdArgs {
 __device__ __forceinline__ float blo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bhi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
-template <bool DYB>
+// WG = false (nvq_pw_bn_backward_ex, NVQ_NO_WGRAD): the input gradient alone - d is neither read nor staged, no weight-gradient
+// MFMA, no partial slabs; dd is formed by the same instructions in the same order as with WG.
+template <bool DYB, bool WG>
 __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
     __shared__ __attribute__((aligned(16))) __bf16 lds[2 * TP * PS];
     __shared__ __attribute__((aligned(16))) float cst[MAXG][6][PC];   // mean, invstd, gamma, beta, mean(g), mean(g xhat)
@@ -76,8 +78,10 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) wf[cb][kb][j] = (__bf16)a.w[(kb * 32 + 8 * g4 + j) * PC + cb * 16 + r];
     f32x4 accw[4];
+    if constexpr (WG) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) accw[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < 4; ++c) accw[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
 
     // staging role: 16-byte piece `piece` (8 channels) of pixels px0 + 32 k of the tile
     const int piece = tid & 7, px0 = tid >> 3;
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
             okm |= (ok ? 1u : 0u) << k;
             const size_t pix = ok ? (size_t)(nbase + px) : 0;
             rp[k] = *reinterpret_cast<const u32x4*>(p16 + pix * a.p_ld + 8 * piece);
-            rd[k] = *reinterpret_cast<const u32x4*>(d16 + pix * a.d_ld + 8 * piece);
+            if constexpr (WG) rd[k] = *reinterpret_cast<const u32x4*>(d16 + pix * a.d_ld + 8 * piece);
             if constexpr (DYB) {
                 ry[k][0] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.dy) + pix * a.dy_ld + 8 * piece);
             } else {
@@ -155,8 +159,10 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
                 o[e] = (__bf16)(ok ? v : 0.f);
             }
             *reinterpret_cast<bf16x8*>(dps + px * PS + 8 * piece) = o;
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4*>(ds_ + px * PS + 8 * piece) = ok ? rd[k] : z;
+            if constexpr (WG) {
+                const u32x4 z = {0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(ds_ + px * PS + 8 * piece) = ok ? rd[k] : z;
+            }
         }
     };
     typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
@@ -200,6 +206,7 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
             }
         }
         // ---- weight gradient: this wave's 16-ci block x the four 16-co blocks, K = the tile's 128 pixels
+        if constexpr (WG) {
 #pragma unroll
         for (int ks = 0; ks < TP / 32; ++ks) {
             const s16x4 a0 = tr(ds_, ks * 32 + 4 * g4, wave), a1 = tr(ds_, ks * 32 + 16 + 4 * g4, wave);
@@ -211,7 +218,9 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
                 accw[cob] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr, accw[cob], 0, 0, 0);
             }
         }
+        }
     }
+    if constexpr (!WG) return;
     // partial slabs: [split][32-ci unit (2)][32-co unit (2)][32 ci][32 co]; wave = 16-ci block `wave`
     const int slab = wave >> 1, cil0 = (wave & 1) * 16;
 #pragma unroll
@@ -227,15 +236,17 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
 
 using namespace nvq;
 
-extern "C" int nvq_pw_bn_backward(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
-                                  int N, int group_images, int H, int W, const float* mean, const float* invstd,
-                                  const float* gamma, const float* beta, int training, const float* weight, float* dd,
-                                  int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
-                                  float* workspace, size_t workspace_bytes, void* stream) {
+static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
+                               int N, int group_images, int H, int W, const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, int training, const float* weight, float* dd,
+                               int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
+                               float* workspace, size_t workspace_bytes, int flags, void* stream) {
+    const bool wg = !(flags & NVQ_NO_WGRAD);
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "pw_bn_backward: groups");
     NVQ_REQUIRE(p_ld % 8 == 0 && d_ld % 8 == 0 && dd_ld % 8 == 0 && dy_ld % 8 == 0 && p_ld >= PC && d_ld >= PC && dd_ld >= PC &&
                     dy_ld >= PC && aligned16(p) && aligned16(d) && aligned16(dd) && aligned16(dy),
                 "pw_bn_backward: 64-channel bf16 tensors, 16-byte addressable");
+    NVQ_REQUIRE(!wg || dweight, "pw_bn_backward: dweight");
     const int G = N / group_images;
     const long group_pix = (long)group_images * H * W;
     hipStream_t s = (hipStream_t)stream;
@@ -243,24 +254,52 @@ extern "C" int nvq_pw_bn_backward(const float* dy, int dy_ld, int dy_bf16, const
     const long ntiles = (long)G * tpg;
     NVQ_REQUIRE(ntiles < ((long)1 << 31), "pw_bn_backward: too many tiles");
     int nsplit = ntiles < WGRAD_MAX_WG ? (int)ntiles : WGRAD_MAX_WG;
-    const size_t part_floats = (size_t)nsplit * 4 * WG_C * WG_C;
+    const size_t part_floats = wg ? (size_t)nsplit * 4 * WG_C * WG_C : 0;
     NVQ_REQUIRE(part_floats * sizeof(float) < workspace_bytes, "pw_bn_backward: workspace");
     float* sums = const_cast<float*>(sums_in);
     int rc = NVQ_OK;
     if (!sums_in) {
-        // BatchNorm sums (and dgamma / dbeta) first: two-stage reduction in the workspace behind the weight-gradient slabs
+        // BatchNorm sums (and dgamma / dbeta) first: two-stage reduction in the workspace behind the weight-gradient slabs.  A
+        // frozen affine (dgamma / dbeta NULL, _ex form): the finalize kernel writes them to the workspace's last 2 x 64 floats
+        size_t sums_bytes = workspace_bytes - part_floats * sizeof(float);
+        if (!dgamma || !dbeta) {
+            NVQ_REQUIRE(sums_bytes > 2 * PC * sizeof(float), "pw_bn_backward: workspace");
+            sums_bytes -= 2 * PC * sizeof(float);
+            float* sink = workspace + sums_bytes / sizeof(float) + part_floats;
+            if (!dgamma) dgamma = sink;
+            if (!dbeta) dbeta = sink + PC;
+        }
         rc = bn_backward_sums(dy, dy_ld, p, p_ld, PC, G, group_pix, mean, invstd, gamma, beta, dgamma, dbeta, workspace + part_floats,
-                              workspace_bytes - part_floats * sizeof(float), dy_bf16, 1, &sums, s);
+                              sums_bytes, dy_bf16, 1, &sums, s);
         if (rc) return rc;
     }
     PwBwdArgs a{dy, dy_ld, reinterpret_cast<const __bf16*>(p), p_ld, reinterpret_cast<const __bf16*>(d), d_ld, mean, invstd, gamma,
                 beta, sums, weight, reinterpret_cast<__bf16*>(dd), dd_ld, workspace, group_pix, G, training, tpg, (int)ntiles,
                 1.f / (float)group_pix};
-    if (dy_bf16)
-        hipLaunchKernelGGL(pw_bn_bwd_kernel<true>, dim3(nsplit), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(pw_bn_bwd_kernel<false>, dim3(nsplit), dim3(256), 0, s, a);
+#define NVQ_PWB(D_, W_) hipLaunchKernelGGL((pw_bn_bwd_kernel<D_, W_>), dim3(nsplit), dim3(256), 0, s, a)
+    if (wg) { if (dy_bf16) NVQ_PWB(true, true); else NVQ_PWB(false, true); }
+    else { if (dy_bf16) NVQ_PWB(true, false); else NVQ_PWB(false, false); }
+#undef NVQ_PWB
     rc = check_launch("pw_bn_backward");
-    if (rc) return rc;
+    if (rc || !wg) return rc;
     return launch_wgrad_reduce(workspace, nsplit, 2, 2, 1, PC, PC, 1.f, 0, dweight, s);
+}
+
+extern "C" int nvq_pw_bn_backward(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
+                                  int N, int group_images, int H, int W, const float* mean, const float* invstd,
+                                  const float* gamma, const float* beta, int training, const float* weight, float* dd,
+                                  int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
+                                  float* workspace, size_t workspace_bytes, void* stream) {
+    return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, training,
+                               weight, dd, dd_ld, dgamma, dbeta, dweight, sums_in, workspace, workspace_bytes, 0, stream);
+}
+
+extern "C" int nvq_pw_bn_backward_ex(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
+                                     int N, int group_images, int H, int W, const float* mean, const float* invstd,
+                                     const float* gamma, const float* beta, int training, const float* weight, float* dd,
+                                     int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
+                                     float* workspace, size_t workspace_bytes, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "pw_bn_backward_ex: flags %d", flags);
+    return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, training,
+                               weight, dd, dd_ld, dgamma, dbeta, dweight, sums_in, workspace, workspace_bytes, flags, stream);
 }

@@ -369,13 +369,117 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     return out, sv
 
 
-def _wgrad(x: Sl, cin_w: int, dy: Sl, G: Dict[str, torch.Tensor], wname: str, bname: Optional[str], ws, ksize,
+# ----------------------------------------------------------------------------- backward plan (frozen parameters)
+class BackwardPlan:
+    """What one backward forms.  wgrad: the parameter names whose gradient is written; dx: the stages whose
+    input gradient runs (a stage's input gradient is needed iff a parameter of an earlier stage, or the frames, needs a gradient);
+    frames: the frames' gradient is formed."""
+    __slots__ = ("wgrad", "dx", "frames", "run", "_key")
+
+    def __init__(self, wgrad, dx, frames: bool, stages):
+        self.wgrad, self.dx, self.frames = frozenset(wgrad), frozenset(dx), bool(frames)
+        self._key = (tuple(sorted(self.wgrad)), self.frames)
+        # a stage's backward runs when its input gradient or one of its weight gradients is needed
+        self.run = frozenset(st for st, names in stages if st in self.dx or any(n in self.wgrad for n in names))
+
+    @property
+    def empty(self) -> bool:
+        return not self.wgrad and not self.frames
+
+    def key(self) -> tuple:
+        return self._key
+
+
+def _plan(stages, names_needing_grad, frames_need_grad: bool) -> BackwardPlan:
+    need = set(names_needing_grad)
+    wgrad, dx = set(), set()
+    upstream = bool(frames_need_grad)          # some tensor before the current stage needs a gradient
+    for st, names in stages:
+        if upstream:
+            dx.add(st)
+        mine = [n for n in names if n in need]
+        wgrad.update(mine)
+        upstream = upstream or bool(mine)
+    return BackwardPlan(wgrad, dx, frames_need_grad, stages)
+
+
+def sr_stages(NB: int, T: int) -> "list[tuple[str, list[str]]]":
+    """SuperResolutionNet's stages in forward order with their parameter names.  The order is a topological order of the
+    forward's dataflow: the extractor's features feed the motion path (correlation -> flow net -> warp) and, through the warp
+    and directly (centre frame), the aligned features; so "upstream of a stage" is "earlier in this list".  With T = 1 there is
+    no motion path: flow_net has no effect on the output and no gradient is formed for it."""
+    fe = "feature_extractor."
+    st = [("head", [fe + "head.0.weight", fe + "head.0.bias"])]
+    st += [(f"body.{k}", [fe + f"body.{k}.{n}" for n in ("depthwise.weight", "pointwise.weight", "bn.weight", "bn.bias")])
+           for k in range(3)]
+    if T > 1:
+        st += [(f"flow.{i}", [f"motion_estimator.flow_net.{i}.weight", f"motion_estimator.flow_net.{i}.bias"]) for i in (0, 2, 4, 6)]
+    ta = "temporal_aggregator."
+    st += [(f"att.{i}", [ta + f"attention.{i}.weight", ta + f"attention.{i}.bias"]) for i in (0, 2, 4)]
+    st.append(("cbam", [ta + "refine.channel_attention.fc.0.weight", ta + "refine.channel_attention.fc.2.weight",
+                        ta + "refine.spatial_attention.conv.weight"]))
+    for k in range(NB):
+        pre = f"residual_blocks.{k}."
+        st.append((f"rdb.{k}", [pre + f"layers.{i}.0.{n}" for i in range(LAYERS) for n in ("weight", "bias")]
+                   + [pre + "lff.weight", pre + "lff.bias"]))
+    st += [("gff", ["gff.0.weight", "gff.0.bias"]), ("up", ["upsampler.conv.weight", "upsampler.conv.bias"])]
+    return st
+
+
+def backward_plan(names_needing_grad, frames_need_grad: bool, NB: int, T: int) -> BackwardPlan:
+    """The backward plan of SuperResolutionNet for a need mask (pure host function)."""
+    return _plan(sr_stages(NB, T), names_needing_grad, frames_need_grad)
+
+
+def light_stages() -> "list[tuple[str, list[str]]]":
+    return ([("head", ["net.0.weight", "net.0.bias"])]
+            + [(f"block.{j}", [f"net.{k}.{n}" for n in ("depthwise.weight", "pointwise.weight", "bn.weight", "bn.bias")])
+               for j, k in enumerate(LIGHT_BLOCKS)]
+            + [("up", ["net.6.weight", "net.6.bias"])])
+
+
+def light_backward_plan(names_needing_grad, frames_need_grad: bool) -> BackwardPlan:
+    """The backward plan of LightweightSuperResolution for a need mask."""
+    return _plan(light_stages(), names_needing_grad, frames_need_grad)
+
+
+class _Grads:
+    """The gradient targets of a planned backward: get(name) is G[name] when the plan forms that gradient (counted: each is
+    written exactly once) and None for a frozen parameter; sink(name) is a throw-away tensor for an output a kernel writes
+    unconditionally (the bias next to a trained weight, a BatchNorm affine next to a trained conv)."""
+
+    def __init__(self, G: Dict[str, torch.Tensor], plan: BackwardPlan, P: Dict[str, torch.Tensor]):
+        self.G, self.plan, self.P, self.writes = G, plan, P, {}
+
+    def get(self, name: str) -> Optional[torch.Tensor]:
+        if name not in self.plan.wgrad:
+            return None
+        self.writes[name] = self.writes.get(name, 0) + 1
+        return self.G[name]
+
+    def sink(self, name: str) -> torch.Tensor:
+        g = self.get(name)
+        return g if g is not None else torch.empty_like(self.P[name])
+
+    def check(self) -> None:
+        bad = {n: c for n, c in self.writes.items() if c != 1}
+        missing = self.plan.wgrad - set(self.writes)
+        assert not bad and not missing, f"backward plan: gradients written {bad}, never written {sorted(missing)}"
+
+
+def _wgrad(x: Sl, cin_w: int, dy: Sl, G: _Grads, wname: str, bname: Optional[str], ws, ksize,
            alpha=1.0, math=K.MATH_F32):
-    """ws: the shared workspace (reduce behind the kernel) or a _ReduceQueue (reduce deferred into its next batch)"""
+    """ws: the shared workspace (reduce behind the kernel) or a _ReduceQueue (reduce deferred into its next batch).  Nothing runs
+    when neither gradient is planned; a frozen bias is not formed, a frozen weight next to a trained bias goes to a sink."""
+    dw, db = G.get(wname), G.get(bname) if bname else None
+    if dw is None and db is None:
+        return
+    if dw is None:
+        dw = torch.empty_like(G.P[wname])
     if isinstance(ws, _ReduceQueue):
-        K.conv_wgrad(x, cin_w, dy, G[wname], G[bname] if bname else None, ws.ws(), ksize, alpha=alpha, math=math, defer=ws.jobs)
+        K.conv_wgrad(x, cin_w, dy, dw, db, ws.ws(), ksize, alpha=alpha, math=math, defer=ws.jobs)
     else:
-        K.conv_wgrad(x, cin_w, dy, G[wname], G[bname] if bname else None, ws, ksize, alpha=alpha, math=math)
+        K.conv_wgrad(x, cin_w, dy, dw, db, ws, ksize, alpha=alpha, math=math)
 
 
 def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, math: int = K.MATH_F32,
@@ -393,14 +497,21 @@ def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, m
 
 
 def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
-             deterministic: bool = False, dframes: Optional[torch.Tensor] = None) -> None:
-    """Write the gradient of every parameter into G[name] (each exactly once, overwrite).  deterministic: the warp gradient
-    without float atomics for any flow (every other kernel of the backward sums in a fixed order already).
+             deterministic: bool = False, dframes: Optional[torch.Tensor] = None, plan: Optional[BackwardPlan] = None) -> None:
+    """Write the gradient of every parameter of the plan into G[name] (each exactly once, overwrite).  deterministic: the warp
+    gradient without float atomics for any flow (every other kernel of the backward sums in a fixed order already).
     dframes (B,T,Cimg,H,W) fp32: also write the gradient w.r.t. the input frames (overwrite) - two launches behind the
-    parameter gradients, which stay exactly what they are without it."""
+    parameter gradients, which stay exactly what they are without it.
+    plan (backward_plan): the gradients to form; every launch it does not need is skipped (frozen layers), and the gradients it
+    forms are bit-identical to the all-trainable backward's.  None: every name in G, and the frames when dframes is given."""
     if sv.feat0 is None:
         raise RuntimeError("forward(features=...) is an inference path: its result cannot be differentiated")
     g = sv.g
+    if plan is None:
+        plan = backward_plan(G.keys(), dframes is not None, g.NB, g.T)
+    assert plan.frames == (dframes is not None), "backward: dframes and the plan disagree"
+    run, dxs = plan.run, plan.dx
+    G = _Grads(G, plan, P)
     dev = dout.device
     B, T, H, W, NI, NO, c, F = g.B, g.T, g.H, g.W, g.NI, g.NO, g.c, g.F
     math, act_dtype = sv.math, sv.act_dtype
@@ -416,17 +527,50 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     # have a batched launch of their own below)
     packs = _Packs(P, math)
     pre_a = "temporal_aggregator.attention."
-    reqs = [("upsampler.conv.weight", True, g.Up, F), ("gff.0.weight", True, F, F), (pre_a + "4.weight", True, g.Tp, F),
-            (pre_a + "2.weight", True, F, F), (pre_a + "0.weight", True, F, T * F)]
+    # (only the packs of the input-gradient convs that run)
+    reqs = [r for st, r in (("up", ("upsampler.conv.weight", True, g.Up, F)), ("gff", ("gff.0.weight", True, F, F)),
+                            ("att.4", (pre_a + "4.weight", True, g.Tp, F)), ("att.2", (pre_a + "2.weight", True, F, F)),
+                            ("att.0", (pre_a + "0.weight", True, F, T * F))) if st in dxs]
     if NO:
         reqs += [(f"motion_estimator.flow_net.{idx}.weight", True, cs, keep)
-                 for idx, cs, keep in zip((6, 4, 2, 0), (4, K.pad4(32), K.pad4(64), K.pad4(128)), (32, 64, 128, 81))]
-    packs.prefetch(reqs)
+                 for idx, cs, keep in zip((6, 4, 2, 0), (4, K.pad4(32), K.pad4(64), K.pad4(128)), (32, 64, 128, 81))
+                 if f"flow.{idx}" in dxs]
+    if reqs:
+        packs.prefetch(reqs)
 
     # ---- upsampler tail
     du = _new(dev, B, H, W, g.Up)
     K.shuffle_clamp_backward(dout, sv.passmask, g.s, du)
     _wgrad(Sl(sv.fused), F, Sl(du, g.U), G, "upsampler.conv.weight", "upsampler.conv.bias", wq, 3, math=math)
+    # Frozen layers: the stages below run while something upstream of them, or one of their own parameters, needs a gradient
+    # (plan.run); past the last such stage the pass ends.
+    head = _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws)
+    if small:
+        wq.flush()
+    G.check()
+    if dframes is not None:
+        # the head conv's input gradient for all T frames (same operands as its weight gradient above), then the bicubic
+        # skip's adjoint onto the centre frame, masked by the clamp
+        dcur, dfeat_all = head
+        wh = P["feature_extractor.head.0.weight"]
+        if sv.img8 is not None:
+            K.head_dgrad(dcur, wh, B, g.slots, dframes)
+        else:
+            K.head_dgrad(dcur, wh, B, g.slots, dframes, act=sv.feat0, dout2=dfeat_all)
+        K.bicubic_adjoint(dout, sv.passmask, g.s, c, 1.0, dframes, accumulate=True)
+
+
+def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws):
+    """backward() behind the upsampler's weight gradient -> (gradient at the head conv's output, feature gradient) when the
+    extractor's backward ran, else None"""
+    g = sv.g
+    dev = dout.device
+    B, T, H, W, NI, NO, c, F = g.B, g.T, g.H, g.W, g.NI, g.NO, g.c, g.F
+    math, act_dtype = sv.math, sv.act_dtype
+    nb = g.NB
+    run, dxs = plan.run, plan.dx
+    if "up" not in dxs:
+        return None
     # bf16 activation mode with reference frames: the feature gradient is FINISHED by the two correlation gradients, which write it
     # as bf16 (dfeat16, below).  Its terms then never meet in an fp32 accumulator: the upsampler input-gradient conv's second
     # output, the attention path's slice of daligned and the warp gradient are bf16 addends of those last passes (no fp32
@@ -444,6 +588,8 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     # ---- gff
     xN = sv.xloc(nb)
     _wgrad(xN, F, Sl(dg), G, "gff.0.weight", "gff.0.bias", wq, 3, math=math)
+    if "gff" not in dxs:          # (the centre features' share, dfeat_c above, only matters when the extractor is trained)
+        return None
     # gradient buffers of the dense blocks, layout [gout(F) | dy_4 | dy_3 | dy_2 | dy_1 | dy_0] (ping-pong)
     dcats = [K.CatBuf(dev, B, H, W, F, LAYERS, g.CATLD, act_dtype, sv.planar) for _ in range(2)] if nb else []
     dagg = _new(dev, B, H, W, F, dtype=sv.cbam_dtype)
@@ -460,17 +606,28 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     reqs = []
     for k in range(nb):
         pre = f"residual_blocks.{k}."
+        if f"rdb.{k}" not in run:
+            continue
         wb, wbx = K.rdb_backward_weights(P[pre + "lff.weight"], [P[pre + f"layers.{i}.0.weight"] for i in range(LAYERS)], F)
         reqs += [(wb[j], False, F + GROWTH * j, None) for j in range(LAYERS)] + [(wbx, False, g.CAT, None)]
     mirror = K.conv_pack_many(reqs, math)
+    # blocks whose backward runs: a suffix k0 .. nb-1 (an upstream need of block k is one of block k + 1)
+    ran = [k for k in range(nb) if f"rdb.{k}" in run]
     for k in range(nb - 1, -1, -1):
+        if k not in ran:
+            break
         cat = sv.cats[k]
         dcat = dcats[k & 1]
         pre = f"residual_blocks.{k}."
         gout = dcat.x()
         _wgrad(cat.inp(g.CAT), g.CAT, gout, G, pre + "lff.weight", pre + "lff.bias", wq, 1, alpha=0.2, math=math)
-        wpb = mirror[k * (LAYERS + 1):(k + 1) * (LAYERS + 1)]     # packs of Wb_4 .. Wb_0, Wb_x
-        for i in range(LAYERS - 1, -1, -1):
+        j = ran.index(k)
+        wpb = mirror[j * (LAYERS + 1):(j + 1) * (LAYERS + 1)]     # packs of Wb_4 .. Wb_0, Wb_x
+        # dy_i is needed for the block's own input gradient or for the weight gradient of layer i or a layer below it
+        lowest = 0 if f"rdb.{k}" in dxs else min(
+            [i for i in range(LAYERS) if pre + f"layers.{i}.0.weight" in G.plan.wgrad or pre + f"layers.{i}.0.bias" in G.plan.wgrad],
+            default=LAYERS)
+        for i in range(LAYERS - 1, lowest - 1, -1):
             cinb = F + GROWTH * (LAYERS - 1 - i)            # channels [0, cinb) = gout, dy_4 .. dy_{i+1}
             dy = dcat.y(LAYERS - 1 - i)                      # slot of dy_i (channels [cinb, cinb + 32) of the buffer)
             if sv.bits is not None:
@@ -482,9 +639,13 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
             cin = F + GROWTH * i
             _wgrad(cat.inp(cin), cin, dy, G, pre + f"layers.{i}.0.weight", pre + f"layers.{i}.0.bias", wq, 3,
                    math=math)
+        if f"rdb.{k}" not in dxs:
+            break
         nxt = dcats[(k - 1) & 1].x() if k > 0 else Sl(dagg)
         K.conv_forward(dcat.inp(g.CAT), wpb[LAYERS], None, nxt, 3, res=gout, math=math, center_cin=ctr)
     K.TIMER_TAG = ""
+    if "cbam" not in run:
+        return None
     dprev = Sl(dagg)
 
     _capture("dagg", lambda: dprev.t[..., dprev.coff:dprev.coff + F].float())
@@ -495,14 +656,21 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     dpre = _new(dev, B, H, W)
     K.cbam_bwd_spatial_pre(dprev, sv.weighted, sv.ca, sv.sa, dpre)
     dsm = _new(dev, B, H, W, 2)
-    K.cbam_bwd_spatial_conv(dpre, sv.sm, w7, dsm, G["temporal_aggregator.refine.spatial_attention.conv.weight"], ws)
+    # (frozen CBAM weights: the _ex forms, the same dsm / dgap_pix without the weight gradients)
+    K.cbam_bwd_spatial_conv(dpre, sv.sm, w7, dsm, G.get("temporal_aggregator.refine.spatial_attention.conv.weight"), ws)
+    fc0, fc2 = "temporal_aggregator.refine.channel_attention.fc.0.weight", "temporal_aggregator.refine.channel_attention.fc.2.weight"
+    if "cbam" not in dxs and fc0 not in G.plan.wgrad and fc2 not in G.plan.wgrad:
+        return None
     dweighted = _new(dev, B, H, W, F, dtype=sv.cbam_dtype)
     dca_partial = _new(dev, B, sv.nblk, F)
     K.cbam_bwd_scale(dprev, sv.weighted, sv.ca, sv.sa, dsm, sv.amax, dweighted, dca_partial)
     dgap_pix = _new(dev, B, F)
-    K.cbam_bwd_channel(dca_partial, sv.nblk, F, g.R, B, H * W, w1, w2, sv.gap, sv.hid, sv.ca,
-                       G["temporal_aggregator.refine.channel_attention.fc.0.weight"],
-                       G["temporal_aggregator.refine.channel_attention.fc.2.weight"], dgap_pix)
+    dw1, dw2 = G.get(fc0), G.get(fc2)
+    if (dw1 is None) != (dw2 is None):                     # one of the two frozen: the full form, the other into a sink
+        dw1, dw2 = (dw1 if dw1 is not None else torch.empty_like(P[fc0])), (dw2 if dw2 is not None else torch.empty_like(P[fc2]))
+    K.cbam_bwd_channel(dca_partial, sv.nblk, F, g.R, B, H * W, w1, w2, sv.gap, sv.hid, sv.ca, dw1, dw2, dgap_pix)
+    if "cbam" not in dxs:
+        return None
 
     # ---- softmax-weighted sum and the attention convs
     daligned = _new(dev, B, H, W, T * F, dtype=sv.aligned.dtype)   # stored like `aligned` (bf16 in the bf16 activation mode)
@@ -510,17 +678,22 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     K.tsum_backward(dweighted, dgap_pix, sv.aligned, sv.attn, T, F, daligned, dlogits)
     pre = "temporal_aggregator.attention."
     _wgrad(Sl(sv.a2), F, Sl(dlogits, T), G, pre + "4.weight", pre + "4.bias", wq, 3, math=math)
-    da2 = _new(dev, B, H, W, F, dtype=act_dtype)
-    K.conv_forward(Sl(dlogits), packs.get(pre + "4.weight", True, g.Tp, F), None, Sl(da2), 3,
-                   mask=Sl(sv.a2), mask_c0=0, mask_c1=F, math=math)
-    _wgrad(Sl(sv.a1), F, Sl(da2), G, pre + "2.weight", pre + "2.bias", wq, 3, math=math)
-    da1 = _new(dev, B, H, W, F, dtype=act_dtype)
-    if sv.a1_bits is not None:
-        K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3, math=math, bits=sv.a1_bits, bits_mode=2)
-    else:
-        K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3,
-                       mask=Sl(sv.a1), mask_c0=0, mask_c1=F, math=math)
-    _wgrad(Sl(sv.aligned), T * F, Sl(da1), G, pre + "0.weight", pre + "0.bias", wq, 3, math=math)
+    if "att.4" in dxs:
+        da2 = _new(dev, B, H, W, F, dtype=act_dtype)
+        K.conv_forward(Sl(dlogits), packs.get(pre + "4.weight", True, g.Tp, F), None, Sl(da2), 3,
+                       mask=Sl(sv.a2), mask_c0=0, mask_c1=F, math=math)
+        _wgrad(Sl(sv.a1), F, Sl(da2), G, pre + "2.weight", pre + "2.bias", wq, 3, math=math)
+    if "att.2" in dxs:
+        da1 = _new(dev, B, H, W, F, dtype=act_dtype)
+        if sv.a1_bits is not None:
+            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3, math=math, bits=sv.a1_bits, bits_mode=2)
+        else:
+            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3,
+                           mask=Sl(sv.a1), mask_c0=0, mask_c1=F, math=math)
+        _wgrad(Sl(sv.aligned), T * F, Sl(da1), G, pre + "0.weight", pre + "0.bias", wq, 3, math=math)
+    if "att.0" not in dxs:
+        # nothing before the attention convs needs a gradient: no motion or extractor backward
+        return None
     K.conv_forward(Sl(da1), packs.get(pre + "0.weight", True, F, T * F), None, Sl(daligned), 3,
                    accumulate=True, math=math)
     if not feat16:
@@ -551,6 +724,8 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
             name = f"motion_estimator.flow_net.{idx}."
             x_sl = Sl(x_t) if li > 0 else Sl(x_t, CORR_LD, 0)
             _wgrad(x_sl, chans[li], Sl(dy_t, dy_c), G, name + "weight", name + "bias", wq, 3, math=math)
+            if f"flow.{idx}" not in dxs:
+                break
             cin_store = dy_t.shape[-1]
             wp = packs.get(name + "weight", True, cin_store, chans[li])
             dx_t = _new(dev, NO, H, W, x_t.shape[-1], dtype=act_dtype if li > 0 else x_t.dtype)
@@ -568,6 +743,9 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
         dcorr = dy_t
         _capture("f1", acts[1])
         _capture("dflow", dflow)
+        if "flow.0" not in dxs:
+            # a trained flow net in front of a frozen extractor (and frames without a gradient): the pass ends here
+            return None
         _capture("dcorr", dcorr)
         center = Sl(sv.aligned, F, c * F)
         # The two correlation gradients are the LAST terms of the feature gradient.  bf16 activation mode: they write the finished
@@ -588,48 +766,63 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
             K.correlation_backward(2, dcorr, Sl(sv.feat_oth), Sl(dfeat_c), True, math=math, groups=T - 1)
 
     # ---- feature extractor (all frames batched)
+    if "body.2" not in run:                     # (T = 1: no motion path, the attention convs' need decides)
+        return None
     _capture("dfeat_all", lambda: dfeat_all.float())
     dcur = dfeat_all
     bn_sums = None                    # BatchNorm-backward sums of layer k, when the depthwise backward of layer k + 1 left them
+    bn_targets = None                 # ... and the dgamma / dbeta that call wrote
     # (built and measured, off by default: with the sums in it the depthwise backward only fits its registers with two instead
     # of five unrolled rows, and the step is 0.2 ms SLOWER than with the separate 0.54 ms reduce passes it replaces)
     fuse_sums = os.environ.get("NVQ_FUSED_BN_SUMS", "0") != "0"
     for k in (2, 1, 0):
         pre = f"feature_extractor.body.{k}."
+        if f"body.{k}" not in run:                # the layers below need nothing either
+            break
+        need_dx = f"body.{k}" in dxs
         dd = _new(dev, NI, H, W, F, dtype=act_dtype)
         fused_bwd = (math == K.MATH_BF16 and act_dtype == torch.bfloat16 and F == 64 and sv.pws[k].dtype == torch.bfloat16
                      and sv.dws[k].dtype == torch.bfloat16)
         if fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
             # BatchNorm backward + the pointwise conv's input and weight gradients in one pass behind the BatchNorm sums: dp is
-            # formed in LDS and never stored (nvq_pw_bn_backward)
+            # formed in LDS and never stored (nvq_pw_bn_backward; a frozen pointwise weight or BatchNorm affine: the _ex form)
+            dgam, dbet = bn_targets if bn_sums is not None else (G.get(pre + "bn.weight"), G.get(pre + "bn.bias"))
             K.pw_bn_backward(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                             P[pre + "bn.bias"], sv.training, P[pre + "pointwise.weight"], dd, G[pre + "bn.weight"],
-                             G[pre + "bn.bias"], G[pre + "pointwise.weight"], ws, sums_in=bn_sums)
+                             P[pre + "bn.bias"], sv.training, P[pre + "pointwise.weight"], dd, dgam, dbet,
+                             G.get(pre + "pointwise.weight"), ws, sums_in=bn_sums)
             bn_sums = None
         else:
             dp = _new(dev, NI, H, W, F, dtype=act_dtype)
             K.bn_relu_backward(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                               P[pre + "bn.bias"], sv.training, dp, G[pre + "bn.weight"], G[pre + "bn.bias"], ws)
+                               P[pre + "bn.bias"], sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
             _wgrad(Sl(sv.dws[k]), F, Sl(dp), G, pre + "pointwise.weight", None, wq, 1, math=math)
             K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
         xin, xin_bn = sv.dw_in[k]
+        dww = G.get(pre + "depthwise.weight")
         if fused_bwd and k > 0 and xin.dtype == torch.bfloat16 and os.environ.get("NVQ_FUSED_DW_BWD", "1") != "0":
             # the depthwise conv's input gradient and weight gradient from one staged tile (nvq_dwconv_backward).  Not for the
             # first layer: with the skip-path add and the head's ReLU mask in its epilogue the one-tile kernel takes as long as
-            # the two launches below (2.53 vs 2.54 ms: the epilogue operands are loaded where they are used, by 8 waves per CU)
+            # the two launches below (2.53 vs 2.54 ms: the epilogue operands are loaded where they are used, by 8 waves per CU).
+            # A frozen depthwise weight: dx alone (dweight None -> the _ex form)
+            if not need_dx and dww is None:
+                break
             dx = _new(dev, NI, H, W, F, dtype=act_dtype)
             prev = f"feature_extractor.body.{k - 1}."
-            if fuse_sums and sv.training and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
+            if fuse_sums and sv.training and need_dx and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
                 # ... and the backward sums of layer k - 1's BatchNorm: this kernel holds its input (xin) and the gradient of
                 # its activation (dx), so the next pw_bn_backward needs no reduce pass of its own
                 bn_sums = _new(dev, T, 2, F)
-                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, G[pre + "depthwise.weight"], ws,
-                                  bn_sums=bn_sums, bn_dgamma=G[prev + "bn.weight"], bn_dbeta=G[prev + "bn.bias"])
+                bn_targets = (G.sink(prev + "bn.weight"), G.sink(prev + "bn.bias"))
+                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws,
+                                  bn_sums=bn_sums, bn_dgamma=bn_targets[0], bn_dbeta=bn_targets[1])
             else:
-                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, G[pre + "depthwise.weight"], ws)
+                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws)
             dcur = dx
             continue
-        K.dwconv_wgrad(xin, dd, G[pre + "depthwise.weight"], ws, bn=xin_bn)
+        if dww is not None:
+            K.dwconv_wgrad(xin, dd, dww, ws, bn=xin_bn)
+        if not need_dx:
+            break
         if k == 0 and sv.img8 is not None:
             # dx + skip path, ReLU-masked by the head features: the gradient of the head conv, as bf16
             dx = _new(dev, NI, H, W, F, dtype=act_dtype)
@@ -638,24 +831,17 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
             dx = _new(dev, NI, H, W, F, dtype=act_dtype if k > 0 else torch.float32)
             K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
         dcur = dx
-    if sv.img8 is not None:
-        K.conv_wgrad(Sl(sv.img8), g.Cimg, Sl(dcur), G["feature_extractor.head.0.weight"],
-                     G["feature_extractor.head.0.bias"], ws, 3, math=math)
-    else:
-        # the skip path of  feat = body(h) + h  is summed inside the head kernel (dout2)
-        K.head_wgrad(sv.frames, g.slots, dcur, sv.feat0, G["feature_extractor.head.0.weight"],
-                     G["feature_extractor.head.0.bias"], ws, dout2=dfeat_all)
-    if small:
-        wq.flush()
-    if dframes is not None:
-        # the head conv's input gradient for all T frames (same operands as its weight gradient above), then the bicubic
-        # skip's adjoint onto the centre frame, masked by the clamp
-        wh = P["feature_extractor.head.0.weight"]
-        if sv.img8 is not None:
-            K.head_dgrad(dcur, wh, B, g.slots, dframes)
-        else:
-            K.head_dgrad(dcur, wh, B, g.slots, dframes, act=sv.feat0, dout2=dfeat_all)
-        K.bicubic_adjoint(dout, sv.passmask, g.s, c, 1.0, dframes, accumulate=True)
+    if "head" in run:
+        hw, hb = G.get("feature_extractor.head.0.weight"), G.get("feature_extractor.head.0.bias")
+        if hw is not None or hb is not None:
+            hw = hw if hw is not None else torch.empty_like(P["feature_extractor.head.0.weight"])
+            if sv.img8 is not None:
+                K.conv_wgrad(Sl(sv.img8), g.Cimg, Sl(dcur), hw, hb, ws, 3, math=math)
+            else:
+                # the skip path of  feat = body(h) + h  is summed inside the head kernel (dout2)
+                K.head_wgrad(sv.frames, g.slots, dcur, sv.feat0, hw, hb if hb is not None else G.sink("feature_extractor.head.0.bias"),
+                             ws, dout2=dfeat_all)
+    return dcur, dfeat_all
 
 
 # ----------------------------------------------------------------------------- LightweightSuperResolution
@@ -710,8 +896,14 @@ def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, train
 
 
 def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
-                   dframes: Optional[torch.Tensor] = None) -> None:
-    """dframes (B,1,3,H,W) fp32: also write the gradient w.r.t. the input image (overwrite)."""
+                   dframes: Optional[torch.Tensor] = None, plan: Optional[BackwardPlan] = None) -> None:
+    """dframes (B,1,3,H,W) fp32: also write the gradient w.r.t. the input image (overwrite).  plan (light_backward_plan): as in
+    backward(); None: every name in G, and the image when dframes is given."""
+    if plan is None:
+        plan = light_backward_plan(G.keys(), dframes is not None)
+    assert plan.frames == (dframes is not None), "light_backward: dframes and the plan disagree"
+    run, dxs = plan.run, plan.dx
+    G = _Grads(G, plan, P)
     dev = dout.device
     B, _, Cimg, H, W = sv.frames.shape
     F, math, act_dtype = LIGHT_F, sv.math, sv.act_dtype
@@ -720,22 +912,37 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
     K.shuffle_clamp_backward(dout, sv.passmask, sv.scale, du)
     last = sv.acts[-1]
     _wgrad(Sl(last), F, Sl(du, sv.U), G, "net.6.weight", "net.6.bias", ws, 3, math=math)
-    dcur = _new(dev, B, H, W, F)
-    K.conv_forward(Sl(du), K.conv_pack(P["net.6.weight"], True, sv.Up, F, math=math), None, Sl(dcur), 3, math=math)
+    dcur = None
+    if "up" in dxs:
+        dcur = _new(dev, B, H, W, F)
+        K.conv_forward(Sl(du), K.conv_pack(P["net.6.weight"], True, sv.Up, F, math=math), None, Sl(dcur), 3, math=math)
     for j in range(len(LIGHT_BLOCKS) - 1, -1, -1):
+        if f"block.{j}" not in run:             # (nor any block below it)
+            break
         pre = f"net.{LIGHT_BLOCKS[j]}."
         dp = _new(dev, B, H, W, F, dtype=act_dtype)
         K.bn_relu_backward(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                           sv.training, dp, G[pre + "bn.weight"], G[pre + "bn.bias"], ws)
+                           sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
         _wgrad(Sl(sv.dws[j]), F, Sl(dp), G, pre + "pointwise.weight", None, ws, 1, math=math)
+        dww = G.get(pre + "depthwise.weight")
+        if dww is None and f"block.{j}" not in dxs:
+            break
         dd = _new(dev, B, H, W, F, dtype=act_dtype)
         K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
         xin = sv.feat0 if j == 0 else sv.acts[j - 1]
-        K.dwconv_wgrad(xin, dd, G[pre + "depthwise.weight"], ws)
+        if dww is not None:
+            K.dwconv_wgrad(xin, dd, dww, ws)
+        if f"block.{j}" not in dxs:
+            break
         dx = _new(dev, B, H, W, F, dtype=act_dtype if j > 0 else torch.float32)
         K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
         dcur = dx
-    K.head_wgrad(sv.frames, [0], dcur, sv.feat0, G["net.0.weight"], G["net.0.bias"], ws)
+    if "head" in run:
+        hw, hb = G.get("net.0.weight"), G.get("net.0.bias")
+        if hw is not None or hb is not None:
+            K.head_wgrad(sv.frames, [0], dcur, sv.feat0, hw if hw is not None else torch.empty_like(P["net.0.weight"]),
+                         hb if hb is not None else torch.empty_like(P["net.0.bias"]), ws)
+    G.check()
     if dframes is not None:
         K.head_dgrad(dcur, P["net.0.weight"], B, [0], dframes, act=sv.feat0)
         K.bicubic_adjoint(dout, sv.passmask, sv.scale, 0, 1.0, dframes, accumulate=True)

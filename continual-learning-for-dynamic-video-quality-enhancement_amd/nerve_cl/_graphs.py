@@ -20,7 +20,9 @@ Rules (checked, never assumed):
     overwritten by a later replay raises;
   * outputs and gradients handed to autograd are copies: autograd may keep a gradient tensor as ``p.grad``, and the next
     replay would overwrite it;
-  * the kernel timer of ``bench.py`` and ``return_intermediate`` use the eager path.
+  * the kernel timer of ``bench.py`` and ``return_intermediate`` use the eager path;
+  * the need mask (which parameters have requires_grad) is part of the key: the backward graph forms only the planned gradients
+    (frozen layers), so a step after a ``requires_grad`` toggle captures an entry of its own.
 """
 from __future__ import annotations
 
@@ -51,6 +53,7 @@ class _Entry:
         self.gen = 0                 # replays of the forward graph so far
         self.pending = None          # weakref to the token of the forward whose backward has not run yet
         self.deterministic = False   # the backward graph's warp gradient mode (part of the key)
+        self.plan = None             # the backward plan (its need mask is part of the key)
         self.eager_calls = 0
 
 
@@ -67,12 +70,15 @@ class StepGraphs:
         self.eager_fallbacks = 0
 
     # ------------------------------------------------------------------ forward
-    def forward(self, net, frames: torch.Tensor, need_grad: bool, act_dtype, deterministic: bool = False):
-        """-> (out, entry, token, gen) or None when this call has to run eagerly."""
+    def forward(self, net, frames: torch.Tensor, need_grad: bool, act_dtype, deterministic: bool = False, plan=None):
+        """-> (out, entry, token, gen) or None when this call has to run eagerly.  plan: the backward plan of a step that needs
+        gradients (None: every parameter's)."""
         if _nvq.TIMER is not None:
             return None
+        if need_grad and plan is None:
+            plan = _engine.backward_plan(net._param_names, False, net._NB, net.num_frames)
         key = (tuple(frames.shape), bool(net.training), net.math_mode, act_dtype, bool(need_grad), frames.device.index,
-               bool(deterministic))
+               bool(deterministic), plan.key() if need_grad else None)
         P = net._tensor_dict()
         ptrs = tuple(t.data_ptr() for t in P.values())
         e = self.entries.get(key)
@@ -87,6 +93,7 @@ class StepGraphs:
                 return None
             e = self.entries[key] = _Entry()
             e.deterministic = bool(deterministic)
+            e.plan = plan if need_grad else None
         if e.fwd is None:
             if e.eager_calls < self.WARMUP:
                 e.eager_calls += 1
@@ -131,7 +138,8 @@ class StepGraphs:
             torch.cuda.synchronize()
             with torch.cuda.graph(g, pool=e.pool):
                 flat, views = net._new_grad_bucket()
-                _engine.backward(net._tensor_dict(), e.sv, e.static_dout, views, deterministic=e.deterministic)
+                _engine.backward(net._tensor_dict(), e.sv, e.static_dout, {n: views[n] for n in e.plan.wgrad},
+                                 deterministic=e.deterministic, plan=e.plan)
             e.bwd, e.flat = g, flat
             e.sv = None                                        # the graphs own the state now
         else:

@@ -107,8 +107,11 @@ SIGNATURES = {
     "nvq_bn_apply_relu": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp]),
     "nvq_bn_relu_backward": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, sz, ci, ci, ci, ci, vp]),
     "nvq_dwconv_backward": (ci, [vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "nvq_dwconv_backward_ex": (ci, [vp, ci, vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, sz, ci, vp]),
     "nvq_dwpw_forward": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, cf, cf, _IP, vp, vp, vp, vp, vp, sz, vp]),
     "nvq_pw_bn_backward": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "nvq_pw_bn_backward_ex": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, sz, ci,
+                                   vp]),
     "nvq_correlation_forward": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp]),
     "nvq_correlation_backward": (ci, [ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp]),
     "nvq_warp_forward": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp]),
@@ -124,8 +127,10 @@ SIGNATURES = {
     "nvq_cbam_spatial_apply": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
     "nvq_cbam_bwd_spatial_pre": (ci, [vp, ci, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp]),
     "nvq_cbam_bwd_spatial_conv": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, sz, ci, vp]),
+    "nvq_cbam_bwd_spatial_conv_ex": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, sz, ci, ci, vp]),
     "nvq_cbam_bwd_scale": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, vp]),
     "nvq_cbam_bwd_channel": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
+    "nvq_cbam_bwd_channel_ex": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     "nvq_upsampler_tail_forward": (ci, [C.POINTER(ConvDesc), vp, ci, ci, ci, ci, vp, vp, vp]),
     "nvq_shuffle_bicubic_clamp": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
     "nvq_shuffle_clamp_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp]),
@@ -675,7 +680,8 @@ def dwconv_backward(x: torch.Tensor, bn, dy: torch.Tensor, weight: torch.Tensor,
     """Input and weight gradient of a 64-channel depthwise 3x3 conv from one staged tile (bf16 mode): see nvq_dwconv_backward.
     bn = (mean, invstd, gamma, beta, group_images): the conv was fed relu(bn(x)); add (fp32) / mask (bf16): dx = (dx + add)
     where mask > 0.  bn_sums [G, 2, 64] (+ bn_dgamma, bn_dbeta [64]): also return the backward sums of that BatchNorm (its input is
-    x, the gradient of its activation is dx) - pw_bn_backward(..., sums_in=bn_sums) then skips its reduce pass."""
+    x, the gradient of its activation is dx) - pw_bn_backward(..., sums_in=bn_sums) then skips its reduce pass.
+    dweight None (a frozen depthwise weight): dx alone, nvq_dwconv_backward_ex(NVQ_NO_WGRAD)."""
     N, H, W, ld = x.shape
     assert x.dtype == dy.dtype == dx.dtype == torch.bfloat16 and weight.shape[0] == 64
     b = _bn_input(bn)
@@ -684,10 +690,13 @@ def dwconv_backward(x: torch.Tensor, bn, dy: torch.Tensor, weight: torch.Tensor,
         e = DwEpilogue()
         e.add, e.add_ld, e.add_bf16 = ptr(add), add.shape[-1] if add is not None else 0, is_bf16(add)
         e.mask, e.mask_ld, e.mask_bf16 = ptr(mask), mask.shape[-1] if mask is not None else 0, is_bf16(mask)
-    check(lib().nvq_dwconv_backward(ptr(x), ld, C.byref(b) if b is not None else None, ptr(dy), dy.shape[-1],
-                                    ptr(weight.contiguous()), ptr(dx), dx.shape[-1], C.byref(e) if e is not None else None,
-                                    N, H, W, ptr(dweight), ptr(bn_sums), ptr(bn_dgamma), ptr(bn_dbeta), ptr(ws), ws.numel() * 4,
-                                    stream()), "nvq_dwconv_backward")
+    args = (ptr(x), ld, C.byref(b) if b is not None else None, ptr(dy), dy.shape[-1], ptr(weight.contiguous()), ptr(dx),
+            dx.shape[-1], C.byref(e) if e is not None else None, N, H, W, ptr(dweight), ptr(bn_sums), ptr(bn_dgamma),
+            ptr(bn_dbeta), ptr(ws), ws.numel() * 4)
+    if dweight is None:
+        check(lib().nvq_dwconv_backward_ex(*args, NO_WGRAD, stream()), "nvq_dwconv_backward_ex")
+        return
+    check(lib().nvq_dwconv_backward(*args, stream()), "nvq_dwconv_backward")
 
 
 def dwpw_forward(x: torch.Tensor, bn, dw_weight: torch.Tensor, pw_weight: torch.Tensor, d: torch.Tensor, p: torch.Tensor,
@@ -712,14 +721,19 @@ def dwpw_forward(x: torch.Tensor, bn, dw_weight: torch.Tensor, pw_weight: torch.
 
 def pw_bn_backward(dy: torch.Tensor, p: torch.Tensor, d: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
                    training: bool, weight: torch.Tensor, dd: torch.Tensor, dgamma, dbeta, dweight, ws, sums_in=None) -> None:
-    """Backward of pointwise conv -> BatchNorm -> ReLU in one pass (bf16 mode, 64 channels): see nvq_pw_bn_backward."""
+    """Backward of pointwise conv -> BatchNorm -> ReLU in one pass (bf16 mode, 64 channels): see nvq_pw_bn_backward.
+    dweight None (a frozen pointwise weight) and / or dgamma, dbeta None (a frozen BatchNorm affine): nvq_pw_bn_backward_ex,
+    dd is the same either way."""
     N, H, W, _ = p.shape
     assert p.dtype == d.dtype == dd.dtype == torch.bfloat16 and tuple(weight.shape[:2]) == (64, 64)
     ev0 = TIMER.start() if TIMER is not None else None
-    check(lib().nvq_pw_bn_backward(ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], ptr(d), d.shape[-1], N,
-                                   group_images, H, W, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), int(training),
-                                   ptr(weight.contiguous()), ptr(dd), dd.shape[-1], ptr(dgamma), ptr(dbeta), ptr(dweight),
-                                   ptr(sums_in), ptr(ws), ws.numel() * 4, stream()), "nvq_pw_bn_backward")
+    args = (ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], ptr(d), d.shape[-1], N, group_images, H, W, ptr(mean),
+            ptr(invstd), ptr(gamma), ptr(beta), int(training), ptr(weight.contiguous()), ptr(dd), dd.shape[-1], ptr(dgamma),
+            ptr(dbeta), ptr(dweight), ptr(sums_in), ptr(ws), ws.numel() * 4)
+    if dweight is None or dgamma is None or dbeta is None:
+        check(lib().nvq_pw_bn_backward_ex(*args, NO_WGRAD if dweight is None else 0, stream()), "nvq_pw_bn_backward_ex")
+    else:
+        check(lib().nvq_pw_bn_backward(*args, stream()), "nvq_pw_bn_backward")
     if ev0 is not None:
         npx = N * H * W
         TIMER.stop(ev0, "pw_bn_bwd_kernel", 2.0 * npx * 64 * 64 * 2,
@@ -763,6 +777,7 @@ def warp_forward(feat: Sl, flow: torch.Tensor, out: Sl):
 
 
 WARP_DETERMINISTIC = 1
+NO_WGRAD = 2        # NVQ_NO_WGRAD: the _ex entry points' input gradient without the weight gradient
 
 
 def warp_backward(dout: Sl, feat: Sl, flow: torch.Tensor, dfeat: Sl, dflow: torch.Tensor, gather: bool = True,
@@ -836,7 +851,12 @@ def cbam_bwd_spatial_pre(dout: Sl, x: torch.Tensor, ca, sa, dpre):
 
 
 def cbam_bwd_spatial_conv(dpre, sm, w7, dsm, dw7, ws, accumulate=False):
+    """dw7 None (a frozen spatial-attention conv): dsm alone (nvq_cbam_bwd_spatial_conv_ex, NVQ_NO_WGRAD)"""
     N, H, W = dpre.shape[:3]
+    if dw7 is None:
+        check(lib().nvq_cbam_bwd_spatial_conv_ex(ptr(dpre), ptr(sm), ptr(w7), N, H, W, ptr(dsm), None, ptr(ws), ws.numel() * 4,
+                                                 int(accumulate), NO_WGRAD, stream()), "nvq_cbam_bwd_spatial_conv_ex")
+        return
     check(lib().nvq_cbam_bwd_spatial_conv(ptr(dpre), ptr(sm), ptr(w7), N, H, W, ptr(dsm), ptr(dw7), ptr(ws),
                                           ws.numel() * 4, int(accumulate), stream()), "nvq_cbam_bwd_spatial_conv")
 
@@ -850,6 +870,12 @@ def cbam_bwd_scale(dout: Sl, x: torch.Tensor, ca, sa, dsm, amax, dx: torch.Tenso
 
 
 def cbam_bwd_channel(dca_partial, nblk, Cc, R, N, HW, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix, accumulate=False):
+    """dw1 and dw2 None (a frozen channel attention): dgap_pix alone (nvq_cbam_bwd_channel_ex, NVQ_NO_WGRAD)"""
+    if dw1 is None and dw2 is None:
+        check(lib().nvq_cbam_bwd_channel_ex(ptr(dca_partial), nblk, Cc, R, N, HW, ptr(w1), ptr(w2), ptr(gap), ptr(hid), ptr(ca),
+                                            None, None, ptr(dgap_pix), int(accumulate), NO_WGRAD, stream()),
+              "nvq_cbam_bwd_channel_ex")
+        return
     check(lib().nvq_cbam_bwd_channel(ptr(dca_partial), nblk, Cc, R, N, HW, ptr(w1), ptr(w2), ptr(gap), ptr(hid),
                                      ptr(ca), ptr(dw1), ptr(dw2), ptr(dgap_pix), int(accumulate), stream()),
           "nvq_cbam_bwd_channel")

@@ -178,11 +178,13 @@ class _SRFunction(torch.autograd.Function):
         ctx.net = net
         ctx.graph = ctx.token = None
         ctx.deterministic = resolve_deterministic(net.deterministic)
-        if need_grad:
+        # frozen parameters (requires_grad False): the backward forms only what the need mask asks for
+        ctx.plan = net._backward_plan(ctx.needs_input_grad[3:], ctx.needs_input_grad[1]) if need_grad else None
+        if any(ctx.needs_input_grad[3:]):
             net._mark_awaiting(ctx)
         # (a step whose frames need a gradient runs eagerly: the captured graphs compute no input gradient)
         if net._graphs_wanted(frames) and not want_inter and not ctx.needs_input_grad[1]:
-            hit = net._step_graphs.forward(net, frames, need_grad, act, ctx.deterministic)
+            hit = net._step_graphs.forward(net, frames, need_grad, act, ctx.deterministic, ctx.plan)
             if hit is not None:
                 out, entry, ctx.token, gen = hit
                 ctx.graph = (entry, gen) if need_grad else None
@@ -196,7 +198,7 @@ class _SRFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        net, sv = ctx.net, ctx.sv
+        net, sv, plan = ctx.net, ctx.sv, ctx.plan
         names = net._param_names
         dframes = None
         if ctx.graph is not None:
@@ -205,19 +207,22 @@ class _SRFunction(torch.autograd.Function):
             if sv is None:
                 raise RuntimeError("SuperResolutionNet backward called without saved forward state (a second backward through "
                                    "the same forward needs net.retain_backward_state = True, the analogue of retain_graph)")
-            flat, views = net._new_grad_bucket()
+            # with no trainable parameter (frames' gradient only) no bucket is formed
+            flat, views = net._new_grad_bucket() if any(ctx.needs_input_grad[3:]) else (None, {})
             dframes = torch.empty_like(sv.frames) if ctx.needs_input_grad[1] else None
             with torch.cuda.device(dout.device):
-                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), views, deterministic=ctx.deterministic,
-                                 dframes=dframes)
+                _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), {n: views[n] for n in plan.wgrad},
+                                 deterministic=ctx.deterministic, dframes=dframes, plan=plan)
             # A custom Function cannot see retain_graph, and the state of a 540p step is tens of GB that must not outlive
             # the backward (autograd frees its own saved tensors here too), so it is dropped unless the module asks to keep it.
             if not getattr(net, "retain_backward_state", False):
                 ctx.sv = None
-        # data-parallel all-reduce of the whole bucket (nerve_cl.parallel), then the deferred EWC penalty gradient; the frames'
-        # gradient is local to the rank and stays out of the bucket
-        net._finish_bucket(flat)
-        return (None, dframes, None) + tuple(views[n] for n in names)
+        # data-parallel all-reduce of the whole bucket (nerve_cl.parallel; frozen slots are zero), then the deferred EWC penalty
+        # gradient; the frames' gradient is local to the rank and stays out of the bucket
+        if flat is not None:
+            net._finish_bucket(flat)
+        need = ctx.needs_input_grad[3:]
+        return (None, dframes, None) + tuple(views[n] if w else None for n, w in zip(names, need))
 
 
 class SuperResolutionNet(BucketedNet):
@@ -270,6 +275,16 @@ class SuperResolutionNet(BucketedNet):
         self.deterministic: Optional[bool] = _env_deterministic()
 
     GRAPH_AUTO_MAX_PIXELS = 8 * 3 * 128 * 128     # B*T*H*W up to which a step is launch-bound on MI355X
+
+    def _backward_plan(self, need_mask, frames_need_grad: bool) -> "_engine.BackwardPlan":
+        """The backward plan for the parameters' need mask (one bool per named parameter), cached per mask."""
+        key = (tuple(bool(x) for x in need_mask), bool(frames_need_grad))
+        cache = self.__dict__.setdefault("_plan_cache", {})
+        plan = cache.get(key)
+        if plan is None:
+            plan = cache[key] = _engine.backward_plan([n for n, w in zip(self._param_names, key[0]) if w], key[1], self._NB,
+                                                      self.num_frames)
+        return plan
 
     def _graphs_wanted(self, frames: torch.Tensor) -> bool:
         if self.use_hip_graphs == "auto":
@@ -355,8 +370,13 @@ class _LightFunction(torch.autograd.Function):
         out, sv = _engine.light_forward(net._tensor_dict(), x, net.scale_factor, net.training, net.math_mode, act)
         ctx.net = net
         ctx.sv = sv if (any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[1]) else None
+        ctx.plan = None
         if ctx.sv is not None:
-            net._mark_awaiting(ctx)
+            # frozen parameters: only what the need mask asks for
+            ctx.plan = _engine.light_backward_plan([n for n, w in zip(net._param_names, ctx.needs_input_grad[2:]) if w],
+                                                   ctx.needs_input_grad[1])
+            if any(ctx.needs_input_grad[2:]):
+                net._mark_awaiting(ctx)
         return out
 
     @staticmethod
@@ -364,15 +384,18 @@ class _LightFunction(torch.autograd.Function):
         net, sv = ctx.net, ctx.sv
         if sv is None:
             raise RuntimeError("LightweightSuperResolution backward called without saved forward state")
-        flat, views = net._new_grad_bucket()
+        plan = ctx.plan
+        flat, views = net._new_grad_bucket() if any(ctx.needs_input_grad[2:]) else (None, {})
         dframes = torch.empty_like(sv.frames) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(dout.device):
-            _engine.light_backward(net._tensor_dict(), sv, dout.contiguous().float(), views, dframes=dframes)
+            _engine.light_backward(net._tensor_dict(), sv, dout.contiguous().float(), {n: views[n] for n in plan.wgrad},
+                                   dframes=dframes, plan=plan)
         if not getattr(net, "retain_backward_state", False):
             ctx.sv = None
-        net._finish_bucket(flat)
+        if flat is not None:
+            net._finish_bucket(flat)
         dx = dframes.view(dframes.shape[0], *dframes.shape[2:]) if dframes is not None else None
-        return (None, dx) + tuple(views[n] for n in net._param_names)
+        return (None, dx) + tuple(views[n] if w else None for n, w in zip(net._param_names, ctx.needs_input_grad[2:]))
 
 
 class LightweightSuperResolution(BucketedNet):

@@ -194,6 +194,18 @@ int nvq_pw_bn_backward(const float* dy, int dy_ld, int dy_bf16, const float* p, 
                        const float* gamma, const float* beta, int training, const float* weight, float* dd, int dd_ld,
                        float* dgamma, float* dbeta, float* dweight, const float* sums_in, float* workspace,
                        size_t workspace_bytes, void* stream);
+/* Flags bit of the _ex entry points below: the input gradient alone, without the weight gradient the full form forms as a side
+ * product (a frozen layer).  The input gradient is bit-identical to the full form's; the weight-gradient outputs are neither
+ * written nor read and may be NULL. */
+#define NVQ_NO_WGRAD 2
+/* nvq_pw_bn_backward with a flags word.  flags == 0: exactly nvq_pw_bn_backward.  NVQ_NO_WGRAD: dd alone - d is not read,
+ * dweight is not written (may be NULL), no reduce launch.  dgamma / dbeta may be NULL (a frozen BatchNorm affine, with or without
+ * the flag): the sums dd needs are still formed. */
+int nvq_pw_bn_backward_ex(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
+                          int N, int group_images, int H, int W, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, int training, const float* weight, float* dd, int dd_ld,
+                          float* dgamma, float* dbeta, float* dweight, const float* sums_in, float* workspace,
+                          size_t workspace_bytes, int flags, void* stream);
 
 /* ------------------------------------------------------------------ feature extractor
  * FeatureExtractor.head, super_resolution.py:40-43: relu(conv3x3(frame; W[F,Cin,3,3], b)).
@@ -255,6 +267,12 @@ int nvq_dwconv_backward(const float* x, int x_ld, const nvq_bn_input* bn, const 
                         float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W, float* dweight,
                         float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace, size_t workspace_bytes,
                         void* stream);
+/* nvq_dwconv_backward with a flags word.  flags == 0: exactly nvq_dwconv_backward.  NVQ_NO_WGRAD: dx (and bn_sums) alone -
+ * no depthwise weight gradient (dweight not written, may be NULL), x is staged only for bn_sums. */
+int nvq_dwconv_backward_ex(const float* x, int x_ld, const nvq_bn_input* bn, const float* dy, int dy_ld, const float* weight,
+                           float* dx, int dx_ld, const nvq_dw_epilogue* epi, int N, int H, int W, float* dweight,
+                           float* bn_sums, float* bn_dgamma, float* bn_dbeta, float* workspace, size_t workspace_bytes,
+                           int flags, void* stream);
 /* Forward of  depthwise 3x3 -> pointwise 1x1 (no bias) -> BatchNorm2d statistics  of a DepthwiseSeparableConv
  * (efficient_layers.py:49-66) in the bf16 mode, 64 channels: what nvq_dwconv_forward + nvq_conv_forward (1x1) + nvq_bn_stats
  * do in three launches (five tensor passes), in one pass x -> d, p.  in [N,H,W,in_ld] bf16; bn != NULL: x := relu(bn(x)) is
@@ -419,6 +437,10 @@ int nvq_cbam_bwd_spatial_pre(const float* dout, int dout_ld, int dout_coff, cons
 int nvq_cbam_bwd_spatial_conv(const float* dpre, const float* sm, const float* w7, int N,
                               int H, int W, float* dsm, float* dw7, float* workspace,
                               size_t workspace_bytes, int accumulate, void* stream);
+/* flags == 0: exactly nvq_cbam_bwd_spatial_conv.  NVQ_NO_WGRAD: dsm alone (sm not read, dw7 not written, no workspace). */
+int nvq_cbam_bwd_spatial_conv_ex(const float* dpre, const float* sm, const float* w7, int N,
+                                 int H, int W, float* dsm, float* dw7, float* workspace,
+                                 size_t workspace_bytes, int accumulate, int flags, void* stream);
 /* step3: dxc = dout*sa + dsm0/C + [c==amax] dsm1 ; dx = dxc*ca ;
  *        dca_partial[n][blk][c] = block sums of dxc*x   (nblk = nvq_tsum_blocks) */
 int nvq_cbam_bwd_scale(const float* dout, int dout_ld, int dout_coff, const float* x, int x_ld,
@@ -430,6 +452,11 @@ int nvq_cbam_bwd_channel(const float* dca_partial, int nblk, int C, int R, int N
                          const float* w1, const float* w2, const float* gap, const float* hid,
                          const float* ca, float* dw1, float* dw2, float* dgap_pix,
                          int accumulate, void* stream);
+/* flags == 0: exactly nvq_cbam_bwd_channel.  NVQ_NO_WGRAD: dgap_pix alone (dw1 / dw2 not written, may be NULL). */
+int nvq_cbam_bwd_channel_ex(const float* dca_partial, int nblk, int C, int R, int N, int HW,
+                            const float* w1, const float* w2, const float* gap, const float* hid,
+                            const float* ca, float* dw1, float* dw2, float* dgap_pix,
+                            int accumulate, int flags, void* stream);
 
 /* The whole upsampler tail in one launch (NVQ_MATH_BF16, bf16 input): PixelShuffleUpsampler.conv (3x3, cin -> Cimg*s*s, bias;
  * efficient_layers.py:94-100) whose epilogue puts the tile's conv outputs through LDS, reads them back as s x s pixel blocks
