@@ -28,7 +28,8 @@ BN_MOM = 0.1
 
 _ws_cache: Dict[torch.device, torch.Tensor] = {}
 
-# When set to a dict, backward() stores intermediate gradients in it (tests / debugging only).
+# When set to a dict, forward() stores the flows, the dense blocks' output and the fused features, and backward() the
+# intermediate gradients in it (tests / debugging only).
 DEBUG_CAPTURE: Optional[dict] = None
 
 _TAIL_ROWS = int(os.environ.get("NVQ_TAIL_ROWS", "0"))   # 4: the four-wave rdb_tail kernel (A/B switch, same results)
@@ -275,6 +276,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
             t = g.slots[j]
             K.warp_forward(Sl(feat_oth).images((j - 1) * B, j * B), flow[(j - 1) * B:j * B], Sl(aligned, F, t * F))
     sv.flow = sv.flow_acts[-1] if NO else None
+    _capture("flow", sv.flow)
 
     # ---- temporal aggregation
     a1, a2 = _new(dev, B, H, W, F, dtype=act_dtype), _new(dev, B, H, W, F, dtype=act_dtype)
@@ -352,8 +354,10 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     K.TIMER_TAG = ""
     # ---- global fusion + upsampler tail
     fused, gr = _new(dev, B, H, W, F, dtype=act_dtype), _new(dev, B, H, W, F, dtype=act_dtype)   # conv-to-conv tensors
+    _capture("residual", lambda: xloc(nblocks).t[..., :F].float())
     K.conv_forward(xloc(nblocks), packs.get("gff.0.weight", False, F), P["gff.0.bias"], Sl(fused), 3,
                    relu=True, out2=Sl(gr), res=center, math=math)
+    _capture("fused", lambda: fused.float())
     out = _new(dev, B, g.Cimg, H * scale, W * scale)
     passmask = _new(dev, B, g.Cimg, H * scale, W * scale, dtype=torch.uint8)
     wup = packs.get("upsampler.conv.weight", False, F)

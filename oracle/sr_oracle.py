@@ -296,6 +296,46 @@ def sr_forward(P: Params, lr_frames: torch.Tensor, training: bool = True,
     return out
 
 
+def sr_forward_checkpointed(P: Params, lr_frames: torch.Tensor, training: bool = True):
+    """:func:`sr_forward` with every stage under ``torch.utils.checkpoint`` (non-reentrant): autograd keeps only the stage
+    boundaries, and the backward recomputes one stage at a time.  This is what lets a float64 training step at full size
+    (540x960, B=2) fit in memory.  Same stage functions, same order, same results as ``sr_forward(...,
+    return_intermediate=True)``, whose (out, intermediates) pair it returns.
+
+    The recompute runs :func:`batch_norm_call` a second time, so the backward updates the BatchNorm running statistics
+    and ``num_batches_tracked`` once more: a caller that needs the state after one step snapshots the buffers after the
+    forward and restores them after the backward."""
+    from torch.utils.checkpoint import checkpoint
+
+    def ck(fn, *args):
+        return checkpoint(fn, *args, use_reentrant=False)
+
+    B, T, C, H, W = lr_frames.shape
+    c = T // 2
+    s = scale_of(P, C)
+    feats = [ck(lambda f: feature_extractor(P, f, training), lr_frames[:, t]) for t in range(T)]
+    center = feats[c]
+    aligned, flows = [], {}
+    for t in range(T):
+        if t == c:
+            aligned.append(center)
+            continue
+        fl = ck(lambda a, b: flow_net(P, correlation(a, b)), feats[t], center)
+        flows[t] = fl
+        aligned.append(ck(warp, feats[t], fl))
+    agg = ck(lambda *al: temporal_aggregator(P, list(al)), *aligned)
+    y = agg
+    for k in range(num_blocks(P)):
+        y = ck(lambda v, k=k: residual_dense_block(P, k, v), y)
+    fused = ck(lambda v, ctr: F.relu(F.conv2d(v, P["gff.0.weight"], P["gff.0.bias"], padding=1)) + ctr, y, center)
+
+    def tail(v, frame):
+        up = F.pixel_shuffle(F.conv2d(v, P["upsampler.conv.weight"], P["upsampler.conv.bias"], padding=1), s)
+        return torch.clamp(bicubic_up(frame, s) + up, 0, 1)
+    out = ck(tail, fused, lr_frames[:, c])
+    return out, {"features": feats, "aligned": aligned, "aggregated": agg, "flows": flows, "residual": y, "fused": fused}
+
+
 def compute_psnr(pred: torch.Tensor, target: torch.Tensor) -> float:
     """experiments/train_baseline.py:27-32."""
     mse = torch.mean((pred - target) ** 2)

@@ -67,7 +67,8 @@ def test_135x240_training_step_fp32_every_gradient(oracle_135, oracle_135_f64):
     """Every one of the 131 gradients of the exact-fp32 mode against the fp32 CPU oracle: whole-tensor relative L2 and the
     max-normalised element error both under 1e-3 - or, for a tensor that is not, ATTRIBUTED with the float64 oracle: the HIP
     gradient may sit at most 4x as far from the float64 gradient as the fp32 CPU oracle itself does (+ 2e-5, the kernels'
-    own tolerance).  A tensor listed under that rule is one whose fp32 evaluation is ill-conditioned at this size (tiny
+    own tolerance) - and in any case within L2 1e-2 and max-normalised 2e-2 of the fp32 oracle, for at most 3 listed
+    tensors.  A tensor listed under that rule is one whose fp32 evaluation is ill-conditioned at this size (tiny
     gradients formed by cancellation, ReLU pre-activations within rounding of zero), not one the kernels get wrong: an
     ordering / accumulation defect would put the HIP gradient far from float64 where the CPU oracle is close."""
     x, tgt, o_out, o_loss, ora = oracle_135
@@ -79,13 +80,15 @@ def test_135x240_training_step_fp32_every_gradient(oracle_135, oracle_135_f64):
     assert (out.detach().cpu() - o_out).abs().max().item() < 1e-3
     assert abs(loss.item() - o_loss) < 1e-5 * o_loss
     onamed = ora.named()
-    listed, failed, num, den = [], [], 0.0, 0.0
+    listed, failed, capped, num, den = [], [], [], 0.0, 0.0
     for n, p in net.named_parameters():
         g, r, t = p.grad.detach().double().cpu(), onamed[n].grad.double(), g64[n]
         e = ((g - r).abs().max() / r.abs().max().clamp_min(1e-300)).item()
         l2 = ((g - r).norm() / r.norm().clamp_min(1e-300)).item()
         num += float(((g - r) ** 2).sum())
         den += float((r ** 2).sum())
+        if not (e < 2e-2 and l2 < 1e-2):
+            capped.append((n, f"max {e:.2e} L2 {l2:.2e}"))
         if e < 1e-3 and l2 < 1e-3:
             continue
         # attribution: distance to the float64 gradient, max-normalised and whole-tensor L2, HIP vs the fp32 CPU oracle
@@ -103,7 +106,8 @@ def test_135x240_training_step_fp32_every_gradient(oracle_135, oracle_135_f64):
     for row in listed:
         print("    ", *row)
     assert not failed, failed
-    assert len(listed) <= 12, listed          # (a handful of ill-conditioned tensors, not a systematic offset)
+    assert not capped, capped                 # the attribution excuses an ill-conditioned tensor, not an arbitrary error
+    assert len(listed) <= 3, listed           # (the recorded run lists one: a new outlier is a finding, not noise)
     assert glob < 1e-4
     sd = net.state_dict()
     for n in sr_oracle.buffer_shapes(64):
