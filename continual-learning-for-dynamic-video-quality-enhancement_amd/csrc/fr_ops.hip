@@ -217,6 +217,8 @@ __global__ __launch_bounds__(256) void bn2_apply_kernel(const float* __restrict_
     }
 }
 
+// OPT (nvq_bn2_backward_ex): dgamma and / or dbeta may be NULL (a frozen BatchNorm affine), their stores are dropped
+template <bool OPT>
 __global__ __launch_bounds__(256) void bn2_bwd_final_kernel(const float* __restrict__ part, int nblk, int C,
                                                             float* __restrict__ sums, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta) {
@@ -227,8 +229,8 @@ __global__ __launch_bounds__(256) void bn2_bwd_final_kernel(const float* __restr
     if (threadIdx.x >= 16 || c >= C) return;
     sums[c] = (float)s;
     sums[C + c] = (float)ss;
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)ss;
+    if (!OPT || dbeta) dbeta[c] = (float)s;
+    if (!OPT || dgamma) dgamma[c] = (float)ss;
 }
 
 // dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat))   (training)   |   gamma * invstd * g   (eval)
@@ -274,6 +276,59 @@ __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restr
             if (!g && relu && !(xh * ga[k] + be[k] > 0.f)) gg = 0.f;
             o[k] = training ? ga[k] * is[k] * (gg - k1[k] - xh * k2[k]) : ga[k] * is[k] * gg;   // padding channels: ga = is = 0
         }
+        stx4(dx, p * dx_ld + c, bf, make_float4(o[0], o[1], o[2], o[3]));
+    }
+}
+
+// Eval-mode backward without affine gradients (nvq_bn2_backward_ex, NVQ_NO_WGRAD, training == 0) in one element-wise pass:
+// dx = gamma * invstd * g with g = dy masked by the ReLU of bn(x) (+ res); dres = g when res != NULL.  No sums, no
+// workspace.  Every expression, and its order, is the one of bn2_partial_kernel (mask, dres) and bn2_bwd_apply_kernel (dx),
+// so that dx and dres are bit-identical to the three-pass form's.  Same thread mapping as bn2_bwd_apply_kernel.
+template <bool BF>
+__global__ __launch_bounds__(256) void bn2_bwd_eval_kernel(const float* __restrict__ x, int x_ld, int C, long npix,
+                                                           const float* __restrict__ dy, int dy_ld,
+                                                           const float* __restrict__ res, int res_ld,
+                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           int relu, float* __restrict__ dx, int dx_ld,
+                                                           float* __restrict__ dres, int dres_ld) {
+    constexpr int bf = BF;
+    const int G4 = dx_ld >> 2;
+    const int rows = 256 / G4;
+    const int gi = threadIdx.x % G4, row = threadIdx.x / G4;
+    if (row >= rows) return;
+    const int c = 4 * gi;
+    const long per = (npix + gridDim.x - 1) / gridDim.x;
+    const long p0 = (long)blockIdx.x * per, p1 = (p0 + per < npix) ? p0 + per : npix;
+    if (c >= C) {
+        for (long p = p0 + row; p < p1; p += rows) stx4(dx, p * dx_ld + c, bf, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
+    const float4 m4 = cpar(mean, c, C), is4 = cpar(invstd, c, C), ga4 = cpar(gamma, c, C), be4 = cpar(beta, c, C);
+    const float mm[4] = {m4.x, m4.y, m4.z, m4.w}, is[4] = {is4.x, is4.y, is4.z, is4.w}, ga[4] = {ga4.x, ga4.y, ga4.z, ga4.w};
+    const float be[4] = {be4.x, be4.y, be4.z, be4.w};
+    for (long p = p0 + row; p < p1; p += rows) {
+        const float4 v = ldx4(x, p * x_ld + c, bf);
+        const float4 t = ldx4(dy, p * dy_ld + c, bf);
+        const float xv[4] = {v.x, v.y, v.z, v.w};
+        float gg[4] = {t.x, t.y, t.z, t.w};
+        float rv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (relu && res) {
+            const float4 r = ldx4(res, p * res_ld + c, bf);
+            rv[0] = r.x; rv[1] = r.y; rv[2] = r.z; rv[3] = r.w;
+        }
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float xh = (xv[k] - mm[k]) * is[k];
+            if (relu) {
+                float y = xh * ga[k] + be[k];
+                if (res) y += rv[k];
+                if (!(y > 0.f)) gg[k] = 0.f;
+            }
+            o[k] = ga[k] * is[k] * gg[k];            // padding channels: ga = is = 0
+        }
+        if (res) stx4(dres, p * dres_ld + c, bf, make_float4(gg[0], gg[1], gg[2], gg[3]));
         stx4(dx, p * dx_ld + c, bf, make_float4(o[0], o[1], o[2], o[3]));
     }
 }
@@ -905,17 +960,28 @@ int nvq_bn2_apply(const float* x, int x_ld, int C, long npix, const float* mean,
     return check_launch("bn2_apply");
 }
 
-int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
-                     const float* invstd, const float* gamma, const float* beta, const float* res, int res_ld, int relu,
-                     int training, float* dx, int dx_ld, float* dres, int dres_ld, float* dgamma, float* dbeta,
-                     float* workspace, size_t workspace_bytes, int bf16, void* stream) {
+int nvq_bn2_backward_ex(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, const float* res, int res_ld, int relu,
+                        int training, float* dx, int dx_ld, float* dres, int dres_ld, float* dgamma, float* dbeta,
+                        float* workspace, size_t workspace_bytes, int bf16, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "bn2_backward_ex: flags %d", flags);
+    if (flags & NVQ_NO_WGRAD) dgamma = dbeta = nullptr;
     const int C4 = (C + 3) & ~3;
     NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && C4 <= dx_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && dx_ld % 4 == 0 &&
                     aligned16(dx) && aligned16(x) && aligned16(dy), "bn2_backward: C %d", C);
     NVQ_REQUIRE(!res || (dres && C4 <= dres_ld && dres_ld % 4 == 0 && C4 <= res_ld && res_ld % 4 == 0 && aligned16(res) && aligned16(dres)),
                 "bn2_backward: a residual input needs its gradient buffer");
-    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C) + 2 * (size_t)C * sizeof(float), "bn2_backward: workspace");
     hipStream_t s = (hipStream_t)stream;
+    if (!training && !dgamma && !dbeta) {
+        // eval mode without affine gradients: dx (and dres) need no reduction - one element-wise pass, no workspace
+        NVQ_REQUIRE(dx_ld <= 1024, "bn2_backward: ld %d", dx_ld);
+#define NVQ_B2E(B_) hipLaunchKernelGGL(bn2_bwd_eval_kernel<B_>, dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, npix, dy, \
+                                       dy_ld, res, res_ld, mean, invstd, gamma, beta, relu, dx, dx_ld, dres, dres_ld)
+        if (bf16) NVQ_B2E(true); else NVQ_B2E(false);
+#undef NVQ_B2E
+        return check_launch("bn2_bwd_eval");
+    }
+    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C) + 2 * (size_t)C * sizeof(float), "bn2_backward: workspace");
     const int nb = bn2_nblk(npix);
     float* sums = workspace + (size_t)BN2_MAXBLK * 2 * C;
 #define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<1, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, dy, dy_ld, res, res_ld, \
@@ -924,7 +990,10 @@ int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C
 #undef NVQ_B2P
     int rc = check_launch("bn2_bwd_partial");
     if (rc) return rc;
-    hipLaunchKernelGGL(bn2_bwd_final_kernel, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma, dbeta);
+    if (dgamma && dbeta)
+        hipLaunchKernelGGL(bn2_bwd_final_kernel<false>, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma, dbeta);
+    else
+        hipLaunchKernelGGL(bn2_bwd_final_kernel<true>, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma, dbeta);
     rc = check_launch("bn2_bwd_final");
     if (rc) return rc;
     NVQ_REQUIRE(dx_ld <= 1024, "bn2_backward: ld %d", dx_ld);
@@ -933,6 +1002,15 @@ int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C
     if (bf16) NVQ_B2B(true); else NVQ_B2B(false);
 #undef NVQ_B2B
     return check_launch("bn2_bwd_apply");
+}
+
+int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
+                     const float* invstd, const float* gamma, const float* beta, const float* res, int res_ld, int relu,
+                     int training, float* dx, int dx_ld, float* dres, int dres_ld, float* dgamma, float* dbeta,
+                     float* workspace, size_t workspace_bytes, int bf16, void* stream) {
+    NVQ_REQUIRE(dgamma && dbeta, "bn2_backward: dgamma / dbeta (nvq_bn2_backward_ex takes NULL)");
+    return nvq_bn2_backward_ex(dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, res, res_ld, relu, training, dx, dx_ld,
+                               dres, dres_ld, dgamma, dbeta, workspace, workspace_bytes, bf16, 0, stream);
 }
 
 int nvq_maxpool_forward(const float* x, int ld, int N, int H, int W, int k, int s, int pad, float* out, uint8_t* idx,

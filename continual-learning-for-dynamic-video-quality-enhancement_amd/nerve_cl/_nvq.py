@@ -147,6 +147,7 @@ SIGNATURES = {
     "nvq_bn2_eval_stats": (ci, [vp, vp, ci, cf, vp, vp, vp]),
     "nvq_bn2_apply": (ci, [vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp]),
     "nvq_bn2_backward": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp, sz, ci, vp]),
+    "nvq_bn2_backward_ex": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp, sz, ci, ci, vp]),
     "nvq_maxpool_forward": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp]),
     "nvq_maxpool_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp]),
     "nvq_subsample2": (ci, [vp, ci, ci, ci, ci, vp, ci, ci, vp]),

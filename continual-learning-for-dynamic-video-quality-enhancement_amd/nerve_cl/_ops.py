@@ -10,6 +10,8 @@ Convention: activations are ``[N, H, W, ld]`` (NHWC), fp32 with ``ld = pad4(C)``
 FrameRecoveryNet's high-resolution stages in the bf16 mode - bf16 with ``ld = pad8(C)``; channels ``[C, ld)`` are zero.
 An op's output has its input's storage type unless it takes an ``out_dtype``; the attention / fusion ops are fp32 only.
 There is no CPU path: every function raises on non-HIP tensors.
+A weight (or BatchNorm affine) that does not need a gradient (``ctx.needs_input_grad``: a frozen parameter) gets none: its
+weight-gradient launches are skipped, and the input gradient is formed by the same launches as when it trains.
 """
 from __future__ import annotations
 
@@ -159,7 +161,10 @@ class Conv(torch.autograd.Function):
             K.axpy_slice(Sl(g), Sl(dy), 1.0, accumulate=False, mask=Sl(y))
         else:
             g = dy
-        dw, db = _wgrad(x, Ci, g, Co, weight.shape, ctx.has_bias, k, ctx.math)
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:           # one launch forms both: as before when either trains
+            dw, db = _wgrad(x, Ci, g, Co, weight.shape, ctx.has_bias, k, ctx.math)
+            dw, db = (dw if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None)
         dx = None
         if ctx.sink is not None:
             drefs = ctx.sink.drefs
@@ -186,8 +191,10 @@ class DwConv(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy = dy.contiguous()
-        dw = torch.empty_like(weight)
-        K.dwconv_wgrad(x, dy, dw, _ws(x))
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight)
+            K.dwconv_wgrad(x, dy, dw, _ws(x))
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -229,15 +236,17 @@ class TemporalConv(torch.autograd.Function):
         Co, Ci = taps.shape[1:3]
         dy = dy.contiguous()
         assert dy.dtype == torch.float32 or Co % 8 == 0
-        xs, gs = Sl(x), Sl(dy, Co)
-        dtaps = _new(x, 3, Co, Ci, 1, 1, zero=(T == 1))
-        ws = _ws(x)
-        K.conv_wgrad(xs, Ci, gs, dtaps[1], None, ws, 1, math=math)
-        if T > 1:
-            K.conv_wgrad(xs.images(0, NB - B), Ci, gs.images(B, NB), dtaps[0], None, ws, 1, math=math)
-            K.conv_wgrad(xs.images(B, NB), Ci, gs.images(0, NB - B), dtaps[2], None, ws, 1, math=math)
-        dw = _new(x, *ctx.wshape)
-        check(lib().nvq_tconv_relayout(ptr(dtaps), ptr(dw), Co, Ci, 0, stream()), "nvq_tconv_relayout")
+        dw = None
+        if ctx.needs_input_grad[1]:
+            xs, gs = Sl(x), Sl(dy, Co)
+            dtaps = _new(x, 3, Co, Ci, 1, 1, zero=(T == 1))
+            ws = _ws(x)
+            K.conv_wgrad(xs, Ci, gs, dtaps[1], None, ws, 1, math=math)
+            if T > 1:
+                K.conv_wgrad(xs.images(0, NB - B), Ci, gs.images(B, NB), dtaps[0], None, ws, 1, math=math)
+                K.conv_wgrad(xs.images(B, NB), Ci, gs.images(0, NB - B), dtaps[2], None, ws, 1, math=math)
+            dw = _new(x, *ctx.wshape)
+            check(lib().nvq_tconv_relayout(ptr(dtaps), ptr(dw), Co, Ci, 0, stream()), "nvq_tconv_relayout")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -284,11 +293,14 @@ class SpatialConvTC(torch.autograd.Function):
         Cpi, Cpo = ld // T, dy.shape[-1] // T
         Co, Ci = weight.shape[:2]
         dy = dy.contiguous()
-        Cg = Cpo if dy.dtype == torch.bfloat16 else Co
-        full = _new(x, Cg, *weight.shape[1:])
-        ws = _ws(x)
-        for t in range(T):
-            K.conv_wgrad(Sl(x, Cpi, t * Cpi), Ci, Sl(dy, Cg, t * Cpo), full, None, ws, 3, accumulate=t > 0, math=math)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            Cg = Cpo if dy.dtype == torch.bfloat16 else Co
+            full = _new(x, Cg, *weight.shape[1:])
+            ws = _ws(x)
+            for t in range(T):
+                K.conv_wgrad(Sl(x, Cpi, t * Cpi), Ci, Sl(dy, Cg, t * Cpo), full, None, ws, 3, accumulate=t > 0, math=math)
+            dw = full[:Co]
         dx = None
         if ctx.sink is not None:
             # frame t of the gradient sits at channel offset t * Cpo of every image
@@ -298,7 +310,7 @@ class SpatialConvTC(torch.autograd.Function):
             wt = K.conv_pack(weight, True, Cpo, Ci, math=math)
             for t in range(T):
                 K.conv_forward(Sl(dy, Cpo, t * Cpo), wt, None, Sl(dx, Ci, t * Cpi), 3, cout_store=Cpi, math=math)
-        return dx, full[:Co], None, None, None, None
+        return dx, dw, None, None, None, None
 
 
 def _tconv_cat(weight, Cp: int, k0: int, nk: int, transpose: bool) -> torch.Tensor:
@@ -341,22 +353,24 @@ class TemporalConvTC(torch.autograd.Function):
         Cpi, Cpo = ld // T, dy.shape[-1] // T
         Co, Ci = weight.shape[:2]
         dy = dy.contiguous()
-        Cg = Cpo if dy.dtype == torch.bfloat16 else Co
-        ws = _ws(x)
-        # weight gradient: one launch per frame into the block of its form; the inner frames accumulate into "mid"
-        g = {"first": _new(x, Cg, 2 * Cpi, 1, 1), "last": _new(x, Cg, 2 * Cpi, 1, 1),
-             "mid": _new(x, Cg, 3 * Cpi, 1, 1) if T > 2 else None}
-        seen = set()
-        for t in range(T):
-            lo, hi = max(t - 1, 0), min(t + 1, T - 1)
-            form = "first" if t == 0 else "last" if t == T - 1 else "mid"
-            nk = hi - lo + 1
-            K.conv_wgrad(Sl(x, nk * Cpi, lo * Cpi), nk * Cpi, Sl(dy, Cg, t * Cpo), g[form], None, ws, 1,
-                         accumulate=form in seen, math=math)
-            seen.add(form)
-        dw = _new(x, *weight.shape)
-        check(lib().nvq_tconv_grad_combine(ptr(g["first"]), ptr(g["mid"]), ptr(g["last"]), Co, Ci, Cpi, ptr(dw), stream()),
-              "nvq_tconv_grad_combine")
+        dw = None
+        if ctx.needs_input_grad[1]:
+            Cg = Cpo if dy.dtype == torch.bfloat16 else Co
+            ws = _ws(x)
+            # weight gradient: one launch per frame into the block of its form; the inner frames accumulate into "mid"
+            g = {"first": _new(x, Cg, 2 * Cpi, 1, 1), "last": _new(x, Cg, 2 * Cpi, 1, 1),
+                 "mid": _new(x, Cg, 3 * Cpi, 1, 1) if T > 2 else None}
+            seen = set()
+            for t in range(T):
+                lo, hi = max(t - 1, 0), min(t + 1, T - 1)
+                form = "first" if t == 0 else "last" if t == T - 1 else "mid"
+                nk = hi - lo + 1
+                K.conv_wgrad(Sl(x, nk * Cpi, lo * Cpi), nk * Cpi, Sl(dy, Cg, t * Cpo), g[form], None, ws, 1,
+                             accumulate=form in seen, math=math)
+                seen.add(form)
+            dw = _new(x, *weight.shape)
+            check(lib().nvq_tconv_grad_combine(ptr(g["first"]), ptr(g["mid"]), ptr(g["last"]), Co, Ci, Cpi, ptr(dw), stream()),
+                  "nvq_tconv_grad_combine")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -433,10 +447,12 @@ class ConvT(torch.autograd.Function):
         dy = dy.contiguous()
         du = _new(x, N, H, W, 4 * Co, dtype=dy.dtype)
         check(lib().nvq_depth_space2(ptr(dy), ptr(du), N, H, W, Co, 1, _bf(dy), stream()), "nvq_depth_space2")
-        dw3 = torch.empty_like(w3)
-        K.conv_wgrad(Sl(x), Ci, Sl(du), dw3, None, _ws(x), 3, math=math)
-        dw = _new(x, *ctx.wshape)
-        check(lib().nvq_convt_unpack_grad(ptr(dw3), Ci, Co, ptr(dw), stream()), "nvq_convt_unpack_grad")
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw3 = torch.empty_like(w3)
+            K.conv_wgrad(Sl(x), Ci, Sl(du), dw3, None, _ws(x), 3, math=math)
+            dw = _new(x, *ctx.wshape)
+            check(lib().nvq_convt_unpack_grad(ptr(dw3), Ci, Co, ptr(dw), stream()), "nvq_convt_unpack_grad")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -468,10 +484,12 @@ class Stem7(torch.autograd.Function):
         (x4,) = ctx.saved_tensors
         N, H, W, _ = x4.shape
         dy = dy.contiguous()
-        dw = _new(x4, *ctx.wshape)
-        ws = _ws(x4)
-        check(lib().nvq_stem7_wgrad(ptr(x4), ptr(dy), dy.shape[-1], N, H, W, ctx.wshape[0], ptr(dw), ptr(ws), ws.numel() * 4,
-                                    _bf(dy), stream()), "nvq_stem7_wgrad")
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = _new(x4, *ctx.wshape)
+            ws = _ws(x4)
+            check(lib().nvq_stem7_wgrad(ptr(x4), ptr(dy), dy.shape[-1], N, H, W, ctx.wshape[0], ptr(dw), ptr(ws), ws.numel() * 4,
+                                        _bf(dy), stream()), "nvq_stem7_wgrad")
         if ctx.sink is not None:
             K.stem7_dgrad(dy, ctx.weight, ctx.sink.dframe, ctx.sink.dmask, H, W, accumulate=True)
         return None, dw, None, None
@@ -512,12 +530,18 @@ class BatchNorm(torch.autograd.Function):
         assert dy.dtype == x.dtype
         dx = torch.empty_like(x)
         dres = torch.empty_like(res) if res is not None else None
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dgamma = torch.empty_like(gamma) if need_g else None
+        dbeta = torch.empty_like(beta) if need_b else None
         ws = _ws(x)
-        check(lib().nvq_bn2_backward(ptr(dy), dy.shape[-1], ptr(x), ld, C, N * H * W, ptr(mean), ptr(invstd), ptr(gamma),
-                                     ptr(beta), ptr(res), res.shape[-1] if res is not None else 0, int(ctx.relu),
-                                     int(ctx.training), ptr(dx), ld, ptr(dres), dres.shape[-1] if dres is not None else 0,
-                                     ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel() * 4, _bf(x), stream()), "nvq_bn2_backward")
+        args = (ptr(dy), dy.shape[-1], ptr(x), ld, C, N * H * W, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(res),
+                res.shape[-1] if res is not None else 0, int(ctx.relu), int(ctx.training), ptr(dx), ld, ptr(dres),
+                dres.shape[-1] if dres is not None else 0, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel() * 4, _bf(x))
+        if need_g and need_b:
+            check(lib().nvq_bn2_backward(*args, stream()), "nvq_bn2_backward")
+        else:
+            # a frozen affine: its store is dropped; with both frozen in eval mode dx (and dres) take one pass
+            check(lib().nvq_bn2_backward_ex(*args, 0 if need_g or need_b else K.NO_WGRAD, stream()), "nvq_bn2_backward_ex")
         return dx, dgamma, dbeta, dres, None, None, None, None
 
 
@@ -687,15 +711,18 @@ class CBAMFn(torch.autograd.Function):
         ws = _ws(x)
         dpre = _new(x, N, H, W)
         K.cbam_bwd_spatial_pre(Sl(dy), x, ca, sa, dpre)
-        dsm, dw7 = _new(x, N, H, W, 2), torch.empty_like(w7)
+        # the weight gradients are side products of the input gradient: formed (all three, as before) when any of them trains
+        wg = any(ctx.needs_input_grad[1:4])
+        dsm, dw7 = _new(x, N, H, W, 2), (torch.empty_like(w7) if wg else None)
         K.cbam_bwd_spatial_conv(dpre, sm, w7, dsm, dw7, ws)
         nblk = K.tsum_blocks(H, W)
         dx, dca_partial = torch.empty_like(x), _new(x, N, nblk, C)
         K.cbam_bwd_scale(Sl(dy), x, ca, sa, dsm, amax, dx, dca_partial)
-        dw1, dw2, dgap_pix = torch.empty_like(w1), torch.empty_like(w2), _new(x, N, C)
+        dw1, dw2, dgap_pix = (torch.empty_like(w1) if wg else None), (torch.empty_like(w2) if wg else None), _new(x, N, C)
         K.cbam_bwd_channel(dca_partial, nblk, C, R, N, H * W, w1, w2, gap, hid, ca, dw1, dw2, dgap_pix)
         check(lib().nvq_add_image_channel(ptr(dx), C, C, N, H, W, ptr(dgap_pix), stream()), "nvq_add_image_channel")
-        return dx, dw1, dw2, dw7
+        need = ctx.needs_input_grad
+        return dx, (dw1 if need[1] else None), (dw2 if need[2] else None), (dw7 if need[3] else None)
 
 
 class FusionMix(torch.autograd.Function):

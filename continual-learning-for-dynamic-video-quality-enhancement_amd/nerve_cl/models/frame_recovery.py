@@ -136,11 +136,16 @@ class _FRFunction(torch.autograd.Function):
     """One autograd node for the whole network: runs the layer graph (an inner autograd graph over the libnvq ops), keeps
     it, and on backward collects its parameter gradients into the flat bucket.  The image inputs' gradients (frame, refs,
     mask) are written by the ops at the network's edge into an _ops.InputGradSink: they stay out of the bucket (local to
-    the rank)."""
+    the rank).
+
+    Frozen parameters (requires_grad False) enter the layer graph as plain tensors: autograd prunes every op backward with
+    nothing upstream to train, and the ops skip a frozen weight's gradient launches.  They get None from backward; their
+    slots of the bucket are zeros."""
 
     @staticmethod
     def forward(ctx, net: "FrameRecoveryNet", frame, refs, mask, *params):
-        need_params = any(ctx.needs_input_grad[4:])
+        need = ctx.needs_input_grad[4:]
+        need_params = any(need)
         want = ctx.needs_input_grad[1:4]                 # frame, refs, mask
         ctx.net = net
         # the layer graph sees the inputs as data: their gradients come out of the sink, not out of the inner graph
@@ -153,12 +158,13 @@ class _FRFunction(torch.autograd.Function):
         if any(want):
             sink = _ops.InputGradSink(*(torch.empty_like(t) if w else None for t, w in zip((frame, refs, mask), want)))
         # Function.forward runs with autograd switched off: switch it back on for the layer graph, whose leaves are the
-        # real parameters (torch.autograd.grad in backward reads their gradients without touching .grad).  With every
-        # parameter frozen the leaves are the network's NHWC input images instead, so that the graph is still recorded.
+        # trained parameters (torch.autograd.grad in backward reads their gradients without touching .grad).  With a sink the
+        # network's NHWC input images are leaves too, so that the ops at the edge are reached even behind frozen layers.
         with torch.enable_grad():
-            leaves = list(params) if need_params else []
-            out = net._graph(frame, refs, mask, sink, None if need_params else leaves)
-        ctx.inner = (out, leaves, sink, need_params)
+            leaves = [p for p, n in zip(params, need) if n]
+            ntrained = len(leaves)
+            out = net._graph(frame, refs, mask, sink, leaves if sink is not None else None)
+        ctx.inner = (out, leaves, ntrained, sink, need)
         if need_params:
             net._mark_awaiting(ctx)
         return out.detach()
@@ -168,27 +174,39 @@ class _FRFunction(torch.autograd.Function):
         net = ctx.net
         if ctx.inner is None:
             raise RuntimeError("FrameRecoveryNet backward called twice (or without saved state)")
-        out, leaves, sink, need_params = ctx.inner
+        out, leaves, ntrained, sink, need = ctx.inner
         ctx.inner = None
         dinputs = (sink.dframe, sink.drefs, sink.dmask) if sink is not None else (None, None, None)
         with _nvq.device_guard(dout.device):
-            grads = torch.autograd.grad(out, leaves, dout.contiguous(), allow_unused=True)
-            if not need_params:
+            grads = torch.autograd.grad(out, leaves, dout.contiguous(), allow_unused=True)[:ntrained]
+            if not ntrained:
                 # frozen parameters: the input gradients alone, no bucket (nothing to all-reduce or finish)
                 return (None,) + dinputs + (None,) * len(net._param_names)
+            trained = iter(grads)
             lay, total = net._bucket_layout()
+            zero = None
+            if not all(need):
+                # the frozen slots' zeros: views of one buffer (one fill launch instead of one per frozen tensor)
+                zero = torch.zeros(max([4] + [k for (_, k), n in zip(lay.values(), need) if not n]), dtype=torch.float32,
+                                   device=dout.device)
+
+            def zeros(m):
+                if zero is not None and m <= zero.numel():
+                    return zero[:m]
+                return torch.zeros(m, dtype=torch.float32, device=dout.device)
             pieces, off = [], 0
-            for (name, (o, k)), g, leaf in zip(lay.items(), grads, leaves):
+            for (name, (o, k)), n in zip(lay.items(), need):
+                g = next(trained) if n else None
                 if o > off:
-                    pieces.append(torch.zeros(o - off, dtype=torch.float32, device=dout.device))
-                pieces.append(g.reshape(-1) if g is not None else torch.zeros(k, dtype=torch.float32, device=dout.device))
+                    pieces.append(zeros(o - off))
+                pieces.append(g.reshape(-1) if g is not None else zeros(k))
                 off = o + k
             if total > off:
-                pieces.append(torch.zeros(total - off, dtype=torch.float32, device=dout.device))
+                pieces.append(zeros(total - off))
             flat = torch.cat(pieces)
             net._finish_bucket(flat)
         views = net._bucket_views(flat)
-        return (None,) + dinputs + tuple(views[n] for n in net._param_names)
+        return (None,) + dinputs + tuple(views[n] if w else None for n, w in zip(net._param_names, need))
 
 
 class FrameRecoveryNet(BucketedNet):
@@ -224,8 +242,9 @@ class FrameRecoveryNet(BucketedNet):
     # ------------------------------------------------------------------ the layer graph (NHWC, libnvq ops)
     def _graph(self, frame: torch.Tensor, refs: torch.Tensor, mask: torch.Tensor,
                sink: "Optional[_ops.InputGradSink]" = None, input_leaves: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
-        """sink: where the backward writes the inputs' gradients; input_leaves (frozen parameters): a list that receives the
-        NHWC input images whose gradient the sink takes, made grad-requiring so that the layer graph is recorded"""
+        """sink: where the backward writes the inputs' gradients; input_leaves (with a sink): a list that receives the NHWC input
+        images whose gradient the sink takes, made grad-requiring so that the ops at the network's edge are recorded and
+        reached whatever is frozen"""
         B, C, H, W = frame.shape
         T = refs.shape[1]
         math = self.math_mode

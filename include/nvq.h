@@ -567,6 +567,16 @@ int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C
                      const float* res, int res_ld, int relu, int training, float* dx, int dx_ld,
                      float* dres, int dres_ld, float* dgamma, float* dbeta, float* workspace,
                      size_t workspace_bytes, int bf16, void* stream);
+/* nvq_bn2_backward with a flags word.  flags == 0: exactly nvq_bn2_backward, except that dgamma and / or dbeta may be NULL
+ * (a frozen BatchNorm affine: that store is dropped; in training mode the reduction still runs, dx needs its sums).
+ * NVQ_NO_WGRAD: neither dgamma nor dbeta is written (both may be NULL).  In eval mode (training == 0) with no affine gradient,
+ * dx and dres take one element-wise pass: no reduction and no workspace (may be NULL).  dx and dres are bit-identical to the
+ * full form's. */
+int nvq_bn2_backward_ex(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix,
+                        const float* mean, const float* invstd, const float* gamma, const float* beta,
+                        const float* res, int res_ld, int relu, int training, float* dx, int dx_ld,
+                        float* dres, int dres_ld, float* dgamma, float* dbeta, float* workspace,
+                        size_t workspace_bytes, int bf16, int flags, void* stream);
 /* nn.MaxPool2d(k, s, pad) (frame_recovery.py:46) and F.max_pool3d(x, (1,2,2)) (:155,158): first maximum in scan order
  * wins (PyTorch's tie rule, matters after ReLU); idx = one byte per element; the backward is a gather (no atomics) */
 int nvq_maxpool_forward(const float* x, int ld, int N, int H, int W, int k, int s, int pad, float* out,
