@@ -13,7 +13,7 @@ block owns one [B,H,W,F+160] buffer, layer i reads channels [0, F+32i) and write
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
@@ -501,13 +501,16 @@ def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, m
 
 
 def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
-             deterministic: bool = False, dframes: Optional[torch.Tensor] = None, plan: Optional[BackwardPlan] = None) -> None:
+             deterministic: bool = False, dframes: Optional[torch.Tensor] = None, plan: Optional[BackwardPlan] = None,
+             dinter: Optional[list] = None) -> None:
     """Write the gradient of every parameter of the plan into G[name] (each exactly once, overwrite).  deterministic: the warp
     gradient without float atomics for any flow (every other kernel of the backward sums in a fixed order already).
     dframes (B,T,Cimg,H,W) fp32: also write the gradient w.r.t. the input frames (overwrite) - two launches behind the
     parameter gradients, which stay exactly what they are without it.
     plan (backward_plan): the gradients to form; every launch it does not need is skipped (frozen layers), and the gradients it
-    forms are bit-identical to the all-trainable backward's.  None: every name in G, and the frames when dframes is given."""
+    forms are bit-identical to the all-trainable backward's.  None: every name in G, and the frames when dframes is given.
+    dinter: upstream gradients of the intermediates() tensors (fp32 NCHW, same order, None where absent), added into the gradient
+    slices where the reference graph has those tensors (nvq_inject_nchw); None or all-None: no launch."""
     if sv.feat0 is None:
         raise RuntimeError("forward(features=...) is an inference path: its result cannot be differentiated")
     g = sv.g
@@ -548,7 +551,9 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     _wgrad(Sl(sv.fused), F, Sl(du, g.U), G, "upsampler.conv.weight", "upsampler.conv.bias", wq, 3, math=math)
     # Frozen layers: the stages below run while something upstream of them, or one of their own parameters, needs a gradient
     # (plan.run); past the last such stage the pass ends.
-    head = _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws)
+    if dinter is not None and all(d is None for d in dinter):
+        dinter = None
+    head = _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinter)
     if small:
         wq.flush()
     G.check()
@@ -564,7 +569,7 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
         K.bicubic_adjoint(dout, sv.passmask, g.s, c, 1.0, dframes, accumulate=True)
 
 
-def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws):
+def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinter):
     """backward() behind the upsampler's weight gradient -> (gradient at the head conv's output, feature gradient) when the
     extractor's backward ran, else None"""
     g = sv.g
@@ -651,6 +656,9 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws):
     if "cbam" not in run:
         return None
     dprev = Sl(dagg)
+    if dinter is not None:
+        # `aggregated` (the CBAM's output, block 0's input): its gradient is complete here
+        K.inject_nchw([(dprev, [dinter[2 * T]])])
 
     _capture("dagg", lambda: dprev.t[..., dprev.coff:dprev.coff + F].float())
     # ---- CBAM
@@ -700,6 +708,10 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws):
         return None
     K.conv_forward(Sl(da1), packs.get(pre + "0.weight", True, F, T * F), None, Sl(daligned), 3,
                    accumulate=True, math=math)
+    if dinter is not None:
+        # `aligned[t]` into slice t; `features[c]` (the same tensor in the reference) into slice c too, which reaches the centre
+        # frame's feature gradient in both forms below (axpy_slice / the correlation gradient's addend)
+        K.inject_nchw([(Sl(daligned, F, t * F), [dinter[T + t]] + ([dinter[c]] if t == c else [])) for t in range(T)])
     if not feat16:
         K.axpy_slice(Sl(dfeat_c), Sl(daligned, F, c * F))
     _capture("dweighted", lambda: dweighted.float())
@@ -751,6 +763,9 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws):
             # a trained flow net in front of a frozen extractor (and frames without a gradient): the pass ends here
             return None
         _capture("dcorr", dcorr)
+        if dinter is not None:
+            # `features[t]`, t != c: the warp gradient has written its slot; the correlation gradients add to it / read it next
+            K.inject_nchw([(Sl(dfeat_oth).images((j - 1) * B, j * B), [dinter[g.slots[j]]]) for j in range(1, T)])
         center = Sl(sv.aligned, F, c * F)
         # The two correlation gradients are the LAST terms of the feature gradient.  bf16 activation mode: they write the finished
         # sum as bf16 (dfeat16) instead of back into the fp32 accumulator - the extractor's backward reads it three times
@@ -952,21 +967,19 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
         K.bicubic_adjoint(dout, sv.passmask, sv.scale, 0, 1.0, dframes, accumulate=True)
 
 
-def nhwc_to_nchw(t: torch.Tensor, c: Optional[int] = None, coff: int = 0) -> torch.Tensor:
-    c = t.shape[-1] - coff if c is None else c
-    return t[..., coff:coff + c].permute(0, 3, 1, 2).contiguous().float()
-
-
-def intermediates(sv: Saved) -> dict:
-    """return_intermediate payload in the reference's NCHW layout (super_resolution.py:384-389)."""
+def intermediates(sv: Saved) -> "list[torch.Tensor]":
+    """return_intermediate payload in the reference's NCHW layout (super_resolution.py:384-389), fp32, in the order
+    features[0 .. T-1], aligned[0 .. T-1], aggregated: one nvq_gather_nchw launch out of the NHWC slices."""
     g = sv.g
-    feats: List[Optional[torch.Tensor]] = [None] * g.T
-    aligned: List[Optional[torch.Tensor]] = [None] * g.T
+    B, T, F, c = g.B, g.T, g.F, g.c
+    dev = sv.aligned.device
+    outs = [_new(dev, B, F, g.H, g.W) for _ in range(2 * T + 1)]
+    jobs = []
     for j, t in enumerate(g.slots):
-        if j == 0:
-            feats[t] = nhwc_to_nchw(sv.aligned, g.F, g.c * g.F)
-        else:
-            feats[t] = nhwc_to_nchw(sv.feat_oth[(j - 1) * g.B:j * g.B])
-        aligned[t] = nhwc_to_nchw(sv.aligned, g.F, t * g.F)
+        src = Sl(sv.aligned, F, c * F) if j == 0 else Sl(sv.feat_oth).images((j - 1) * B, j * B)
+        jobs.append((src, outs[t]))
+    jobs += [(Sl(sv.aligned, F, t * F), outs[T + t]) for t in range(T)]
     x0 = sv.xloc(0)
-    return {"features": feats, "aligned": aligned, "aggregated": nhwc_to_nchw(x0.t, g.F, 0)}
+    jobs.append((Sl(x0.t, F, x0.coff), outs[2 * T]))
+    K.gather_nchw(jobs)
+    return outs

@@ -78,6 +78,18 @@ class WgradReduceJob(C.Structure):
     ]
 
 
+LAYOUT_MAX_JOBS = 2 * MAX_T + 1
+INJECT_MAX_SRC = 4
+
+
+class GatherJob(C.Structure):
+    _fields_ = [("src", vp), ("src_ld", ci), ("src_coff", ci), ("src_bf16", ci), ("dst", vp)]
+
+
+class InjectJob(C.Structure):
+    _fields_ = [("dst", vp), ("dst_ld", ci), ("dst_coff", ci), ("dst_bf16", ci), ("src", vp * INJECT_MAX_SRC)]
+
+
 _IP = C.POINTER(ci)
 
 # name -> (restype, argtypes); must list every symbol declared in include/nvq.h
@@ -142,6 +154,10 @@ SIGNATURES = {
     "nvq_mask_blend_backward_ex": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
     "nvq_nchw_to_nhwc": (ci, [vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp]),
     "nvq_nhwc_to_nchw": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, cl, vp]),
+    "nvq_gather_nchw": (ci, [vp, ci, ci, ci, ci, ci, vp]),
+    "nvq_inject_nchw": (ci, [vp, ci, ci, ci, ci, ci, vp]),
+    "nvq_sizeof_gather_job": (sz, []),
+    "nvq_sizeof_inject_job": (sz, []),
     "nvq_bn2_workspace_bytes": (sz, [ci]),
     "nvq_bn2_stats": (ci, [vp, ci, ci, cl, cf, cf, vp, vp, vp, vp, vp, sz, ci, vp]),
     "nvq_bn2_eval_stats": (ci, [vp, vp, ci, cf, vp, vp, vp]),
@@ -199,6 +215,8 @@ def lib():
         assert l.nvq_sizeof_conv_desc() == C.sizeof(ConvDesc), "nvq_conv_desc layout mismatch"
         assert l.nvq_sizeof_wgrad_desc() == C.sizeof(WgradDesc), "nvq_wgrad_desc layout mismatch"
         assert l.nvq_sizeof_wgrad_reduce_job() == C.sizeof(WgradReduceJob), "nvq_wgrad_reduce_job layout mismatch"
+        assert l.nvq_sizeof_gather_job() == C.sizeof(GatherJob), "nvq_gather_job layout mismatch"
+        assert l.nvq_sizeof_inject_job() == C.sizeof(InjectJob), "nvq_inject_job layout mismatch"
         _lib = l
     return _lib
 
@@ -575,6 +593,43 @@ def wgrad_reduce_batch(jobs: list) -> None:
     arr = (WgradReduceJob * len(jobs))(*[j for j, _ in jobs])
     check(lib().nvq_wgrad_reduce_batch(arr, len(jobs), stream()), "nvq_wgrad_reduce_batch")
     jobs.clear()
+
+
+# ----------------------------------------------------------------------------- return_intermediate tensors
+def _nhwc4(src: Sl):
+    """(N, C, H, W) of an NHWC slice"""
+    n, h, w, _ = src.t.shape
+    return n, src.c, h, w
+
+
+def gather_nchw(jobs: "Sequence[tuple[Sl, torch.Tensor]]") -> None:
+    """dst = src as fp32 NCHW for every (src slice, dst [N,C,H,W] fp32) pair, one launch (nvq_gather_nchw; bit-exact)."""
+    if not jobs:
+        return
+    shape = _nhwc4(jobs[0][0])
+    arr = (GatherJob * len(jobs))()
+    for a, (src, dst) in zip(arr, jobs):
+        assert _nhwc4(src) == shape and not src.plane and dst.dtype == torch.float32 and tuple(dst.shape) == shape
+        a.src, a.src_ld, a.src_coff, a.src_bf16, a.dst = ptr(src.t), src.ld, src.coff, src.bf16, ptr(dst)
+    check(lib().nvq_gather_nchw(C.addressof(arr), len(jobs), *shape, stream()), "nvq_gather_nchw")
+
+
+def inject_nchw(jobs: "Sequence[tuple[Sl, Sequence[Optional[torch.Tensor]]]]") -> None:
+    """dst slice += src_0 + src_1 + ... (fp32 NCHW [N,C,H,W] each, None skipped) in that order, for every (dst slice, sources)
+    pair, one launch (nvq_inject_nchw).  Jobs without a source are dropped; nothing runs when none is left."""
+    jobs = [(d, list(ss)) for d, ss in jobs if any(x is not None for x in ss)]
+    if not jobs:
+        return
+    shape = _nhwc4(jobs[0][0])
+    arr = (InjectJob * len(jobs))()
+    for a, (dst, srcs) in zip(arr, jobs):
+        assert _nhwc4(dst) == shape and not dst.plane and len(srcs) <= INJECT_MAX_SRC
+        a.dst, a.dst_ld, a.dst_coff, a.dst_bf16 = ptr(dst.t), dst.ld, dst.coff, dst.bf16
+        for i, x in enumerate(srcs):
+            if x is not None:
+                assert x.dtype == torch.float32 and tuple(x.shape) == shape
+                a.src[i] = ptr(x)
+    check(lib().nvq_inject_nchw(C.addressof(arr), len(jobs), *shape, stream()), "nvq_inject_nchw")
 
 
 # ----------------------------------------------------------------------------- feature extractor

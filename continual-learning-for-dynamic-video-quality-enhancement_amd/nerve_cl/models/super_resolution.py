@@ -166,7 +166,9 @@ def warp_features(features: torch.Tensor, flow: torch.Tensor, deterministic: Opt
 
 
 class _SRFunction(torch.autograd.Function):
-    """One autograd node for the whole network."""
+    """One autograd node for the whole network.  With want_inter its outputs are out followed by the 2T + 1 intermediates
+    (features[0 .. T-1], aligned[0 .. T-1], aggregated: _engine.intermediates), whose gradients the backward injects where the
+    reference graph has those tensors."""
 
     @staticmethod
     def forward(ctx, net: "SuperResolutionNet", frames: torch.Tensor, want_inter: bool, *params):
@@ -178,6 +180,8 @@ class _SRFunction(torch.autograd.Function):
         ctx.net = net
         ctx.graph = ctx.token = None
         ctx.deterministic = resolve_deterministic(net.deterministic)
+        # an intermediate nobody differentiates reaches backward as None, not as a tensor of zeros
+        ctx.set_materialize_grads(False)
         # frozen parameters (requires_grad False): the backward forms only what the need mask asks for
         ctx.plan = net._backward_plan(ctx.needs_input_grad[3:], ctx.needs_input_grad[1]) if need_grad else None
         if any(ctx.needs_input_grad[3:]):
@@ -189,15 +193,15 @@ class _SRFunction(torch.autograd.Function):
                 out, entry, ctx.token, gen = hit
                 ctx.graph = (entry, gen) if need_grad else None
                 ctx.sv = None
-                net._last_intermediates = None
                 return out
         out, sv = _engine.forward(P, frames, net._F, net._NB, net.scale_factor, net.training, net.math_mode, act)
         ctx.sv = sv if need_grad else None
-        net._last_intermediates = _engine.intermediates(sv) if want_inter else None
+        if want_inter:
+            return (out, *_engine.intermediates(sv))
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *dinter):
         net, sv, plan = ctx.net, ctx.sv, ctx.plan
         names = net._param_names
         dframes = None
@@ -210,9 +214,13 @@ class _SRFunction(torch.autograd.Function):
             # with no trainable parameter (frames' gradient only) no bucket is formed
             flat, views = net._new_grad_bucket() if any(ctx.needs_input_grad[3:]) else (None, {})
             dframes = torch.empty_like(sv.frames) if ctx.needs_input_grad[1] else None
+            g = sv.g
+            if dout is None:        # a loss on the intermediates only: the output stages run on a zero gradient
+                dout = torch.zeros(g.B, g.Cimg, g.H * g.s, g.W * g.s, device=sv.frames.device)
+            dinter = [d.contiguous().float() if d is not None else None for d in dinter] if dinter else None
             with torch.cuda.device(dout.device):
                 _engine.backward(net._tensor_dict(), sv, dout.contiguous().float(), {n: views[n] for n in plan.wgrad},
-                                 deterministic=ctx.deterministic, dframes=dframes, plan=plan)
+                                 deterministic=ctx.deterministic, dframes=dframes, plan=plan, dinter=dinter)
             # A custom Function cannot see retain_graph, and the state of a 540p step is tens of GB that must not outlive
             # the backward (autograd frees its own saved tensors here too), so it is dropped unless the module asks to keep it.
             if not getattr(net, "retain_backward_state", False):
@@ -262,7 +270,6 @@ class SuperResolutionNet(BucketedNet):
         self.math_mode = _nvq.MATH_BF16 if bf16 else _nvq.MATH_F32
         self.bf16_activations = bf16 and os.environ.get("NVQ_BF16_ACTIVATIONS", "1") != "0"
         self._init_bucket()
-        self._last_intermediates = None
         # HIP-graph replay of the step (nerve_cl/_graphs.py): True / False / "auto" = only for small frame sizes.  Off by
         # default: measured on MI355X it frees the host thread but does not shorten the step (see _graphs.py).
         # NVQ_GRAPH=1|0|auto sets the default for unmodified caller scripts.
@@ -308,11 +315,12 @@ class SuperResolutionNet(BucketedNet):
         frames = lr_frames.to(torch.float32).contiguous()
         params = [p for _, p in named]
         with torch.cuda.device(frames.device):      # the kernels launch on the CURRENT device's stream
-            out = _SRFunction.apply(self, frames, bool(return_intermediate), *params)
+            res = _SRFunction.apply(self, frames, bool(return_intermediate), *params)
         if return_intermediate:
-            inter, self._last_intermediates = self._last_intermediates, None
-            return out, inter
-        return out
+            # (the reference's dict; every entry is an output of the autograd node, so a loss on it trains the network)
+            out, inter = res[0], res[1:]
+            return out, {"features": list(inter[:T]), "aligned": list(inter[T:2 * T]), "aggregated": inter[2 * T]}
+        return res
 
     # ------------------------------------------------------------------ inference with cached per-frame features
     def _act_dtype(self):

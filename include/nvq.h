@@ -651,6 +651,29 @@ int nvq_colsum(const float* x, int x_ld, int x_coff, int C, long npix, float alp
                float* out, float* workspace, size_t workspace_bytes, int accumulate,
                void* stream);
 
+/* ------------------------------------------------------------------ return_intermediate tensors (csrc/intermediates.hip)
+ * SuperResolutionNet.forward(return_intermediate=True), super_resolution.py:384-389: the `features`, `aligned` and
+ * `aggregated` tensors live in the engine as NHWC channel slices (fp32 or bf16); at the module boundary they are fp32 NCHW
+ * [N,C,H,W] tensors of the autograd graph.  Every job of one launch has the same N, C, H, W; C a power of two in [16, 256];
+ * a slice needs a 16-B aligned base and ld, coff multiples of 4 (fp32) or 8 (bf16).  Any H, W; njobs <= NVQ_LAYOUT_MAX_JOBS. */
+#define NVQ_LAYOUT_MAX_JOBS (2 * NVQ_MAX_T + 1)
+#define NVQ_INJECT_MAX_SRC 4
+typedef struct {
+    const void* src; int src_ld, src_coff, src_bf16;   /* NHWC slice: fp32, or bf16 when src_bf16 */
+    float* dst;                                        /* fp32 NCHW */
+} nvq_gather_job;
+typedef struct {
+    void* dst; int dst_ld, dst_coff, dst_bf16;         /* NHWC gradient slice: fp32, or bf16 when dst_bf16 */
+    const float* src[NVQ_INJECT_MAX_SRC];              /* fp32 NCHW upstream gradients; NULL entries are skipped */
+} nvq_inject_job;
+/* Forward: dst[n,c,y,x] = (float)src[n,y,x,coff+c] for every job: a widening copy, bit-exact. */
+int nvq_gather_nchw(const nvq_gather_job* jobs, int njobs, int N, int C, int H, int W, void* stream);
+/* Backward: dst[n,y,x,coff+c] = ((dst + src[0]) + src[1]) + ... in fp32 (that order, NULL sources skipped), a bf16 dst
+ * rounded once (RNE).  No atomics: deterministic.  A job's dst must not be one of its sources. */
+int nvq_inject_nchw(const nvq_inject_job* jobs, int njobs, int N, int C, int H, int W, void* stream);
+size_t nvq_sizeof_gather_job(void);
+size_t nvq_sizeof_inject_job(void);
+
 /* ------------------------------------------------------------------ EWC (flat buckets)
  * EWC.penalty, ewc.py:195-232: penalty = lambda/2 * sum F*(theta-theta_star)^2 over a flat
  * bucket of n floats; result written to *out (device scalar). */
