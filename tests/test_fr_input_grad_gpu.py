@@ -164,10 +164,11 @@ def test_fr_input_grad_each_input_alone_and_no_mask():
 # relative L2 / cosine of the HIP-bf16 input gradient against float64.  Measured on MI355X (base 64, T 4, 128x160, train;
 # time-in-channels / time-major): bf16 activations dframe 0.580 / 0.581 (cosine 0.837 / 0.838), drefs 0.559 (0.844),
 # dmask 0.567 (0.846); fp32 activations dframe 0.398 / 0.394 (0.921 / 0.923), drefs 0.429 / 0.432 (0.908 / 0.907),
-# dmask 0.387 / 0.382 (0.926 / 0.928).  That is the bf16 mode's gradient accuracy in training mode at this size, not the new
-# kernels': the weight gradients of the same two layers sit at the same distance (stem 0.585 / 0.392, conv1.spatial
-# 0.559 / 0.433 relative L2; median over all 117 parameter gradients 0.51 / 0.36), and the kernels take their bf16
-# operands at 1e-5 in the kernel tests below.
+# dmask 0.387 / 0.382 (0.926 / 0.928).  That distance is the rounding, not a kernel defect: against the float64 oracle that
+# rounds the same operands and stored tensors to bf16 (oracle/fr_oracle.py prec, tests/test_fr_bf16_emulated_gpu.py) the eval
+# step agrees to 4e-5 whole-gradient L2, and in this training step the same emulation evaluated in float32 on the CPU lies as
+# far (0.35-0.39 on these three) from itself in float64 as the HIP network does: with batch statistics the step is chaotic in
+# the bf16 rounding, so no tighter bound holds in training mode at this size.
 BF16_BOUNDS = {True: (0.70, 0.78), False: (0.52, 0.86)}    # bf16_activations: (max rel L2, min cosine)
 
 
