@@ -14,6 +14,7 @@
 
 namespace nvq {
 
+int bn_stats_sums(const float* part, int nblk, int C, int G, long group_pix, double* stats, hipStream_t s);  // pointwise.hip
 int bn_finalize_launch(const float* part, int nblk, int C, int G, long group_pix, float eps, float momentum,
                        const int* order_host, float* mean, float* invstd, float* rmean, float* rvar, hipStream_t s);  // pointwise.hip
 
@@ -277,11 +278,12 @@ __global__ __launch_bounds__(FT, 2) void dwpw_fwd_kernel(const DwPwArgs a) {
 
 using namespace nvq;
 
-extern "C" int nvq_dwpw_forward(const float* in, int in_ld, const nvq_bn_input* bn, const float* dw_weight,
-                                const float* pw_weight, float* d, int d_ld, float* p, int p_ld, int N, int group_images,
-                                int H, int W, int stats, float eps, float momentum, const int* order_host, float* mean,
-                                float* invstd, float* running_mean, float* running_var, float* workspace,
-                                size_t workspace_bytes, void* stream) {
+// sums_out != NULL (nvq_dwpw_forward_sums): the statistics leave as fp64 sums + pixel counts instead of being finalised
+static int dwpw_forward_impl(const float* in, int in_ld, const nvq_bn_input* bn, const float* dw_weight,
+                             const float* pw_weight, float* d, int d_ld, float* p, int p_ld, int N, int group_images,
+                             int H, int W, int stats, float eps, float momentum, const int* order_host, float* mean,
+                             float* invstd, float* running_mean, float* running_var, double* sums_out, float* workspace,
+                             size_t workspace_bytes, void* stream) {
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "dwpw_forward: groups");
     NVQ_REQUIRE(!bn || bn->group_images == group_images, "dwpw_forward: the input transform has other frame groups");
     NVQ_REQUIRE(in_ld % 8 == 0 && d_ld % 8 == 0 && p_ld % 8 == 0 && in_ld >= FC && d_ld >= FC && p_ld >= FC && aligned16(in) &&
@@ -296,7 +298,7 @@ extern "C" int nvq_dwpw_forward(const float* in, int in_ld, const nvq_bn_input* 
     if (nwg >= 8) nwg &= ~7;                                  // multiple of the XCD count, see xcd_tile()
     float* part = nullptr;
     if (stats) {
-        NVQ_REQUIRE(mean && invstd, "dwpw_forward: statistics wanted but no mean / invstd");
+        NVQ_REQUIRE(sums_out || (mean && invstd), "dwpw_forward: statistics wanted but no mean / invstd");
         if ((size_t)G * nwg * 2 * FC * sizeof(float) > workspace_bytes) { set_error("dwpw_forward: workspace"); return NVQ_EWORKSPACE; }
         part = workspace;
     }
@@ -310,6 +312,24 @@ extern "C" int nvq_dwpw_forward(const float* in, int in_ld, const nvq_bn_input* 
         hipLaunchKernelGGL(dwpw_fwd_kernel<false>, dim3(nwg, G), dim3(FT), 0, s, a);
     int rc = check_launch("dwpw_forward");
     if (rc || !stats) return rc;
+    if (sums_out) return bn_stats_sums(part, nwg, FC, G, (long)group_images * H * W, sums_out, s);
     return bn_finalize_launch(part, nwg, FC, G, (long)group_images * H * W, eps, momentum, order_host, mean, invstd, running_mean,
                               running_var, s);
+}
+
+extern "C" int nvq_dwpw_forward(const float* in, int in_ld, const nvq_bn_input* bn, const float* dw_weight,
+                                const float* pw_weight, float* d, int d_ld, float* p, int p_ld, int N, int group_images,
+                                int H, int W, int stats, float eps, float momentum, const int* order_host, float* mean,
+                                float* invstd, float* running_mean, float* running_var, float* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return dwpw_forward_impl(in, in_ld, bn, dw_weight, pw_weight, d, d_ld, p, p_ld, N, group_images, H, W, stats, eps, momentum,
+                             order_host, mean, invstd, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nvq_dwpw_forward_sums(const float* in, int in_ld, const nvq_bn_input* bn, const float* dw_weight,
+                                     const float* pw_weight, float* d, int d_ld, float* p, int p_ld, int N, int group_images,
+                                     int H, int W, double* stats, float* workspace, size_t workspace_bytes, void* stream) {
+    NVQ_REQUIRE(stats, "dwpw_forward_sums: stats");
+    return dwpw_forward_impl(in, in_ld, bn, dw_weight, pw_weight, d, d_ld, p, p_ld, N, group_images, H, W, 1, 0.f, 0.f, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, stats, workspace, workspace_bytes, stream);
 }

@@ -147,6 +147,22 @@ __device__ __forceinline__ void bn2_reduce16(const float* __restrict__ part, int
     }
 }
 
+// fp64 sums of n pixels -> mean / invstd of channel c, running statistics updated as nn.BatchNorm does (momentum, unbiased
+// var).  Shared by the one-call form and the finish phase of a synchronised BatchNorm.
+__device__ __forceinline__ void bn2_fold(double s, double ss, double n, int c, float eps, float momentum, float* __restrict__ mean,
+                                         float* __restrict__ invstd, float* __restrict__ rmean, float* __restrict__ rvar) {
+    const double m = s / n;
+    double var = ss / n - m * m;
+    if (var < 0.0) var = 0.0;
+    mean[c] = (float)m;
+    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (rmean) {
+        const double unb = n > 1.0 ? var * (n / (n - 1.0)) : var;
+        rmean[c] = (float)((1.0 - momentum) * (double)rmean[c] + momentum * m);
+        rvar[c] = (float)((1.0 - momentum) * (double)rvar[c] + momentum * unb);
+    }
+}
+
 // forward statistics: mean / invstd of the batch, running statistics updated as nn.BatchNorm does (momentum, unbiased var)
 __global__ __launch_bounds__(256) void bn2_stats_final_kernel(const float* __restrict__ part, int nblk, int C, long npix,
                                                               float eps, float momentum, float* __restrict__ mean,
@@ -157,16 +173,29 @@ __global__ __launch_bounds__(256) void bn2_stats_final_kernel(const float* __res
     bn2_reduce16(part, nblk, C, sh, s, ss);
     const int c = blockIdx.x * 16 + threadIdx.x;
     if (threadIdx.x >= 16 || c >= C) return;
-    const double m = s / (double)npix;
-    double var = ss / (double)npix - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-        const double unb = npix > 1 ? var * ((double)npix / (double)(npix - 1)) : var;
-        rmean[c] = (float)((1.0 - momentum) * (double)rmean[c] + momentum * m);
-        rvar[c] = (float)((1.0 - momentum) * (double)rvar[c] + momentum * unb);
-    }
+    bn2_fold(s, ss, (double)npix, c, eps, momentum, mean, invstd, rmean, rvar);
+}
+
+// Reduce phase of a synchronised BatchNorm: stats[2C + 1] = {sum x (C), sum x^2 (C), pixel count} in fp64
+__global__ __launch_bounds__(256) void bn2_sums_kernel(const float* __restrict__ part, int nblk, int C, long npix,
+                                                       double* __restrict__ stats) {
+    __shared__ double sh[512];
+    double s, ss;
+    bn2_reduce16(part, nblk, C, sh, s, ss);
+    const int c = blockIdx.x * 16 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) stats[2 * C] = (double)npix;
+    if (threadIdx.x >= 16 || c >= C) return;
+    stats[c] = s;
+    stats[C + c] = ss;
+}
+
+// Finish phase: the (all-reduced) sums and count -> mean / invstd / running statistics (the arithmetic of bn2_stats_final_kernel)
+__global__ __launch_bounds__(256) void bn2_stats_finish_kernel(const double* __restrict__ stats, int C, float eps, float momentum,
+                                                               float* __restrict__ mean, float* __restrict__ invstd,
+                                                               float* __restrict__ rmean, float* __restrict__ rvar) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    bn2_fold(stats[c], stats[C + c], stats[2 * C], c, eps, momentum, mean, invstd, rmean, rvar);
 }
 
 __global__ __launch_bounds__(256) void bn2_eval_stats_kernel(const float* __restrict__ rmean, const float* __restrict__ rvar,
@@ -217,33 +246,42 @@ __global__ __launch_bounds__(256) void bn2_apply_kernel(const float* __restrict_
     }
 }
 
-// OPT (nvq_bn2_backward_ex): dgamma and / or dbeta may be NULL (a frozen BatchNorm affine), their stores are dropped
-template <bool OPT>
+// OPT (nvq_bn2_backward_ex): dgamma and / or dbeta may be NULL (a frozen BatchNorm affine), their stores are dropped.
+// DS (the reduce phase of a synchronised BatchNorm, nvq_bn2_backward_reduce): the sums leave as fp64.
+template <bool OPT, bool DS = false>
 __global__ __launch_bounds__(256) void bn2_bwd_final_kernel(const float* __restrict__ part, int nblk, int C,
-                                                            float* __restrict__ sums, float* __restrict__ dgamma,
+                                                            void* __restrict__ sums_, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta) {
     __shared__ double sh[512];
     double s, ss;
     bn2_reduce16(part, nblk, C, sh, s, ss);
     const int c = blockIdx.x * 16 + threadIdx.x;
     if (threadIdx.x >= 16 || c >= C) return;
-    sums[c] = (float)s;
-    sums[C + c] = (float)ss;
+    if (DS) {
+        static_cast<double*>(sums_)[c] = s;
+        static_cast<double*>(sums_)[C + c] = ss;
+    } else {
+        static_cast<float*>(sums_)[c] = (float)s;
+        static_cast<float*>(sums_)[C + c] = (float)ss;
+    }
     if (!OPT || dbeta) dbeta[c] = (float)s;
     if (!OPT || dgamma) dgamma[c] = (float)ss;
 }
 
 // dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat))   (training)   |   gamma * invstd * g   (eval)
 // g is read from `g` when given (written by the partial pass), else recomputed from dy and the ReLU of bn(x).
-// Same thread mapping as bn2_apply_kernel.
-template <bool BF>
+// Same thread mapping as bn2_apply_kernel.  DS (the finish phase of a synchronised BatchNorm): the sums are the all-reduced fp64
+// ones (dsums) and the pixel count is read from device memory, both rounded to fp32 where the one-call form rounds them.
+template <bool BF, bool DS = false>
 __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restrict__ x, int x_ld, int C, long npix,
                                                             const float* __restrict__ dy, int dy_ld,
                                                             const float* __restrict__ g, int g_ld,
                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ sums, int relu, int training,
-                                                            float* __restrict__ dx, int dx_ld) {
+                                                            float* __restrict__ dx, int dx_ld,
+                                                            const double* __restrict__ dsums = nullptr,
+                                                            const double* __restrict__ count = nullptr) {
     constexpr int bf = BF;
     const int G4 = dx_ld >> 2;
     const int rows = 256 / G4;
@@ -256,9 +294,19 @@ __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restr
         for (long p = p0 + row; p < p1; p += rows) stx4(dx, p * dx_ld + c, bf, make_float4(0.f, 0.f, 0.f, 0.f));
         return;
     }
-    const float inv_n = 1.f / (float)npix;
+    const float inv_n = DS ? 1.f / (float)count[0] : 1.f / (float)npix;
     const float4 m4 = cpar(mean, c, C), is4 = cpar(invstd, c, C), ga4 = cpar(gamma, c, C), be4 = cpar(beta, c, C);
-    const float4 sa = cpar(sums, c, C), sb = cpar(sums + C, c, C);
+    float4 sa, sb;
+    if (DS) {
+        sa = make_float4((float)dsums[c], c + 1 < C ? (float)dsums[c + 1] : 0.f, c + 2 < C ? (float)dsums[c + 2] : 0.f,
+                         c + 3 < C ? (float)dsums[c + 3] : 0.f);
+        const double* db = dsums + C;
+        sb = make_float4((float)db[c], c + 1 < C ? (float)db[c + 1] : 0.f, c + 2 < C ? (float)db[c + 2] : 0.f,
+                         c + 3 < C ? (float)db[c + 3] : 0.f);
+    } else {
+        sa = cpar(sums, c, C);
+        sb = cpar(sums + C, c, C);
+    }
     const float mm[4] = {m4.x, m4.y, m4.z, m4.w}, is[4] = {is4.x, is4.y, is4.z, is4.w}, ga[4] = {ga4.x, ga4.y, ga4.z, ga4.w};
     const float be[4] = {be4.x, be4.y, be4.z, be4.w};
     const float k1[4] = {sa.x * inv_n, sa.y * inv_n, sa.z * inv_n, sa.w * inv_n};
@@ -1011,6 +1059,76 @@ int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C
     NVQ_REQUIRE(dgamma && dbeta, "bn2_backward: dgamma / dbeta (nvq_bn2_backward_ex takes NULL)");
     return nvq_bn2_backward_ex(dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, res, res_ld, relu, training, dx, dx_ld,
                                dres, dres_ld, dgamma, dbeta, workspace, workspace_bytes, bf16, 0, stream);
+}
+
+// ---- synchronised BatchNorm (nn.SyncBatchNorm): reduce / finish phases of nvq_bn2_stats and nvq_bn2_backward.  With local
+// sums the pairs are bit-identical to the one-call forms.
+int nvq_bn2_stats_reduce(const float* x, int x_ld, int C, long npix, double* stats, float* workspace, size_t workspace_bytes,
+                         int bf16, void* stream) {
+    NVQ_REQUIRE(C > 0 && C <= 1024 && ((C + 3) & ~3) <= x_ld && x_ld % 4 == 0 && aligned16(x) && npix > 0 && stats,
+                "bn2_stats_reduce: C %d ld %d", C, x_ld);
+    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "bn2_stats_reduce: workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bn2_nblk(npix);
+#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<0, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, nullptr, 0, nullptr, 0, \
+                                       nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, workspace)
+    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
+#undef NVQ_B2P
+    int rc = check_launch("bn2_partial");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn2_sums_kernel, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, npix, stats);
+    return check_launch("bn2_sums");
+}
+
+int nvq_bn2_stats_finish(const double* stats, int C, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                         float* running_var, void* stream) {
+    NVQ_REQUIRE(C > 0 && C <= 1024 && stats && mean && invstd, "bn2_stats_finish: C %d", C);
+    hipLaunchKernelGGL(bn2_stats_finish_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, stats, C, eps, momentum,
+                       mean, invstd, running_mean, running_var);
+    return check_launch("bn2_stats_finish");
+}
+
+// training-mode backward, reduce phase: sums[2C] = {sum g, sum g xhat} (fp64), dgamma / dbeta (local; either may be NULL) and,
+// with a residual input, dres = g (the ReLU-masked gradient, which the finish phase reads back)
+int nvq_bn2_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
+                            const float* invstd, const float* gamma, const float* beta, const float* res, int res_ld, int relu,
+                            float* dres, int dres_ld, double* sums, float* dgamma, float* dbeta, float* workspace,
+                            size_t workspace_bytes, int bf16, void* stream) {
+    const int C4 = (C + 3) & ~3;
+    NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && aligned16(x) && aligned16(dy) &&
+                    sums, "bn2_backward_reduce: C %d", C);
+    NVQ_REQUIRE(!res || (dres && C4 <= dres_ld && dres_ld % 4 == 0 && C4 <= res_ld && res_ld % 4 == 0 && aligned16(res) && aligned16(dres)),
+                "bn2_backward_reduce: a residual input needs its gradient buffer");
+    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "bn2_backward_reduce: workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bn2_nblk(npix);
+#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<1, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, dy, dy_ld, res, res_ld, \
+                                       mean, invstd, gamma, beta, relu, dres, dres_ld, workspace)
+    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
+#undef NVQ_B2P
+    int rc = check_launch("bn2_bwd_partial");
+    if (rc) return rc;
+    hipLaunchKernelGGL((bn2_bwd_final_kernel<true, true>), dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma,
+                       dbeta);
+    return check_launch("bn2_bwd_final");
+}
+
+// finish phase: dx from the all-reduced sums and the global pixel count (count: device, e.g. the forward's stats + 2C).  dres:
+// the buffer the reduce phase wrote (NULL without a residual input)
+int nvq_bn2_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
+                            const float* invstd, const float* gamma, const float* beta, const float* dres, int dres_ld, int relu,
+                            const double* sums, const double* count, float* dx, int dx_ld, int bf16, void* stream) {
+    const int C4 = (C + 3) & ~3;
+    NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && C4 <= dx_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && dx_ld % 4 == 0 &&
+                    dx_ld <= 1024 && aligned16(dx) && aligned16(x) && aligned16(dy) && sums && count,
+                "bn2_backward_finish: C %d", C);
+    NVQ_REQUIRE(!dres || (C4 <= dres_ld && dres_ld % 4 == 0 && aligned16(dres)), "bn2_backward_finish: dres");
+    hipStream_t s = (hipStream_t)stream;
+#define NVQ_B2B(B_) hipLaunchKernelGGL((bn2_bwd_apply_kernel<B_, true>), dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, \
+                                       npix, dy, dy_ld, dres, dres_ld, mean, invstd, gamma, beta, nullptr, relu, 1, dx, dx_ld, sums, count)
+    if (bf16) NVQ_B2B(true); else NVQ_B2B(false);
+#undef NVQ_B2B
+    return check_launch("bn2_bwd_apply");
 }
 
 int nvq_maxpool_forward(const float* x, int ld, int N, int H, int W, int k, int s, int pad, float* out, uint8_t* idx,

@@ -863,6 +863,34 @@ __device__ __forceinline__ double block_sum_double(double v, double* scratch) {
     return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
+// sum {x, x^2} of channel c over the partials of group g (fp64, one 256-thread block)
+__device__ __forceinline__ void bn_group_sums(const float* __restrict__ part, int nblk, int C, int g, int c, double* scratch,
+                                              double& s, double& q) {
+    const float* p = part + (size_t)g * nblk * 2 * C;
+    s = 0.0; q = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) {
+        s += (double)p[(size_t)b * 2 * C + c];
+        q += (double)p[(size_t)b * 2 * C + C + c];
+    }
+    s = block_sum_double(s, scratch);
+    q = block_sum_double(q, scratch);
+}
+
+// fp64 sums of n pixels -> mean / invstd, folded into the running statistics rm / rv.  Shared by the one-call form and the
+// finish phase of a synchronised BatchNorm, so that both compute the same bits from the same sums.
+__device__ __forceinline__ void bn_fold(double s, double q, double n, float eps, float momentum, float& rm, float& rv,
+                                        float& mean, float& invstd) {
+    const double m = s / n;
+    double var = q / n - m * m;
+    if (var < 0.0) var = 0.0;
+    const double unb = n > 1.0 ? var * n / (n - 1.0) : var;
+    // the contraction spelled out (the one the compiler chose for the one-call kernel): both kernels round alike
+    rm = __builtin_fmaf(1.f - momentum, rm, momentum * (float)m);
+    rv = __builtin_fmaf(1.f - momentum, rv, momentum * (float)unb);
+    mean = (float)m;
+    invstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
 // one 256-thread block per channel; groups are folded into the running statistics in `order`
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int nblk, int C, int G,
                                                           long group_pix, float eps, float momentum, GroupOrder order,
@@ -873,29 +901,57 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     float rm = rmean ? rmean[c] : 0.f, rv = rvar ? rvar[c] : 0.f;
     for (int gi = 0; gi < G; ++gi) {
         const int g = order.g[gi];
-        const float* p = part + (size_t)g * nblk * 2 * C;
-        double s = 0.0, q = 0.0;
-        for (int b = threadIdx.x; b < nblk; b += 256) {
-            s += (double)p[(size_t)b * 2 * C + c];
-            q += (double)p[(size_t)b * 2 * C + C + c];
-        }
-        s = block_sum_double(s, scratch);
-        q = block_sum_double(q, scratch);
-        const double m = s / (double)group_pix;
-        double var = q / (double)group_pix - m * m;
-        if (var < 0.0) var = 0.0;
-        const double unb = group_pix > 1 ? var * (double)group_pix / (double)(group_pix - 1) : var;
-        rm = (1.f - momentum) * rm + momentum * (float)m;
-        rv = (1.f - momentum) * rv + momentum * (float)unb;
+        double s, q;
+        bn_group_sums(part, nblk, C, g, c, scratch, s, q);
+        float mg, ig;
+        bn_fold(s, q, (double)group_pix, eps, momentum, rm, rv, mg, ig);
         if (threadIdx.x == 0) {
-            mean[g * C + c] = (float)m;
-            invstd[g * C + c] = (float)(1.0 / sqrt(var + (double)eps));
+            mean[g * C + c] = mg;
+            invstd[g * C + c] = ig;
         }
     }
     if (threadIdx.x == 0) {
         if (rmean) rmean[c] = rm;
         if (rvar) rvar[c] = rv;
     }
+}
+
+// Reduce phase of a synchronised BatchNorm: stats[g][2C] = {sum x, sum x^2} (fp64), stats[2CG + g] = the group's pixel count.
+// One buffer, so that one all-reduce carries everything the finish phase needs.
+__global__ __launch_bounds__(256) void bn_sums_kernel(const float* __restrict__ part, int nblk, int C, int G, long group_pix,
+                                                      double* __restrict__ stats) {
+    __shared__ double scratch[4];
+    const int c = blockIdx.x;
+    for (int g = 0; g < G; ++g) {
+        double s, q;
+        bn_group_sums(part, nblk, C, g, c, scratch, s, q);
+        if (threadIdx.x == 0) {
+            stats[(size_t)g * 2 * C + c] = s;
+            stats[(size_t)g * 2 * C + C + c] = q;
+        }
+    }
+    if (c == 0 && threadIdx.x < G) stats[(size_t)2 * C * G + threadIdx.x] = (double)group_pix;
+}
+
+// Finish phase: the (all-reduced) sums and counts -> mean / invstd / running statistics, one thread per channel, the groups
+// folded in `order` (the arithmetic of bn_finalize_kernel)
+__global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __restrict__ stats, int C, int G, float eps,
+                                                              float momentum, GroupOrder order, float* __restrict__ mean,
+                                                              float* __restrict__ invstd, float* __restrict__ rmean,
+                                                              float* __restrict__ rvar) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float rm = rmean ? rmean[c] : 0.f, rv = rvar ? rvar[c] : 0.f;
+    for (int gi = 0; gi < G; ++gi) {
+        const int g = order.g[gi];
+        float mg, ig;
+        bn_fold(stats[(size_t)g * 2 * C + c], stats[(size_t)g * 2 * C + C + c], stats[(size_t)2 * C * G + g], eps, momentum, rm,
+                rv, mg, ig);
+        mean[g * C + c] = mg;
+        invstd[g * C + c] = ig;
+    }
+    if (rmean) rmean[c] = rm;
+    if (rvar) rvar[c] = rv;
 }
 
 __global__ void bn_eval_stats_kernel(const float* __restrict__ rmean, const float* __restrict__ rvar,
@@ -992,10 +1048,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     if ((int)threadIdx.x < C4) st4(prow + C + 4 * c4, r2);
 }
 
-// sums[g][2C] (device), dgamma/dbeta
+// sums[g][2C] (device), dgamma/dbeta.  DS (the reduce phase of a synchronised BatchNorm): the sums leave as fp64 (what the
+// one-call form rounds to fp32 after this point), dgamma / dbeta may be NULL (a frozen affine)
+template <bool DS>
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C, int G,
-                                                              float* __restrict__ sums, float* __restrict__ dgamma,
+                                                              void* __restrict__ sums_, float* __restrict__ dgamma,
                                                               float* __restrict__ dbeta, int accumulate) {
+    float* sums = static_cast<float*>(sums_);
+    double* dsums = static_cast<double*>(sums_);
     __shared__ double scratch[4];
     const int c = blockIdx.x;
     double tg = 0.0, tb = 0.0;
@@ -1009,33 +1069,47 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
         s1 = block_sum_double(s1, scratch);
         s2 = block_sum_double(s2, scratch);
         if (threadIdx.x == 0) {
-            sums[(size_t)g * 2 * C + c] = (float)s1;
-            sums[(size_t)g * 2 * C + C + c] = (float)s2;
+            if (DS) {
+                dsums[(size_t)g * 2 * C + c] = s1;
+                dsums[(size_t)g * 2 * C + C + c] = s2;
+            } else {
+                sums[(size_t)g * 2 * C + c] = (float)s1;
+                sums[(size_t)g * 2 * C + C + c] = (float)s2;
+            }
         }
         tb += s1;
         tg += s2;
     }
     if (threadIdx.x == 0) {
-        dgamma[c] = accumulate ? dgamma[c] + (float)tg : (float)tg;
-        dbeta[c] = accumulate ? dbeta[c] + (float)tb : (float)tb;
+        if (!DS || dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)tg : (float)tg;
+        if (!DS || dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)tb : (float)tb;
     }
 }
 
+// DS (the finish phase of a synchronised BatchNorm): the sums are the all-reduced fp64 ones (dsums) and the pixel count is read
+// from device memory (count[g]); they are rounded to fp32 exactly where the one-call form rounds them
+template <bool DS>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float* __restrict__ dy, int dy_ld, const float* __restrict__ x, int x_ld, int C, int c4_shift,
     unsigned group_items, long group_pix, const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums,
-    int training, float* __restrict__ dx, int dx_ld, int dy_bf16, int x_bf16, int dx_bf16) {
+    int training, float* __restrict__ dx, int dx_ld, int dy_bf16, int x_bf16, int dx_bf16,
+    const double* __restrict__ dsums, const double* __restrict__ count) {
     const int g = blockIdx.y;
     const int c4 = threadIdx.x & ((C >> 2) - 1);
     const float4 m = ld4(mean + g * C + 4 * c4), is = ld4(invstd + g * C + 4 * c4);
     const float4 ga = ld4(gamma + 4 * c4), be = ld4(beta + 4 * c4);
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-    if (training) {
+    if (training && DS) {
+        const double* d1 = dsums + (size_t)g * 2 * C + 4 * c4;
+        const double* d2 = d1 + C;
+        s1 = make_float4((float)d1[0], (float)d1[1], (float)d1[2], (float)d1[3]);
+        s2 = make_float4((float)d2[0], (float)d2[1], (float)d2[2], (float)d2[3]);
+    } else if (training) {
         s1 = ld4(sums + (size_t)g * 2 * C + 4 * c4);
         s2 = ld4(sums + (size_t)g * 2 * C + C + 4 * c4);
     }
-    const float inv_n = 1.f / (float)group_pix;
+    const float inv_n = DS ? 1.f / (float)count[g] : 1.f / (float)group_pix;
     const float mv[4] = {m.x, m.y, m.z, m.w}, iv[4] = {is.x, is.y, is.z, is.w};
     const float gv[4] = {ga.x, ga.y, ga.z, ga.w}, bv[4] = {be.x, be.y, be.z, be.w};
     const float a1[4] = {s1.x, s1.y, s1.z, s1.w}, a2[4] = {s2.x, s2.y, s2.z, s2.w};
@@ -1123,7 +1197,7 @@ int bn_backward_sums(const float* dy, int dy_ld, const float* x, int x_ld, int C
     launch_bn_bwd_reduce(dim3(nblk, G), s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd, gamma, beta, dy_bf16, x_bf16, workspace);
     int rc = check_launch("bn_bwd_reduce");
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums, dgamma, dbeta, 0);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums, dgamma, dbeta, 0);
     *sums_out = sums;
     return check_launch("bn_bwd_finalize");
 }
@@ -1131,7 +1205,7 @@ int bn_backward_sums(const float* dy, int dy_ld, const float* x, int x_ld, int C
 // part[g][blk][2C] = {sum g, sum g xhat} -> sums[g][2C], dgamma, dbeta (overwritten).  Shared with dw_bwd.hip, whose kernel can
 // produce these partials itself.
 int bn_bwd_finalize_launch(const float* part, int nblk, int C, int G, float* sums, float* dgamma, float* dbeta, hipStream_t s) {
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, part, nblk, C, G, sums, dgamma, dbeta, 0);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, part, nblk, C, G, sums, dgamma, dbeta, 0);
     return check_launch("bn_bwd_finalize");
 }
 
@@ -1144,6 +1218,13 @@ int bn_finalize_launch(const float* part, int nblk, int C, int G, long group_pix
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, part, nblk, C, G, group_pix, eps, momentum, order, mean,
                        invstd, rmean, rvar);
     return check_launch("bn_finalize");
+}
+
+// part[g][blk][2C] -> stats: fp64 {sum, sum of squares} per (group, channel) + the group pixel counts (the reduce phase of a
+// synchronised BatchNorm).  Shared by nvq_bn_stats_reduce and nvq_dwpw_forward_sums (dwpw_fwd.hip).
+int bn_stats_sums(const float* part, int nblk, int C, int G, long group_pix, double* stats, hipStream_t s) {
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(C), dim3(256), 0, s, part, nblk, C, G, group_pix, stats);
+    return check_launch("bn_sums");
 }
 
 static int blocks_for(long npix, int C) {
@@ -1394,7 +1475,7 @@ int nvq_bn_relu_backward(const float* dy, int dy_ld, const float* x, int x_ld, i
     launch_bn_bwd_reduce(dim3(nblk, G), s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd, gamma, beta, dy_bf16, x_bf16, workspace);
     int rc = check_launch("bn_bwd_reduce");
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums,
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums,
                        dgamma, dbeta, accumulate);
     rc = check_launch("bn_bwd_finalize");
     if (rc) return rc;
@@ -1402,9 +1483,95 @@ int nvq_bn_relu_backward(const float* dy, int dy_ld, const float* x, int x_ld, i
     int shift = 0;
     while ((1 << shift) < C / 4) ++shift;
     const unsigned items = (unsigned)(group_pix * (C / 4));
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, s, dy, dy_ld, x,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, s, dy, dy_ld, x,
                        x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, sums, training, dx, dx_ld, dy_bf16,
-                       x_bf16, dx_bf16);
+                       x_bf16, dx_bf16, nullptr, nullptr);
+    return check_launch("bn_bwd_apply");
+}
+
+// ---------------------------------------------------------------- synchronised BatchNorm: reduce / finish phases
+// The one-call forms above end in a finalize kernel that turns per-block partials into fp64 sums and uses them at once.  For
+// nn.SyncBatchNorm the sums leave to a caller buffer (reduce), are all-reduced over the ranks, and a second call (finish) takes
+// the global sums and reads the pixel count from device memory.  With local sums the pair is bit-identical to the one-call form.
+int nvq_bn_stats_reduce(const float* x, int x_ld, int C, int N, int group_images, int H, int W, double* stats, float* workspace,
+                        size_t workspace_bytes, int x_bf16, void* stream) {
+    NVQ_REQUIRE(pow2_c4(C), "bn_stats_reduce: C %d must be a power of two in [4,256]", C);
+    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_stats_reduce: groups");
+    NVQ_REQUIRE(x_ld % 4 == 0 && aligned16(x) && stats, "bn_stats_reduce: ld");
+    const int G = N / group_images;
+    const long group_pix = (long)group_images * H * W;
+    const int nblk = blocks_for(group_pix, C);
+    if ((size_t)G * nblk * 2 * C * sizeof(float) > workspace_bytes) { set_error("bn_stats_reduce: workspace"); return NVQ_EWORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk, G), dim3(256), 0, s, x, x_ld, C, group_pix, x_bf16, workspace);
+    int rc = check_launch("bn_stats");
+    if (rc) return rc;
+    return bn_stats_sums(workspace, nblk, C, G, group_pix, stats, s);
+}
+
+int nvq_bn_stats_finish(const double* stats, int C, int G, float eps, float momentum, const int* order_host, float* mean,
+                        float* invstd, float* running_mean, float* running_var, void* stream) {
+    NVQ_REQUIRE(C > 0 && G > 0 && G <= NVQ_MAX_T && stats && mean && invstd, "bn_stats_finish: C %d G %d", C, G);
+    GroupOrder order;
+    for (int i = 0; i < NVQ_MAX_T; ++i) order.g[i] = i < G ? (order_host ? order_host[i] : i) : 0;
+    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, stats, C, G, eps,
+                       momentum, order, mean, invstd, running_mean, running_var);
+    return check_launch("bn_stats_finish");
+}
+
+// {sum g, sum g xhat} (fp64) of a BatchNorm + ReLU backward, and dgamma / dbeta (local; either may be NULL)
+static int bn_bwd_reduce_impl(const float* dy, int dy_ld, const float* x, int x_ld, int C, int N, int group_images, int H,
+                              int W, const float* mean, const float* invstd, const float* gamma, const float* beta, double* sums,
+                              float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes, int accumulate, int dy_bf16,
+                              int x_bf16, hipStream_t s) {
+    NVQ_REQUIRE(pow2_c4(C), "bn_backward_reduce: C %d must be a power of two in [4,256]", C);
+    NVQ_REQUIRE(dy_ld % 4 == 0 && x_ld % 4 == 0 && sums, "bn_backward_reduce: ld");
+    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_backward_reduce: groups");
+    const int G = N / group_images;
+    const long group_pix = (long)group_images * H * W;
+    const int nblk = blocks_for(group_pix, C);
+    if ((size_t)G * nblk * 2 * C * sizeof(float) > workspace_bytes) { set_error("bn_backward_reduce: workspace"); return NVQ_EWORKSPACE; }
+    launch_bn_bwd_reduce(dim3(nblk, G), s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd, gamma, beta, dy_bf16, x_bf16, workspace);
+    int rc = check_launch("bn_bwd_reduce");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums, dgamma, dbeta,
+                       accumulate);
+    return check_launch("bn_bwd_finalize");
+}
+
+int nvq_bn_relu_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld, int C, int N, int group_images, int H,
+                                int W, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                double* sums, float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes,
+                                int accumulate, int dy_bf16, int x_bf16, void* stream) {
+    return bn_bwd_reduce_impl(dy, dy_ld, x, x_ld, C, N, group_images, H, W, mean, invstd, gamma, beta, sums, dgamma, dbeta,
+                              workspace, workspace_bytes, accumulate, dy_bf16, x_bf16, (hipStream_t)stream);
+}
+
+// the reduce pass of nvq_pw_bn_backward (its BatchNorm input p is bf16, 64 channels)
+int nvq_pw_bn_backward_reduce(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, int N, int group_images, int H,
+                              int W, const float* mean, const float* invstd, const float* gamma, const float* beta, double* sums,
+                              float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes, void* stream) {
+    return bn_bwd_reduce_impl(dy, dy_ld, p, p_ld, 64, N, group_images, H, W, mean, invstd, gamma, beta, sums, dgamma, dbeta,
+                              workspace, workspace_bytes, 0, dy_bf16, 1, (hipStream_t)stream);
+}
+
+int nvq_bn_relu_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld, int C, int N, int group_images, int H,
+                                int W, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                const double* sums, const double* count, float* dx, int dx_ld, int dy_bf16, int x_bf16,
+                                int dx_bf16, void* stream) {
+    NVQ_REQUIRE(pow2_c4(C), "bn_relu_backward_finish: C %d must be a power of two in [4,256]", C);
+    NVQ_REQUIRE(dy_ld % 4 == 0 && x_ld % 4 == 0 && dx_ld % 4 == 0 && sums && count, "bn_relu_backward_finish: ld");
+    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_relu_backward_finish: groups");
+    const int G = N / group_images;
+    const long group_pix = (long)group_images * H * W;
+    NVQ_REQUIRE(group_pix * (C / 4) < ((long)1 << 32) - 256 * EW_ITEMS, "bn_relu_backward_finish: group of %ld pixels too large",
+                group_pix);
+    int shift = 0;
+    while ((1 << shift) < C / 4) ++shift;
+    const unsigned items = (unsigned)(group_pix * (C / 4));
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, (hipStream_t)stream,
+                       dy, dy_ld, x, x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, nullptr, 1, dx, dx_ld, dy_bf16,
+                       x_bf16, dx_bf16, sums, count);
     return check_launch("bn_bwd_apply");
 }
 

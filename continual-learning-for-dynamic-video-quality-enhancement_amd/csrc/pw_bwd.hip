@@ -42,6 +42,7 @@ struct PwBwdArgs {
     long group_pix;
     int G, training, tiles_per_group, ntiles;
     float inv_n;
+    const double *dsums, *count;   // finish phase of a synchronised BatchNorm: all-reduced fp64 sums, pixel counts (or NULL)
 };
 
 __device__ __forceinline__ float blo(unsigned u) { return __uint_as_float(u << 16); }
@@ -66,8 +67,14 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
         cst[g][1][c] = a.invstd[g * PC + c];
         cst[g][2][c] = a.gamma[c];
         cst[g][3][c] = a.beta[c];
-        cst[g][4][c] = a.training ? a.sums[(size_t)g * 2 * PC + c] * a.inv_n : 0.f;
-        cst[g][5][c] = a.training ? a.sums[(size_t)g * 2 * PC + PC + c] * a.inv_n : 0.f;
+        if (a.count) {                   // the sums and the count rounded to fp32 where the one-call form rounds them
+            const float inv_n = 1.f / (float)a.count[g];
+            cst[g][4][c] = a.training ? (float)a.dsums[(size_t)g * 2 * PC + c] * inv_n : 0.f;
+            cst[g][5][c] = a.training ? (float)a.dsums[(size_t)g * 2 * PC + PC + c] * inv_n : 0.f;
+        } else {
+            cst[g][4][c] = a.training ? a.sums[(size_t)g * 2 * PC + c] * a.inv_n : 0.f;
+            cst[g][5][c] = a.training ? a.sums[(size_t)g * 2 * PC + PC + c] * a.inv_n : 0.f;
+        }
     }
     // W^T fragments of the input gradient (A operand: row = ci, k = co): element j = W[co = kb*32 + 8 g4 + j][ci = cb*16 + r]
     bf16x8 wf[4][2];
@@ -240,7 +247,8 @@ static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const fl
                                int N, int group_images, int H, int W, const float* mean, const float* invstd,
                                const float* gamma, const float* beta, int training, const float* weight, float* dd,
                                int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
-                               float* workspace, size_t workspace_bytes, int flags, void* stream) {
+                               float* workspace, size_t workspace_bytes, int flags, void* stream,
+                               const double* dsums = nullptr, const double* count = nullptr) {
     const bool wg = !(flags & NVQ_NO_WGRAD);
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "pw_bn_backward: groups");
     NVQ_REQUIRE(p_ld % 8 == 0 && d_ld % 8 == 0 && dd_ld % 8 == 0 && dy_ld % 8 == 0 && p_ld >= PC && d_ld >= PC && dd_ld >= PC &&
@@ -258,7 +266,7 @@ static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const fl
     NVQ_REQUIRE(part_floats * sizeof(float) < workspace_bytes, "pw_bn_backward: workspace");
     float* sums = const_cast<float*>(sums_in);
     int rc = NVQ_OK;
-    if (!sums_in) {
+    if (!sums_in && !count) {
         // BatchNorm sums (and dgamma / dbeta) first: two-stage reduction in the workspace behind the weight-gradient slabs.  A
         // frozen affine (dgamma / dbeta NULL, _ex form): the finalize kernel writes them to the workspace's last 2 x 64 floats
         size_t sums_bytes = workspace_bytes - part_floats * sizeof(float);
@@ -275,7 +283,7 @@ static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const fl
     }
     PwBwdArgs a{dy, dy_ld, reinterpret_cast<const __bf16*>(p), p_ld, reinterpret_cast<const __bf16*>(d), d_ld, mean, invstd, gamma,
                 beta, sums, weight, reinterpret_cast<__bf16*>(dd), dd_ld, workspace, group_pix, G, training, tpg, (int)ntiles,
-                1.f / (float)group_pix};
+                1.f / (float)group_pix, dsums, count};
 #define NVQ_PWB(D_, W_) hipLaunchKernelGGL((pw_bn_bwd_kernel<D_, W_>), dim3(nsplit), dim3(256), 0, s, a)
     if (wg) { if (dy_bf16) NVQ_PWB(true, true); else NVQ_PWB(false, true); }
     else { if (dy_bf16) NVQ_PWB(true, false); else NVQ_PWB(false, false); }
@@ -302,4 +310,18 @@ extern "C" int nvq_pw_bn_backward_ex(const float* dy, int dy_ld, int dy_bf16, co
     NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "pw_bn_backward_ex: flags %d", flags);
     return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, training,
                                weight, dd, dd_ld, dgamma, dbeta, dweight, sums_in, workspace, workspace_bytes, flags, stream);
+}
+
+// finish phase of a synchronised BatchNorm: the reduce pass was nvq_pw_bn_backward_reduce, its sums all-reduced (sums [G][2][64]
+// fp64), count [G] the global pixel counts of the forward; dgamma / dbeta stay with the reduce phase
+extern "C" int nvq_pw_bn_backward_finish(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d,
+                                         int d_ld, int N, int group_images, int H, int W, const float* mean, const float* invstd,
+                                         const float* gamma, const float* beta, const float* weight, float* dd, int dd_ld,
+                                         float* dweight, const double* sums, const double* count, float* workspace,
+                                         size_t workspace_bytes, int flags, void* stream) {
+    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "pw_bn_backward_finish: flags %d", flags);
+    NVQ_REQUIRE(sums && count, "pw_bn_backward_finish: sums / count");
+    return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, 1, weight,
+                               dd, dd_ld, nullptr, nullptr, dweight, nullptr, workspace, workspace_bytes, flags, stream, sums,
+                               count);
 }

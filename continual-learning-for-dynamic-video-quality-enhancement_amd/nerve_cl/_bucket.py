@@ -20,6 +20,7 @@ import weakref
 from typing import Dict, List, Optional, Tuple
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from nerve_cl import _nvq
@@ -42,13 +43,50 @@ class BucketedNet(nn.Module):
         self._pending = None                   # weakref to the token of the latest forward-with-grad (see _mark_awaiting)
         self._deferred_adds: list = []         # (lam, star_flat, fisher_flat, scale_dev) to add into the next bucket
 
+    # ------------------------------------------------------------------ caches of the module tree
+    def _invalidate_module_caches(self) -> None:
+        """A sub-module was added or replaced (``nn.SyncBatchNorm.convert_sync_batchnorm`` re-adds every child of the network
+        with add_module): the cached parameter / buffer slots, the bucket layout, the parameter names, the backward plans and
+        the synchronised-BatchNorm list are rebuilt on their next use."""
+        d = self.__dict__
+        for k in ("_slot_cache", "_sync_cache", "_plan_cache"):
+            d.pop(k, None)
+        if "_layout" in d:
+            d["_layout"] = None
+        if "_param_names" in d:
+            d["_param_names"] = [n for n, _ in self.named_parameters()]
+
+    def add_module(self, name: str, module: Optional[nn.Module]) -> None:
+        super().add_module(name, module)
+        self._invalidate_module_caches()
+
+    def __setattr__(self, name: str, value) -> None:
+        super().__setattr__(name, value)
+        if isinstance(value, nn.Module):
+            self._invalidate_module_caches()
+
+    def _sync_bn_groups(self) -> Dict[str, object]:
+        """{holder name: process group} of the BatchNorm holders that synchronise in this pass: the nn.SyncBatchNorm holders
+        (nn.SyncBatchNorm.convert_sync_batchnorm, parallel.enable_data_parallel(sync_bn=True)), in a training pass, when
+        torch.distributed is initialised and the holder's group (None = WORLD) has more than one rank; {} otherwise (the
+        unsynchronised path).  The holders are found once per module tree (see _invalidate_module_caches)."""
+        c = self.__dict__.get("_sync_cache")
+        if c is None:
+            c = [(n, m) for n, m in self.named_modules() if isinstance(m, nn.SyncBatchNorm)]
+            self.__dict__["_sync_cache"] = c
+        if not c or not self.training or not dist.is_available() or not dist.is_initialized():
+            return {}
+        world = dist.group.WORLD
+        return {n: m.process_group if m.process_group is not None else world for n, m in c
+                if dist.get_world_size(m.process_group) > 1}
+
     # ------------------------------------------------------------------ layout
     def _slots(self):
         """([(name, owner._parameters, key)], [(name, owner._buffers, key)]) in named_parameters() / named_buffers() order, built
         once.  Every forward and backward needs all ~180 tensors by name; walking the module tree for them (named_parameters +
         named_buffers, ~150 modules) cost 1 ms of the 4 ms continual-learning step.  The owner dicts are looked up per call, so
         a parameter or buffer that is REPLACED (load_state_dict(assign=True), module.to() with swapped tensors) is still
-        found; adding or removing sub-modules after construction is not supported by the engine anyway."""
+        found; a sub-module added or replaced through add_module / attribute assignment drops the cache."""
         c = self.__dict__.get("_slot_cache")
         if c is None:
             def locate(name: str, kind: str):

@@ -42,6 +42,12 @@ def _fused_tail_ok(math: int, x: torch.Tensor, Cimg: int, scale: int) -> bool:
             and Cimg * scale * scale <= {2: 16, 3: 32, 4: 64}[scale] and os.environ.get("NVQ_FUSED_TAIL", "1") != "0")
 
 
+def _allreduce_sum_(t: torch.Tensor, group) -> None:
+    """the collective between the reduce and finish phases of a synchronised BatchNorm (nn.SyncBatchNorm)"""
+    import torch.distributed as dist
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
 def _capture(name: str, t) -> None:
     """t: a tensor, or a callable producing one (evaluated only while a capture is requested)"""
     if DEBUG_CAPTURE is not None:
@@ -139,7 +145,7 @@ class Saved:
 
 
 def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, training: bool, math: int,
-             act_dtype: torch.dtype, outA: Sl, split_images: int, outB: Optional[Sl], sv) -> None:
+             act_dtype: torch.dtype, outA: Sl, split_images: int, outB: Optional[Sl], sv, sync=None) -> None:
     """FeatureExtractor.forward (super_resolution.py:40-53) for the T = len(slots) frames of every clip, batched in slot
     order; the features of the first `split_images` images go to outA, the rest to outB.  Saves what backward needs in sv."""
     B, _, _, H, W = frames.shape
@@ -154,6 +160,7 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
                    img8=sv.img8, math=math)
     sv.feat0 = feat0
     sv.dws, sv.pws, sv.acts, sv.bn_mean, sv.bn_invstd = [], [], [], [], []
+    sv.bn_sync = []                   # per layer: (process group, forward stats buffer) of a synchronised BatchNorm, or None
     cur, cur_bn = feat0, None         # cur_bn: BatchNorm + ReLU still to be applied to `cur` (fused into the consumer)
     sv.dw_in = []                     # (tensor, bn) the depthwise conv of layer k was fed with
     fuse_bn = K.dwconv_bn_fusable(feat0, F)
@@ -164,7 +171,12 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
         p = _new(dev, NI, H, W, F, dtype=act_dtype)
         mean, invstd = _new(dev, T, F), _new(dev, T, F)
         order = [slots.index(t) for t in range(T)]
-        if fused_fwd:
+        grp = sync.get(pre + "bn") if (training and sync) else None
+        st = K.new_bn_stats(dev, T, F) if grp is not None else None
+        if fused_fwd and grp is not None:
+            # synchronised BatchNorm: the fused pass leaves the per-frame sums, all ranks add them, then the statistics
+            K.dwpw_forward_sums(cur, cur_bn, P[pre + "depthwise.weight"], P[pre + "pointwise.weight"], d, p, B, st, ws)
+        elif fused_fwd:
             # depthwise -> pointwise -> BatchNorm sums in one pass over the tensors (nvq_dwpw_forward)
             K.dwpw_forward(cur, cur_bn, P[pre + "depthwise.weight"], P[pre + "pointwise.weight"], d, p, B,
                            order if training else None, mean, invstd, P[pre + "bn.running_mean"],
@@ -173,9 +185,15 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
             K.dwconv_forward(cur, P[pre + "depthwise.weight"], d, bn=cur_bn)
             wp = K.conv_pack(P[pre + "pointwise.weight"], False, F, math=math)
             K.conv_forward(Sl(d), wp, None, Sl(p), 1, math=math)
-            if training:
+            if grp is not None:
+                K.bn_stats_reduce(p, B, st, ws)
+            elif training:
                 K.bn_stats(p, B, order, mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], ws, BN_EPS,
                            BN_MOM)
+        if grp is not None:
+            _allreduce_sum_(st, grp)
+            K.bn_stats_finish(st, T, order, mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], BN_EPS, BN_MOM)
+        sv.bn_sync.append((grp, st) if grp is not None else None)
         sv.dw_in.append((cur, cur_bn))
         if training:
             P[pre + "bn.num_batches_tracked"].add_(T)
@@ -197,10 +215,11 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
 
 def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: int, scale: int,
             training: bool, math: int = K.MATH_F32, act_dtype: torch.dtype = torch.float32,
-            features: Optional[torch.Tensor] = None) -> "tuple[torch.Tensor, Saved]":
+            features: Optional[torch.Tensor] = None, sync: Optional[dict] = None) -> "tuple[torch.Tensor, Saved]":
     """act_dtype: storage type of the conv-internal tensors (dense-block concat buffers, flow-net and attention
     hidden activations and, in backward, their gradients).  torch.bfloat16 needs math == MATH_BF16; every
-    tensor a non-conv kernel touches stays fp32."""
+    tensor a non-conv kernel touches stays fp32.  sync: {BatchNorm holder name: process group} of the synchronised
+    BatchNorm layers of a training pass (BucketedNet._sync_bn_groups); their statistics are all-reduced over the group."""
     assert act_dtype == torch.float32 or math == K.MATH_BF16
     g = Geometry(frames, F, nblocks, scale)
     dev = frames.device
@@ -232,7 +251,8 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     feat_oth = _new(dev, max(NO, 1), H, W, F, dtype=feat_dtype)
     sv.aligned, sv.feat_oth = aligned, feat_oth
     if features is None:
-        _extract(P, frames, g.slots, F, training, math, act_dtype, Sl(aligned, F, c * F), B, Sl(feat_oth) if NO else None, sv)
+        _extract(P, frames, g.slots, F, training, math, act_dtype, Sl(aligned, F, c * F), B, Sl(feat_oth) if NO else None, sv,
+                 sync)
     else:
         # inference with cached per-frame features (extract_features), [T,B,H,W,F] in time order: no extractor launches
         assert not training and tuple(features.shape) == (T, B, H, W, F) and features.dtype == torch.float32
@@ -794,6 +814,9 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
     # (built and measured, off by default: with the sums in it the depthwise backward only fits its registers with two instead
     # of five unrolled rows, and the step is 0.2 ms SLOWER than with the separate 0.54 ms reduce passes it replaces)
     fuse_sums = os.environ.get("NVQ_FUSED_BN_SUMS", "0") != "0"
+    bn_sync = getattr(sv, "bn_sync", None) or [None, None, None]
+    if any(bn_sync):
+        fuse_sums = False             # a synchronised layer's sums are all-reduced between its reduce and finish phases
     for k in (2, 1, 0):
         pre = f"feature_extractor.body.{k}."
         if f"body.{k}" not in run:                # the layers below need nothing either
@@ -802,7 +825,28 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         dd = _new(dev, NI, H, W, F, dtype=act_dtype)
         fused_bwd = (math == K.MATH_BF16 and act_dtype == torch.bfloat16 and F == 64 and sv.pws[k].dtype == torch.bfloat16
                      and sv.dws[k].dtype == torch.bfloat16)
-        if fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
+        if bn_sync[k] is not None:
+            # synchronised BatchNorm: {sum g, sum g xhat} of every rank, dx from the global sums and the forward's global count
+            grp, st = bn_sync[k]
+            bsums = _new(dev, T * 2 * F, dtype=torch.float64)
+            cnt = K.bn_counts(st, T, F)
+            if fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
+                K.pw_bn_backward_reduce(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"], P[pre + "bn.bias"],
+                                        bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
+                _allreduce_sum_(bsums, grp)
+                K.pw_bn_backward_finish(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
+                                        P[pre + "bn.bias"], P[pre + "pointwise.weight"], dd, G.get(pre + "pointwise.weight"), bsums,
+                                        cnt, ws)
+            else:
+                dp = _new(dev, NI, H, W, F, dtype=act_dtype)
+                K.bn_relu_backward_reduce(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
+                                          P[pre + "bn.bias"], bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
+                _allreduce_sum_(bsums, grp)
+                K.bn_relu_backward_finish(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
+                                          P[pre + "bn.bias"], bsums, cnt, dp)
+                _wgrad(Sl(sv.dws[k]), F, Sl(dp), G, pre + "pointwise.weight", None, wq, 1, math=math)
+                K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
+        elif fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
             # BatchNorm backward + the pointwise conv's input and weight gradients in one pass behind the BatchNorm sums: dp is
             # formed in LDS and never stored (nvq_pw_bn_backward; a frozen pointwise weight or BatchNorm affine: the _ex form)
             dgam, dbet = bn_targets if bn_sums is not None else (G.get(pre + "bn.weight"), G.get(pre + "bn.bias"))
@@ -868,9 +912,9 @@ LIGHT_F = 32
 LIGHT_BLOCKS = (2, 3, 4, 5)       # indices of the DepthwiseSeparableConv modules inside `net`
 
 def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, training: bool, math: int = K.MATH_F32,
-                  act_dtype: torch.dtype = torch.float32) -> "tuple[torch.Tensor, Saved]":
+                  act_dtype: torch.dtype = torch.float32, sync: Optional[dict] = None) -> "tuple[torch.Tensor, Saved]":
     """Single-frame net (reference super_resolution.py:434-470): conv3x3+ReLU, four depthwise-separable blocks,
-    conv3x3 -> PixelShuffle, + bicubic(x), clamp.  Same kernels as the SR feature extractor and tail."""
+    conv3x3 -> PixelShuffle, + bicubic(x), clamp.  Same kernels as the SR feature extractor and tail.  sync: as in forward()."""
     assert act_dtype == torch.float32 or math == K.MATH_BF16
     dev = x.device
     B, Cimg, H, W = x.shape
@@ -882,6 +926,7 @@ def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, train
     feat0 = _new(dev, B, H, W, F, dtype=act_dtype)
     K.head_forward(frames, [0], P["net.0.weight"], P["net.0.bias"], feat0, math=math)
     sv.feat0, sv.dws, sv.pws, sv.acts, sv.bn_mean, sv.bn_invstd = feat0, [], [], [], [], []
+    sv.bn_sync = []
     cur = feat0
     for k in LIGHT_BLOCKS:
         pre = f"net.{k}."
@@ -890,7 +935,16 @@ def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, train
         p = _new(dev, B, H, W, F, dtype=act_dtype)
         K.conv_forward(Sl(d), K.conv_pack(P[pre + "pointwise.weight"], False, F, math=math), None, Sl(p), 1, math=math)
         mean, invstd = _new(dev, 1, F), _new(dev, 1, F)
-        if training:
+        grp = sync.get(pre + "bn") if (training and sync) else None
+        sv.bn_sync.append(None)
+        if grp is not None:
+            st = K.new_bn_stats(dev, 1, F)
+            K.bn_stats_reduce(p, B, st, ws)
+            _allreduce_sum_(st, grp)
+            K.bn_stats_finish(st, 1, [0], mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], BN_EPS, BN_MOM)
+            P[pre + "bn.num_batches_tracked"].add_(1)
+            sv.bn_sync[-1] = (grp, st)
+        elif training:
             K.bn_stats(p, B, [0], mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], ws, BN_EPS, BN_MOM)
             P[pre + "bn.num_batches_tracked"].add_(1)
         else:
@@ -940,8 +994,18 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
             break
         pre = f"net.{LIGHT_BLOCKS[j]}."
         dp = _new(dev, B, H, W, F, dtype=act_dtype)
-        K.bn_relu_backward(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                           sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
+        bsync = sv.bn_sync[j] if getattr(sv, "bn_sync", None) else None
+        if bsync is not None:
+            # synchronised BatchNorm (see backward())
+            bsums = _new(dev, 2 * F, dtype=torch.float64)
+            K.bn_relu_backward_reduce(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
+                                      bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
+            _allreduce_sum_(bsums, bsync[0])
+            K.bn_relu_backward_finish(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
+                                      bsums, K.bn_counts(bsync[1], 1, F), dp)
+        else:
+            K.bn_relu_backward(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
+                               sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
         _wgrad(Sl(sv.dws[j]), F, Sl(dp), G, pre + "pointwise.weight", None, ws, 1, math=math)
         dww = G.get(pre + "depthwise.weight")
         if dww is None and f"block.{j}" not in dxs:

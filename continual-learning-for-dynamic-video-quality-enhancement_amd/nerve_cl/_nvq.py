@@ -164,6 +164,19 @@ SIGNATURES = {
     "nvq_bn2_apply": (ci, [vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp]),
     "nvq_bn2_backward": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp, sz, ci, vp]),
     "nvq_bn2_backward_ex": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp, sz, ci, ci, vp]),
+    # synchronised BatchNorm: reduce / finish phases (fp64 sums in caller buffers)
+    "nvq_bn_stats_reduce": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, sz, ci, vp]),
+    "nvq_bn_stats_finish": (ci, [vp, ci, ci, cf, cf, _IP, vp, vp, vp, vp, vp]),
+    "nvq_dwpw_forward_sums": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, sz, vp]),
+    "nvq_bn_relu_backward_reduce": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, vp]),
+    "nvq_bn_relu_backward_finish": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "nvq_pw_bn_backward_reduce": (ci, [vp, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "nvq_pw_bn_backward_finish": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz,
+                                       ci, vp]),
+    "nvq_bn2_stats_reduce": (ci, [vp, ci, ci, cl, vp, vp, sz, ci, vp]),
+    "nvq_bn2_stats_finish": (ci, [vp, ci, cf, cf, vp, vp, vp, vp, vp]),
+    "nvq_bn2_backward_reduce": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, sz, ci, vp]),
+    "nvq_bn2_backward_finish": (ci, [vp, ci, vp, ci, ci, cl, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, vp]),
     "nvq_maxpool_forward": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp]),
     "nvq_maxpool_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp]),
     "nvq_subsample2": (ci, [vp, ci, ci, ci, ci, vp, ci, ci, vp]),
@@ -794,6 +807,79 @@ def pw_bn_backward(dy: torch.Tensor, p: torch.Tensor, d: torch.Tensor, group_ima
         npx = N * H * W
         TIMER.stop(ev0, "pw_bn_bwd_kernel", 2.0 * npx * 64 * 64 * 2,
                    npx * 64 * (2.0 * 2 + (2 if is_bf16(dy) else 4) * 2 + 2), f"n{N} 64->64 {'h' if is_bf16(dy) else 'f'}")
+
+
+# ----------------------------------------------------------------------------- synchronised BatchNorm (reduce / finish)
+# Forward stats buffers: fp64 [G * 2 * C + G] = {sum x, sum x^2} per (group, channel), then the G pixel counts; backward sums:
+# fp64 [G * 2 * C] = {sum g, sum g xhat}.  The caller all-reduces them between the two phases (see include/nvq.h).
+def new_bn_stats(dev, G: int, Cc: int) -> torch.Tensor:
+    return torch.empty(G * 2 * Cc + G, dtype=torch.float64, device=dev)
+
+
+def bn_counts(stats: torch.Tensor, G: int, Cc: int) -> torch.Tensor:
+    """the G pixel counts at the end of a forward stats buffer (what the backward finish phases read)"""
+    return stats[G * 2 * Cc:]
+
+
+def bn_stats_reduce(x: torch.Tensor, group_images: int, stats: torch.Tensor, ws) -> None:
+    N, H, W, ld = x.shape
+    Cc = (stats.numel() // (N // group_images) - 1) // 2
+    check(lib().nvq_bn_stats_reduce(ptr(x), ld, Cc, N, group_images, H, W, ptr(stats), ptr(ws), ws.numel() * 4, is_bf16(x),
+                                    stream()), "nvq_bn_stats_reduce")
+
+
+def bn_stats_finish(stats: torch.Tensor, G: int, order: Sequence[int], mean, invstd, rmean, rvar, eps=1e-5,
+                    momentum=0.1) -> None:
+    check(lib().nvq_bn_stats_finish(ptr(stats), mean.shape[-1], G, eps, momentum, int_array(order), ptr(mean), ptr(invstd),
+                                    ptr(rmean), ptr(rvar), stream()), "nvq_bn_stats_finish")
+
+
+def dwpw_forward_sums(x: torch.Tensor, bn, dw_weight: torch.Tensor, pw_weight: torch.Tensor, d: torch.Tensor, p: torch.Tensor,
+                      group_images: int, stats: torch.Tensor, ws) -> None:
+    """dwpw_forward whose statistics leave as sums (nvq_dwpw_forward_sums)"""
+    N, H, W, ld = x.shape
+    assert x.dtype == d.dtype == p.dtype == torch.bfloat16 and tuple(pw_weight.shape[:2]) == (64, 64)
+    b = _bn_input(bn)
+    check(lib().nvq_dwpw_forward_sums(ptr(x), ld, C.byref(b) if b is not None else None, ptr(dw_weight.contiguous()),
+                                      ptr(pw_weight.contiguous()), ptr(d), d.shape[-1], ptr(p), p.shape[-1], N, group_images, H,
+                                      W, ptr(stats), ptr(ws), ws.numel() * 4, stream()), "nvq_dwpw_forward_sums")
+
+
+def bn_relu_backward_reduce(dy: torch.Tensor, x: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
+                            sums: torch.Tensor, dgamma, dbeta, ws, accumulate=False) -> None:
+    N, H, W, ld = x.shape
+    check(lib().nvq_bn_relu_backward_reduce(ptr(dy), dy.shape[-1], ptr(x), ld, gamma.numel(), N, group_images, H, W, ptr(mean),
+                                            ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), ptr(dgamma), ptr(dbeta), ptr(ws),
+                                            ws.numel() * 4, int(accumulate), is_bf16(dy), is_bf16(x), stream()),
+          "nvq_bn_relu_backward_reduce")
+
+
+def bn_relu_backward_finish(dy: torch.Tensor, x: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
+                            sums: torch.Tensor, count: torch.Tensor, dx: torch.Tensor) -> None:
+    N, H, W, ld = x.shape
+    check(lib().nvq_bn_relu_backward_finish(ptr(dy), dy.shape[-1], ptr(x), ld, gamma.numel(), N, group_images, H, W, ptr(mean),
+                                            ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), ptr(count), ptr(dx), dx.shape[-1],
+                                            is_bf16(dy), is_bf16(x), is_bf16(dx), stream()), "nvq_bn_relu_backward_finish")
+
+
+def pw_bn_backward_reduce(dy: torch.Tensor, p: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
+                          sums: torch.Tensor, dgamma, dbeta, ws) -> None:
+    N, H, W, _ = p.shape
+    assert p.dtype == torch.bfloat16
+    check(lib().nvq_pw_bn_backward_reduce(ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], N, group_images, H, W,
+                                          ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), ptr(dgamma), ptr(dbeta),
+                                          ptr(ws), ws.numel() * 4, stream()), "nvq_pw_bn_backward_reduce")
+
+
+def pw_bn_backward_finish(dy: torch.Tensor, p: torch.Tensor, d: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
+                          weight: torch.Tensor, dd: torch.Tensor, dweight, sums: torch.Tensor, count: torch.Tensor, ws) -> None:
+    N, H, W, _ = p.shape
+    assert p.dtype == d.dtype == dd.dtype == torch.bfloat16 and tuple(weight.shape[:2]) == (64, 64)
+    check(lib().nvq_pw_bn_backward_finish(ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], ptr(d), d.shape[-1], N,
+                                          group_images, H, W, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
+                                          ptr(weight.contiguous()), ptr(dd), dd.shape[-1], ptr(dweight), ptr(sums), ptr(count),
+                                          ptr(ws), ws.numel() * 4, NO_WGRAD if dweight is None else 0, stream()),
+          "nvq_pw_bn_backward_finish")
 
 
 # ----------------------------------------------------------------------------- motion

@@ -545,6 +545,70 @@ class BatchNorm(torch.autograd.Function):
         return dx, dgamma, dbeta, dres, None, None, None, None
 
 
+class SyncBatchNorm(torch.autograd.Function):
+    """BatchNorm (training mode) of an nn.SyncBatchNorm holder whose process group has more than one rank: BatchNorm's
+    forward and backward with every statistic taken over all ranks' pixels (torch.nn.SyncBatchNorm's semantics).  Each
+    direction is reduce (fp64 sums into a small buffer) -> one all-reduce -> finish (nvq_bn2_*_reduce / _finish); the count
+    travels in the forward's buffer, so ranks may hold different batch sizes.  dgamma / dbeta are this rank's (the bucket
+    all-reduce averages them like every other parameter gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, relu: bool, group):
+        N, H, W, ld = x.shape
+        C = gamma.numel()
+        npix = N * H * W
+        assert res is None or res.dtype == x.dtype
+        mean, invstd = _new(x, C), _new(x, C)
+        st = _new(x, 2 * C + 1, dtype=torch.float64)
+        ws = _ws(x)
+        check(lib().nvq_bn2_stats_reduce(ptr(x), ld, C, npix, ptr(st), ptr(ws), ws.numel() * 4, _bf(x), stream()),
+              "nvq_bn2_stats_reduce")
+        _engine._allreduce_sum_(st, group)
+        check(lib().nvq_bn2_stats_finish(ptr(st), C, BN_EPS, BN_MOMENTUM, ptr(mean), ptr(invstd), ptr(rmean), ptr(rvar),
+                                         stream()), "nvq_bn2_stats_finish")
+        y = torch.empty_like(x)
+        check(lib().nvq_bn2_apply(ptr(x), ld, C, npix, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(res),
+                                  res.shape[-1] if res is not None else 0, int(relu), ptr(y), ld, _bf(x), stream()), "nvq_bn2_apply")
+        ctx.save_for_backward(x, gamma, beta, res, mean, invstd, st)
+        ctx.relu, ctx.group = relu, group
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, res, mean, invstd, st = ctx.saved_tensors
+        N, H, W, ld = x.shape
+        C = gamma.numel()
+        npix = N * H * W
+        dy = dy.contiguous()
+        assert dy.dtype == x.dtype
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(res) if res is not None else None
+        dgamma = torch.empty_like(gamma) if ctx.needs_input_grad[1] else None
+        dbeta = torch.empty_like(beta) if ctx.needs_input_grad[2] else None
+        sums = _new(x, 2 * C, dtype=torch.float64)
+        ws = _ws(x)
+        rl, dl = (res.shape[-1] if res is not None else 0), (dres.shape[-1] if dres is not None else 0)
+        check(lib().nvq_bn2_backward_reduce(ptr(dy), dy.shape[-1], ptr(x), ld, C, npix, ptr(mean), ptr(invstd), ptr(gamma),
+                                            ptr(beta), ptr(res), rl, int(ctx.relu), ptr(dres), dl, ptr(sums), ptr(dgamma),
+                                            ptr(dbeta), ptr(ws), ws.numel() * 4, _bf(x), stream()), "nvq_bn2_backward_reduce")
+        _engine._allreduce_sum_(sums, ctx.group)
+        check(lib().nvq_bn2_backward_finish(ptr(dy), dy.shape[-1], ptr(x), ld, C, npix, ptr(mean), ptr(invstd), ptr(gamma),
+                                            ptr(beta), ptr(dres), dl, int(ctx.relu), ptr(sums), ptr(st, 2 * C), ptr(dx), ld,
+                                            _bf(x), stream()), "nvq_bn2_backward_finish")
+        return dx, dgamma, dbeta, dres, None, None, None, None
+
+
+def sync_group(mod):
+    """the process group an nn.SyncBatchNorm holder synchronises over in a training pass, or None (an nn.BatchNorm holder,
+    torch.distributed not initialised, a group of one rank): the unsynchronised path"""
+    if not isinstance(mod, torch.nn.SyncBatchNorm):
+        return None
+    import torch.distributed as dist
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(mod.process_group) <= 1:
+        return None
+    return mod.process_group if mod.process_group is not None else dist.group.WORLD
+
+
 # ----------------------------------------------------------------------------- pooling / resampling
 class MaxPool(torch.autograd.Function):
     """nn.MaxPool2d(k, s, pad) / F.max_pool3d(x, (1,k,k)) on the image batch"""
@@ -919,4 +983,7 @@ def bn(x, mod, training: bool, relu: bool, res=None):
     """apply an nn.BatchNorm2d / BatchNorm3d holder `mod` (its buffers are updated in place in training mode)"""
     if training:
         mod.num_batches_tracked.add_(1)
+        group = sync_group(mod)
+        if group is not None:
+            return SyncBatchNorm.apply(x, mod.weight, mod.bias, res, mod.running_mean, mod.running_var, relu, group)
     return BatchNorm.apply(x, mod.weight, mod.bias, res, mod.running_mean, mod.running_var, training, relu)

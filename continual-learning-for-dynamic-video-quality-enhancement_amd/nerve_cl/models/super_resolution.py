@@ -186,15 +186,23 @@ class _SRFunction(torch.autograd.Function):
         ctx.plan = net._backward_plan(ctx.needs_input_grad[3:], ctx.needs_input_grad[1]) if need_grad else None
         if any(ctx.needs_input_grad[3:]):
             net._mark_awaiting(ctx)
+        # synchronised BatchNorm layers (nn.SyncBatchNorm holders in a training pass of a multi-rank group): their collectives are
+        # not captured, so such a step runs eagerly (an explicit use_hip_graphs = True counts it as an eager fallback)
+        sync = net._sync_bn_groups()
+        graphs = net._graphs_wanted(frames)
+        if graphs and sync:
+            if net.use_hip_graphs is True:
+                net._step_graphs.eager_fallbacks += 1
+            graphs = False
         # (a step whose frames need a gradient runs eagerly: the captured graphs compute no input gradient)
-        if net._graphs_wanted(frames) and not want_inter and not ctx.needs_input_grad[1]:
+        if graphs and not want_inter and not ctx.needs_input_grad[1]:
             hit = net._step_graphs.forward(net, frames, need_grad, act, ctx.deterministic, ctx.plan)
             if hit is not None:
                 out, entry, ctx.token, gen = hit
                 ctx.graph = (entry, gen) if need_grad else None
                 ctx.sv = None
                 return out
-        out, sv = _engine.forward(P, frames, net._F, net._NB, net.scale_factor, net.training, net.math_mode, act)
+        out, sv = _engine.forward(P, frames, net._F, net._NB, net.scale_factor, net.training, net.math_mode, act, sync=sync)
         ctx.sv = sv if need_grad else None
         if want_inter:
             return (out, *_engine.intermediates(sv))
@@ -375,7 +383,8 @@ class _LightFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net: "LightweightSuperResolution", x: torch.Tensor, *params):
         act = torch.bfloat16 if (net.bf16_activations and net.math_mode == _nvq.MATH_BF16) else torch.float32
-        out, sv = _engine.light_forward(net._tensor_dict(), x, net.scale_factor, net.training, net.math_mode, act)
+        out, sv = _engine.light_forward(net._tensor_dict(), x, net.scale_factor, net.training, net.math_mode, act,
+                                        sync=net._sync_bn_groups())
         ctx.net = net
         ctx.sv = sv if (any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[1]) else None
         ctx.plan = None

@@ -101,14 +101,21 @@ def unflatten_into_(flat: torch.Tensor, tensors: Iterable[torch.Tensor]) -> None
         off += n
 
 
-def enable_data_parallel(module: torch.nn.Module, group=None, broadcast: bool = True) -> torch.nn.Module:
+def enable_data_parallel(module: torch.nn.Module, group=None, broadcast: bool = True, sync_bn: bool = False) -> torch.nn.Module:
     """Turn on gradient all-reduce for every bucketed network (SuperResolutionNet, LightweightSuperResolution,
     FrameRecoveryNet) inside `module`.
 
     After this call ``loss.backward()`` leaves rank-averaged gradients in ``.grad`` exactly
     where a single-process run would leave them, so the reference training loops need no change.
-    (``EWC.compute_fisher`` switches the hook off while it runs: the Fisher needs per-rank gradients.)"""
+    (``EWC.compute_fisher`` switches the hook off while it runs: the Fisher needs per-rank gradients.)
+
+    sync_bn: convert every BatchNorm holder to ``nn.SyncBatchNorm`` over `group` (``convert_sync_batchnorm``; the state_dict
+    keys stay the same).  Training-mode BatchNorm then normalises with the statistics of the global batch, so the gradients
+    are the single-process gradients of the global-batch loss.  The conversion replaces sub-modules:
+    use the returned module (it is `module` itself unless `module` is a BatchNorm)."""
     from nerve_cl._bucket import BucketedNet
+    if sync_bn:
+        module = torch.nn.SyncBatchNorm.convert_sync_batchnorm(module, group)
     if broadcast:
         broadcast_state_(module, 0, group)
     for m in module.modules():
@@ -128,7 +135,8 @@ def allreduce_scalars(values, group=None, device=None) -> "list[float]":
 
 def average_bn_buffers_(module: torch.nn.Module, group=None) -> None:
     """Average BatchNorm running statistics across ranks (done at checkpoint time; training
-    itself uses per-rank batch statistics, i.e. standard DDP semantics)."""
+    itself uses per-rank batch statistics, i.e. standard DDP semantics, SURVEY.md 8e, unless the holders are
+    nn.SyncBatchNorm: then the ranks' statistics are identical already)."""
     w = world_size(group)
     if w <= 1:
         return

@@ -41,7 +41,7 @@ def train(args) -> None:
     say("Creating model...")
     model = SuperResolutionNet(scale_factor=2, num_features=32, num_residual_blocks=4, temporal_window=1).to(device)
     if world > 1:
-        parallel.enable_data_parallel(model)
+        model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     say(f"  Parameters: {sum(p.numel() for p in model.parameters()):,}")
     optimizer = make_optimizer(torch.optim.AdamW, model.parameters(), lr=args.lr, weight_decay=1e-5)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=args.epochs)
@@ -99,6 +99,8 @@ def main() -> None:
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
     args = ap.parse_args()
     Path("checkpoints").mkdir(exist_ok=True)
     train(args)

@@ -122,6 +122,8 @@ def main() -> None:
                     help="MFMA operand precision of the convolutions (accumulation fp32; fp32 = the exact parity mode)")
     ap.add_argument("--graphs", choices=["auto", "on", "off"], default="auto",
                     help="HIP-graph replay of the training step (auto: for launch-bound frame sizes only)")
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
     args = ap.parse_args()
 
     device, rank, world = pick_device()
@@ -131,7 +133,7 @@ def main() -> None:
                                                 sr_num_residual_blocks=args.blocks)).to(device)
     configure_precision(model, args.precision, args.graphs)
     if world > 1:
-        parallel.enable_data_parallel(model)
+        model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
     config = {"ewc_lambda": args.ewc_lambda}
     if args.strategy == "ewc":

@@ -694,6 +694,56 @@ int nvq_fisher_accumulate(const float* grad, long n, float* fisher, void* stream
 int nvq_si_update(const float* theta, const float* grad, long n, float* p_old, float* W, void* stream);
 int nvq_si_consolidate(const float* theta, long n, float damping, float* p_old, float* W, float* omega, void* stream);
 
+/* ---- Synchronised BatchNorm (nn.SyncBatchNorm in data-parallel training): every statistics reduction above ends in a
+ * finalize step that turns per-block partials into fp64 sums.  These entry points split it at that seam: REDUCE leaves the
+ * sums in a caller buffer (fp64), the caller all-reduces that buffer over the ranks, FINISH takes the global sums and reads
+ * the pixel count from device memory (no host synchronisation).  With the local sums, reduce + finish is bit-identical to the
+ * one-call form.  Buffers (fp64):
+ *   forward stats: [G][2][C] = {sum x, sum x^2} per group and channel, then [G] pixel counts (G = 1 for nvq_bn2_*);
+ *   backward sums: [G][2][C] = {sum g, sum g*xhat} (g = dy masked by the forward ReLU).
+ * dgamma / dbeta are written by the backward reduce phase from the local sums (either may be NULL: a frozen affine); the
+ * backward finish phases take the forward's counts (stats + 2*C*G) and compute dx as training-mode BatchNorm does. */
+int nvq_bn_stats_reduce(const float* x, int x_ld, int C, int N, int group_images, int H, int W, double* stats,
+                        float* workspace, size_t workspace_bytes, int x_bf16, void* stream);
+int nvq_bn_stats_finish(const double* stats, int C, int G, float eps, float momentum, const int* order_host,
+                        float* mean, float* invstd, float* running_mean, float* running_var, void* stream);
+/* nvq_dwpw_forward with its statistics left as sums (the fused bf16, 64-channel forward) */
+int nvq_dwpw_forward_sums(const float* in, int in_ld, const nvq_bn_input* bn, const float* dw_weight,
+                          const float* pw_weight, float* d, int d_ld, float* p, int p_ld, int N, int group_images,
+                          int H, int W, double* stats, float* workspace, size_t workspace_bytes, void* stream);
+int nvq_bn_relu_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld, int C, int N, int group_images,
+                                int H, int W, const float* mean, const float* invstd, const float* gamma,
+                                const float* beta, double* sums, float* dgamma, float* dbeta, float* workspace,
+                                size_t workspace_bytes, int accumulate, int dy_bf16, int x_bf16, void* stream);
+int nvq_bn_relu_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld, int C, int N, int group_images,
+                                int H, int W, const float* mean, const float* invstd, const float* gamma,
+                                const float* beta, const double* sums, const double* count, float* dx, int dx_ld,
+                                int dy_bf16, int x_bf16, int dx_bf16, void* stream);
+/* the reduce pass of nvq_pw_bn_backward alone, and the pass behind it (dd, dweight; flags: 0 or NVQ_NO_WGRAD) */
+int nvq_pw_bn_backward_reduce(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, int N,
+                              int group_images, int H, int W, const float* mean, const float* invstd,
+                              const float* gamma, const float* beta, double* sums, float* dgamma, float* dbeta,
+                              float* workspace, size_t workspace_bytes, void* stream);
+int nvq_pw_bn_backward_finish(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d,
+                              int d_ld, int N, int group_images, int H, int W, const float* mean,
+                              const float* invstd, const float* gamma, const float* beta, const float* weight,
+                              float* dd, int dd_ld, float* dweight, const double* sums, const double* count,
+                              float* workspace, size_t workspace_bytes, int flags, void* stream);
+int nvq_bn2_stats_reduce(const float* x, int x_ld, int C, long npix, double* stats, float* workspace,
+                         size_t workspace_bytes, int bf16, void* stream);
+int nvq_bn2_stats_finish(const double* stats, int C, float eps, float momentum, float* mean, float* invstd,
+                         float* running_mean, float* running_var, void* stream);
+/* dres (with res): the reduce phase writes g there, the finish phase reads it back */
+int nvq_bn2_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix,
+                            const float* mean, const float* invstd, const float* gamma, const float* beta,
+                            const float* res, int res_ld, int relu, float* dres, int dres_ld, double* sums,
+                            float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes, int bf16,
+                            void* stream);
+int nvq_bn2_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix,
+                            const float* mean, const float* invstd, const float* gamma, const float* beta,
+                            const float* dres, int dres_ld, int relu, const double* sums, const double* count,
+                            float* dx, int dx_ld, int bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
