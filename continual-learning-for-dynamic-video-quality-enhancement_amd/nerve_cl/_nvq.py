@@ -201,6 +201,11 @@ SIGNATURES = {
     "nvq_pixel_shuffle": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp]),
     "nvq_mse_forward": (ci, [vp, vp, cl, vp, vp, sz, vp]),
     "nvq_mse_backward": (ci, [vp, vp, cl, vp, vp, vp]),
+    "nvq_quality_sums": (ci, [vp, vp, ci, cl, vp, vp, sz, vp]),
+    "nvq_pixel_loss_forward": (ci, [vp, vp, ci, cl, ci, cf, vp, vp, sz, vp]),
+    "nvq_pixel_loss_backward": (ci, [vp, vp, ci, cl, ci, cf, vp, vp, vp]),
+    "nvq_ssim_forward": (ci, [vp, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, sz, vp]),
+    "nvq_ssim_backward": (ci, [vp, vp, ci, ci, ci, ci, cf, vp, ci, cf, vp, vp]),
     "nvq_axpy_slice": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, cl, cf, ci, ci, vp]),
     "nvq_colsum": (ci, [vp, ci, ci, ci, cl, cf, vp, vp, sz, ci, vp]),
     "nvq_ewc_penalty": (ci, [vp, vp, vp, cl, cf, vp, vp, sz, vp]),
@@ -1136,6 +1141,43 @@ def mse_forward(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, ws: torch.T
 
 def mse_backward(a: torch.Tensor, b: torch.Tensor, go_dev: Optional[torch.Tensor], da: torch.Tensor):
     check(lib().nvq_mse_backward(ptr(a), ptr(b), a.numel(), ptr(go_dev), ptr(da), stream()), "nvq_mse_backward")
+
+
+LOSS_L1, LOSS_CHARBONNIER, LOSS_MSE = 0, 1, 2   # NVQ_LOSS_*
+
+
+def quality_sums(x: torch.Tensor, y: torch.Tensor, out: torch.Tensor, ws: torch.Tensor):
+    """out (B, 8) float64: per sample n and the seven sums of nvq_quality_sums; x, y (B, ...) fp32"""
+    B = x.shape[0]
+    check(lib().nvq_quality_sums(ptr(x), ptr(y), B, x.numel() // B, ptr(out), ptr(ws), ws.numel() * 4, stream()),
+          "nvq_quality_sums")
+
+
+def pixel_loss_forward(x: torch.Tensor, y: torch.Tensor, kind: int, eps: float, out: torch.Tensor, ws: torch.Tensor):
+    """out (G,): G = 1 the mean over the whole tensor, G = x.shape[0] the mean over each sample"""
+    G = out.numel()
+    check(lib().nvq_pixel_loss_forward(ptr(x), ptr(y), G, x.numel() // G, kind, eps, ptr(out), ptr(ws), ws.numel() * 4,
+                                       stream()), "nvq_pixel_loss_forward")
+
+
+def pixel_loss_backward(x: torch.Tensor, y: torch.Tensor, kind: int, eps: float, go_dev: torch.Tensor, dx: torch.Tensor):
+    G = go_dev.numel()
+    check(lib().nvq_pixel_loss_backward(ptr(x), ptr(y), G, x.numel() // G, kind, eps, ptr(go_dev), ptr(dx), stream()),
+          "nvq_pixel_loss_backward")
+
+
+def ssim_forward(x: torch.Tensor, y: torch.Tensor, data_range: float, as_loss: bool, out: torch.Tensor, ws: torch.Tensor):
+    """x, y (B, C, H, W) fp32; out (B,) per sample or (1,) over the batch"""
+    B, Cc, H, W = x.shape
+    check(lib().nvq_ssim_forward(ptr(x), ptr(y), B, Cc, H, W, data_range, int(out.numel() != 1 or B == 1), int(as_loss),
+                                 ptr(out), ptr(ws), ws.numel() * 4, stream()), "nvq_ssim_forward")
+
+
+def ssim_backward(x: torch.Tensor, y: torch.Tensor, data_range: float, go_dev: torch.Tensor, scale: float, dx: torch.Tensor):
+    """dx = scale * go * d(mean SSIM) / dx; go_dev (B,) per sample or (1,) for the batch mean"""
+    B, Cc, H, W = x.shape
+    check(lib().nvq_ssim_backward(ptr(x), ptr(y), B, Cc, H, W, data_range, ptr(go_dev), int(go_dev.numel() != 1 or B == 1),
+                                  scale, ptr(dx), stream()), "nvq_ssim_backward")
 
 
 # ----------------------------------------------------------------------------- EWC

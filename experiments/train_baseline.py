@@ -13,7 +13,7 @@ import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
 from _common import compute_psnr, make_optimizer, pick_device, shard
-from nerve_cl import ops, parallel
+from nerve_cl import metrics, ops, parallel
 from nerve_cl.models import SuperResolutionNet
 
 
@@ -45,7 +45,8 @@ def train(args) -> None:
     say(f"  Parameters: {sum(p.numel() for p in model.parameters()):,}")
     optimizer = make_optimizer(torch.optim.AdamW, model.parameters(), lr=args.lr, weight_decay=1e-5)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=args.epochs)
-    criterion = ops.MSELoss()       # nn.MSELoss() of the reference, as libnvq kernels
+    # nn.MSELoss() of the reference, as libnvq kernels; --loss picks another libnvq loss
+    criterion = ops.MSELoss() if args.loss == "mse" else ops.LOSSES[args.loss]
 
     say(f"\nTraining for {args.epochs} epochs...")
     say("-" * 60)
@@ -64,20 +65,28 @@ def train(args) -> None:
 
         model.eval()
         val_loss = val_psnr = 0.0
+        meter = metrics.QualityMeter() if args.metrics else None
         with torch.no_grad():
             for lr, hr in val_loader:
                 lr, hr = lr.to(device), hr.to(device)
                 out = model(as_clip(lr))
                 val_loss += criterion(out, hr).item()
                 val_psnr += compute_psnr(out, hr)
+                if meter is not None:
+                    meter.update(out, hr)       # device-side sums, no host synchronisation
         # rank-uniform validation numbers (each rank validated its shard): every rank must take the same branch below,
         # because the branch contains collectives
         val_loss, val_psnr, nval = parallel.allreduce_scalars([val_loss, val_psnr, len(val_loader)], device=device)
         val_loss /= max(nval, 1)
         val_psnr /= max(nval, 1)
         scheduler.step()
+        extra = ""
+        if meter is not None and nval > 0:
+            meter.all_reduce()
+            m = meter.compute()
+            extra = f"Val SSIM: {m['ssim_global']:.4f} | Val MAE: {m['mae']:.4f} | "
         say(f"Epoch {epoch + 1:3d}/{args.epochs} | Train Loss: {running:.4f} | Val Loss: {val_loss:.4f} | "
-            f"Val PSNR: {val_psnr:.2f} dB | Time: {time.time() - t_start:.1f}s")
+            f"Val PSNR: {val_psnr:.2f} dB | {extra}Time: {time.time() - t_start:.1f}s")
         if val_psnr > best_psnr:
             best_psnr = val_psnr
             if world > 1:
@@ -101,6 +110,10 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--sync-bn", action="store_true",
                     help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
+    ap.add_argument("--loss", choices=("mse", "l1", "charbonnier", "ssim"), default="mse",
+                    help="training and validation loss (libnvq kernels; default: the reference's MSE)")
+    ap.add_argument("--metrics", action="store_true",
+                    help="add the global-statistics SSIM and the MAE of the validation set to the progress line")
     args = ap.parse_args()
     Path("checkpoints").mkdir(exist_ok=True)
     train(args)

@@ -19,7 +19,7 @@ import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
 from _common import make_optimizer, pick_device, shard
-from nerve_cl import ops, parallel
+from nerve_cl import metrics, ops, parallel
 from nerve_cl.continual import EWC, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 
@@ -52,12 +52,28 @@ def configure_precision(model: EnhancementEngine, precision: str, graphs: str) -
     sr.use_hip_graphs = {"auto": "auto", "on": True, "off": False}[graphs]
 
 
+def make_criterion(config):
+    """nn.MSELoss() of the reference as libnvq kernels, or the libnvq loss that --loss names"""
+    name = config.get("loss", "mse")
+    return ops.MSELoss() if name == "mse" else ops.LOSSES[name]
+
+
+def metrics_suffix(meter, world: int = 1) -> str:
+    """' SSIM=... MAE=...' of the epoch's (detached) outputs against their targets; '' without --metrics"""
+    if meter is None:
+        return ""
+    if world > 1:
+        meter.all_reduce()
+    m = meter.compute()
+    return f" SSIM={m['ssim_global']:.4f} MAE={m['mae']:.4f}"
+
+
 def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
     device = next(model.parameters()).device
     adapter = _ClipAdapter(model)
     ewc = EWC(adapter, ewc_lambda=config.get("ewc_lambda", 5000))
     optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
-    criterion = ops.MSELoss()       # nn.MSELoss() of the reference, as libnvq kernels
+    criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
@@ -66,6 +82,7 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
         for epoch in range(epochs):
             model.train()
             total = 0.0
+            meter = metrics.QualityMeter() if config.get("metrics") else None
             for lr_b, hr_b in loader:
                 lr_b, hr_b = lr_b.to(device), hr_b.to(device)
                 optimizer.zero_grad()
@@ -74,9 +91,11 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
                 loss.backward()
                 optimizer.step()
                 total += loss.item()
+                if meter is not None:
+                    meter.update(out, hr_b)
             if world > 1:                          # the printed loss is the mean over all ranks' batches (rank-uniform call)
                 total = parallel.allreduce_scalars([total], device=device)[0] / world
-            say(f"  Epoch {epoch + 1}: Loss={total / len(loader):.4f}")
+            say(f"  Epoch {epoch + 1}: Loss={total / len(loader):.4f}{metrics_suffix(meter, world)}")
         ewc.register_task(task_id, loader)
         say(f"  Registered task {task_id} for EWC protection")
     return model
@@ -85,7 +104,7 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
 def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
     device = next(model.parameters()).device
     optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
-    criterion = ops.MSELoss()       # nn.MSELoss() of the reference, as libnvq kernels
+    criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
@@ -101,7 +120,11 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
             loss = criterion(out, hr_b)
             loss.backward()
             optimizer.step()
-            say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f}")
+            meter = None
+            if config.get("metrics"):
+                meter = metrics.QualityMeter()
+                meter.update(out, hr_b)
+            say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f}{metrics_suffix(meter)}")
         for i in range(min(50, len(lr))):
             memory.store(lr[i], hr[i], metadata={"content_type": task_name})
         say(f"  Memory size: {len(memory)}")
@@ -124,6 +147,10 @@ def main() -> None:
                     help="HIP-graph replay of the training step (auto: for launch-bound frame sizes only)")
     ap.add_argument("--sync-bn", action="store_true",
                     help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
+    ap.add_argument("--loss", choices=("mse", "l1", "charbonnier", "ssim"), default="mse",
+                    help="data term of the training loss (libnvq kernels; default: the reference's MSE)")
+    ap.add_argument("--metrics", action="store_true",
+                    help="add the global-statistics SSIM and the MAE of each epoch's outputs to its progress line")
     args = ap.parse_args()
 
     device, rank, world = pick_device()
@@ -135,7 +162,7 @@ def main() -> None:
     if world > 1:
         model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
-    config = {"ewc_lambda": args.ewc_lambda}
+    config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics}
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs)
     elif args.strategy == "replay":

@@ -536,6 +536,35 @@ int nvq_mse_forward(const float* a, const float* b, long n, float* out, float* w
 int nvq_mse_backward(const float* a, const float* b, long n, const float* grad_out_dev, float* da,
                      void* stream);
 
+/* ------------------------------------------------------------------ quality metrics and losses (csrc/quality.hip)
+ * x = prediction, y = target: contiguous fp32, 16-byte aligned.  No float atomics: every entry point is deterministic. */
+#define NVQ_LOSS_L1 0          /* |x - y|;                  slope sign(x - y), sign(0) = 0 */
+#define NVQ_LOSS_CHARBONNIER 1 /* sqrt((x - y)^2 + eps^2);  slope (x - y) / sqrt((x - y)^2 + eps^2) */
+#define NVQ_LOSS_MSE 2         /* (x - y)^2;                slope 2 (x - y) */
+/* One pass over both tensors.  out (double [B][8], device): per sample n, sum x, sum y, sum x^2, sum y^2, sum xy,
+ * sum |x - y|, sum (x - y)^2 over its `per` elements.  workspace >= B * min(1024, ceil(per / 4096)) * 28 bytes. */
+int nvq_quality_sums(const float* x, const float* y, int B, long per, double* out, float* workspace,
+                     size_t workspace_bytes, void* stream);
+/* out[g] = mean over group g's `per` elements of the NVQ_LOSS_* `kind` (groups = 1: the whole tensor; groups = B: one
+ * value per sample).  eps: Charbonnier only.  workspace >= groups * 8 KiB. */
+int nvq_pixel_loss_forward(const float* x, const float* y, int groups, long per, int kind, float eps, float* out,
+                           float* workspace, size_t workspace_bytes, void* stream);
+/* dx = grad_out_dev[g] * slope(x - y) / per  (grad_out_dev: `groups` device floats, NULL for 1) */
+int nvq_pixel_loss_backward(const float* x, const float* y, int groups, long per, int kind, float eps,
+                            const float* grad_out_dev, float* dx, void* stream);
+/* Windowed SSIM of [B][C][H][W] planes, H, W >= 11: per channel an 11 x 11 Gaussian window (sigma 1.5, separable, taps
+ * normalised in fp32), valid positions only, biased local statistics, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ * the map is averaged over the valid positions and channels of a sample (per_sample != 0: out[B]) or of the whole batch
+ * (out[1]); as_loss != 0 writes 1 - that mean.  Neither the map nor any moment reaches memory.
+ * workspace >= B * C * ceil((H - 10) / 32) * ceil((W - 10) / 64) * 4 bytes. */
+int nvq_ssim_forward(const float* x, const float* y, int B, int C, int H, int W, float data_range, int per_sample,
+                     int as_loss, float* out, float* workspace, size_t workspace_bytes, void* stream);
+/* dx = scale * grad_out_dev[b] * d(mean SSIM of sample b) / dx  (grad_per_sample != 0: B device floats), or
+ * dx = scale * grad_out_dev[0] * d(mean SSIM of the batch) / dx  (grad_per_sample == 0); NULL grad_out_dev reads as 1.
+ * Recomputes the moments per tile (nothing is saved by the forward); gather form, fixed tap order. */
+int nvq_ssim_backward(const float* x, const float* y, int B, int C, int H, int W, float data_range,
+                      const float* grad_out_dev, int grad_per_sample, float scale, float* dx, void* stream);
+
 /* ------------------------------------------------------------------ FrameRecoveryNet layers (csrc/fr_ops.hip)
  * Generic NHWC kernels for reference nerve_cl/models/frame_recovery.py:23-446 (+ efficient_layers.py:109-151,
  * 231-294).  Tensors are [N,H,W,ld], logical channel count C <= ld, ld % 4 == 0, channels [C, ld) kept 0; fp32, or -

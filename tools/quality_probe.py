@@ -1,0 +1,123 @@
+"""Time the quality kernels (csrc/quality.hip) at 8 x 3 x 1080 x 1920 fp32 against the torch-op composition of the same
+formulas, which is what a user of the package would otherwise run.
+usage: python tools/quality_probe.py [--mode time|kernels|ssim] [--iters 10] [--rounds 3]
+  time    : fused and composed forms alternated, device events around `iters` calls, `rounds` rounds; prints a table with the
+            algorithmic bytes and the share of the 8 TB/s HBM peak
+  kernels : a few calls of every fused op and nothing else, for `rocprofv3 --kernel-trace --stats`
+  ssim    : the SSIM forward and backward alone, for a `rocprofv3 --pmc` run of their own"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
+                                "continual-learning-for-dynamic-video-quality-enhancement_amd"))
+from nerve_cl import metrics, ops  # noqa: E402
+
+B, C, H, W = 8, 3, 1080, 1920
+N = B * C * H * W
+HBM_PEAK = 8e12
+
+
+def gauss(dev):
+    d = torch.arange(11, dtype=torch.float32, device=dev) - 5
+    g = torch.exp(-(d * d) / (2 * 1.5 * 1.5))
+    return g / g.sum()
+
+
+def torch_ssim(x, y, g):
+    """1 - windowed SSIM with stock ops: five separable valid convolutions per image and the element-wise map"""
+    def blur(t):
+        t = t.reshape(B * C, 1, H, W)
+        return F.conv2d(F.conv2d(t, g.view(1, 1, 1, 11)), g.view(1, 1, 11, 1))
+    mx, my = blur(x), blur(y)
+    sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
+    m = ((2 * mx * my + 1e-4) * (2 * sxy + 9e-4)) / ((mx * mx + my * my + 1e-4) * (sxx + syy + 9e-4))
+    return 1 - m.mean()
+
+
+def torch_sums(x, y):
+    xf, yf = x.flatten(1), y.flatten(1)
+    d = xf - yf
+    return torch.stack([xf.sum(1), yf.sum(1), (xf * xf).sum(1), (yf * yf).sum(1), (xf * yf).sum(1), d.abs().sum(1), (d * d).sum(1)], 1)
+
+
+def rows(x, y, g):
+    """name -> (fused callable, composed callable, algorithmic bytes of the fused form); `+bwd` rows run forward and backward"""
+    xr = x.clone().requires_grad_(True)
+
+    def fb(fn):
+        def run():
+            xr.grad = None
+            fn(xr, y).backward()
+        return run
+
+    eps = 1e-3
+    t_l1, t_ch = F.l1_loss, (lambda a, b: torch.sqrt((a - b) ** 2 + eps * eps).mean())
+    t_ms = lambda a, b: ((a - b) ** 2).flatten(1).mean(1)          # noqa: E731
+    f_ms = lambda a, b: ops.mse_loss(a, b, reduction="none")        # noqa: E731
+    r = {
+        "quality_sums": (lambda: metrics.quality_sums(x, y), lambda: torch_sums(x, y), 8 * N),
+        "l1 fwd": (lambda: ops.l1_loss(x, y), lambda: t_l1(x, y), 8 * N),
+        "l1 fwd+bwd": (fb(ops.l1_loss), fb(t_l1), 20 * N),
+        "charbonnier fwd": (lambda: ops.charbonnier_loss(x, y), lambda: t_ch(x, y), 8 * N),
+        "charbonnier fwd+bwd": (fb(ops.charbonnier_loss), fb(t_ch), 20 * N),
+        "mse per-sample fwd": (lambda: f_ms(x, y), lambda: t_ms(x, y), 8 * N),
+        "mse per-sample fwd+bwd": (fb(lambda a, b: f_ms(a, b).sum()), fb(lambda a, b: t_ms(a, b).sum()), 20 * N),
+        "ssim fwd": (lambda: ops.ssim_loss(x, y), lambda: torch_ssim(x, y, g), 8 * N),
+        "ssim fwd+bwd": (fb(ops.ssim_loss), fb(lambda a, b: torch_ssim(a, b, g)), 20 * N),
+    }
+    return r
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters * 1e3      # us per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["time", "kernels", "ssim"], default="time")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "the probe times the MI355X"
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    y = torch.rand(B, C, H, W, device=dev, generator=gen)
+    x = (y + 0.05 * torch.randn(B, C, H, W, device=dev, generator=gen)).clamp(0, 1)
+    g = gauss(dev)
+    table = rows(x, y, g)
+    if args.mode != "time":
+        for name, (fused, _, _) in table.items():
+            if args.mode == "ssim" and not name.startswith("ssim"):
+                continue
+            for _ in range(3):
+                fused()
+        torch.cuda.synchronize()
+        return
+    print(f"{B} x {C} x {H} x {W} fp32, {args.iters} calls per timing, {args.rounds} alternated rounds (us per call)")
+    for name, (fused, composed, nbytes) in table.items():
+        for _ in range(2):
+            fused()
+            composed()
+        torch.cuda.synchronize()
+        tf, tc = [], []
+        for _ in range(args.rounds):
+            tf.append(timed(fused, args.iters))
+            tc.append(timed(composed, args.iters))
+        bf, bc = min(tf), min(tc)
+        print(f"{name:24s} fused {' '.join(f'{t:9.1f}' for t in tf)} | torch ops {' '.join(f'{t:9.1f}' for t in tc)} | "
+              f"ratio {bc / bf:6.2f}x | {nbytes / 1e6:7.1f} MB -> {nbytes / bf / 1e6:5.2f} TB/s = "
+              f"{nbytes / (bf * 1e-6) / HBM_PEAK:4.2f} of peak", flush=True)
+
+
+if __name__ == "__main__":
+    main()
