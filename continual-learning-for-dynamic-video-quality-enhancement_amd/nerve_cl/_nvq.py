@@ -213,6 +213,12 @@ SIGNATURES = {
     "nvq_fisher_accumulate": (ci, [vp, cl, vp, vp]),
     "nvq_si_update": (ci, [vp, vp, cl, vp, vp, vp]),
     "nvq_si_consolidate": (ci, [vp, cl, cf, vp, vp, vp, vp]),
+    # device-resident episodic memory (csrc/replay.hip)
+    "nvq_replay_store": (ci, [vp, vp, ci, cl, cl, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
+    "nvq_replay_gather": (ci, [vp, vp, ci, ci, cl, cl, vp, ci, vp, vp, ci, vp, vp]),
+    "nvq_replay_sample_weighted": (ci, [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp, vp]),
+    "nvq_replay_update_importance": (ci, [vp, ci, vp, vp, ci, cf, vp]),
+    "nvq_replay_nearest": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
 }
 
 
@@ -1202,3 +1208,75 @@ def si_consolidate(theta, damping: float, p_old, W, omega):
 
 def fisher_accumulate(grad, fisher):
     check(lib().nvq_fisher_accumulate(ptr(grad), grad.numel(), ptr(fisher), stream()), "nvq_fisher_accumulate")
+
+
+# ----------------------------------------------------------------------------- device-resident episodic memory
+REPLAY_MEANS_ONLY = 1   # NVQ_REPLAY_MEANS_ONLY
+
+
+def require_replay_device(dev: torch.device) -> None:
+    """DeviceEpisodicMemory keeps its tables in HBM and moves samples with libnvq kernels only."""
+    if dev.type != "cuda":
+        raise RuntimeError(
+            f"DeviceEpisodicMemory on {dev}: the device-resident memory runs only as HIP kernels on an AMD GPU; there is "
+            "no CPU fallback (nerve_cl.continual.EpisodicMemory is the host-side store).")
+    lib()
+
+
+def replay_store(src_lr: torch.Tensor, src_hr: torch.Tensor, slots: torch.Tensor, imps: torch.Tensor, times: torch.Tensor,
+                 types: torch.Tensor, lr_store: torch.Tensor, hr_store: torch.Tensor, means: torch.Tensor,
+                 importance: torch.Tensor, time: torch.Tensor, access: torch.Tensor, type_id: torch.Tensor) -> None:
+    """src_lr / src_hr (n, ...) fp32 -> rows slots[j] of the (capacity, ...) fp32 or bf16 stores; the per-slot tables are
+    written by the same call (nvq_replay_store).  slots / times / types int32 (n,), imps fp32 (n,), all on the device."""
+    n, cap = src_lr.shape[0], lr_store.shape[0]
+    check(lib().nvq_replay_store(ptr(src_lr), ptr(src_hr), n, src_lr.numel() // n, src_hr.numel() // n, means.shape[1],
+                                 ptr(slots), ptr(imps), ptr(times), ptr(types), ptr(lr_store), ptr(hr_store),
+                                 is_bf16(lr_store), cap, ptr(means), ptr(importance), ptr(time), ptr(access), ptr(type_id), 0,
+                                 stream()), "nvq_replay_store")
+
+
+def replay_means(src_lr: torch.Tensor, out: torch.Tensor) -> None:
+    """out (n, C) = per-channel means of src_lr (n, C, ...): nvq_replay_store's mean pass alone, the same bits"""
+    n = src_lr.shape[0]
+    slots = torch.arange(n, dtype=torch.int32, device=src_lr.device)
+    check(lib().nvq_replay_store(ptr(src_lr), None, n, src_lr.numel() // n, 1, out.shape[1], ptr(slots), None, None, None,
+                                 None, None, 0, n, ptr(out), None, None, None, None, REPLAY_MEANS_ONLY, stream()),
+          "nvq_replay_store(means)")
+
+
+def replay_gather(lr_store: torch.Tensor, hr_store: torch.Tensor, idx: torch.Tensor, lr_batch: torch.Tensor,
+                  hr_batch: torch.Tensor, row0: int, access: torch.Tensor) -> None:
+    """rows [row0, row0 + k) of the fp32 batches = slots idx (int32 (k,), device) of the stores, one launch"""
+    k, cap = idx.numel(), lr_store.shape[0]
+    if row0 < 0 or row0 + k > lr_batch.shape[0] or lr_batch.shape[0] != hr_batch.shape[0]:
+        raise ValueError(f"replay_gather: rows [{row0}, {row0 + k}) outside a batch of {lr_batch.shape[0]}")
+    assert lr_batch.dtype == torch.float32 and hr_batch.dtype == torch.float32 and idx.dtype == torch.int32
+    assert lr_batch.shape[1:] == lr_store.shape[1:] and hr_batch.shape[1:] == hr_store.shape[1:]
+    check(lib().nvq_replay_gather(ptr(lr_store), ptr(hr_store), is_bf16(lr_store), cap, lr_store.numel() // cap,
+                                  hr_store.numel() // cap, ptr(idx), k, ptr(lr_batch), ptr(hr_batch), row0, ptr(access),
+                                  stream()), "nvq_replay_gather")
+
+
+def replay_sample_weighted(importance: torch.Tensor, time: torch.Tensor, type_id: torch.Tensor, now: int,
+                           recency_weight: float, type_filter: int, uniforms: torch.Tensor, out_idx: torch.Tensor) -> None:
+    """out_idx (k,) int32 = the k slots with the largest keys log(u_i) / w_i (nvq_replay_sample_weighted), -1 padded"""
+    assert uniforms.dtype == torch.float32 and uniforms.numel() == importance.numel() and out_idx.dtype == torch.int32
+    check(lib().nvq_replay_sample_weighted(ptr(importance), ptr(time), ptr(type_id), importance.numel(), now, recency_weight,
+                                           type_filter, ptr(uniforms), out_idx.numel(), ptr(out_idx), stream()),
+          "nvq_replay_sample_weighted")
+
+
+def replay_update_importance(importance: torch.Tensor, idx: torch.Tensor, values: torch.Tensor, momentum: float) -> None:
+    """importance[idx[j]] = momentum * importance[idx[j]] + (1 - momentum) * values[j]; non-finite values are skipped"""
+    assert idx.dtype == torch.int32 and values.dtype == torch.float32 and idx.numel() == values.numel()
+    check(lib().nvq_replay_update_importance(ptr(importance), importance.numel(), ptr(idx), ptr(values), idx.numel(), momentum,
+                                             stream()), "nvq_replay_update_importance")
+
+
+def replay_nearest(query: Optional[torch.Tensor], table: torch.Tensor, type_id: torch.Tensor, out: torch.Tensor) -> None:
+    """out (2,) int32 = [slot, bits of the fp32 distance]: the non-empty slot whose table row is nearest to `query`, or
+    (query None, table (capacity,)) whose table value is smallest"""
+    assert out.dtype == torch.int32 and out.numel() == 2
+    cap = type_id.numel()
+    check(lib().nvq_replay_nearest(ptr(query), ptr(table), ptr(type_id), cap, table.numel() // cap, ptr(out), ptr(out, 1),
+                                   stream()), "nvq_replay_nearest")

@@ -9,7 +9,9 @@ returns ``['enhanced']``, so the Fisher / penalty actually run; everything up to
 reference prints.  ``--tasks`` / ``--samples`` / ``--epochs`` are additions (defaults = the reference's values), and so are
 ``--precision`` / ``--graphs``: 64x64 clips are launch-bound on an MI355X, so the script runs the network
 in its throughput mode by default - bf16 MFMA operands with fp32 accumulation and, for such small frames, HIP-graph replay of the
-step (``net.use_hip_graphs = "auto"``); ``--precision fp32 --graphs off`` is the exact-fp32 parity mode the package defaults to."""
+step (``net.use_hip_graphs = "auto"``); ``--precision fp32 --graphs off`` is the exact-fp32 parity mode the package defaults to.
+``--device-memory`` (with ``--memory-storage`` / ``--prioritized``) keeps the replay memory in HBM (DeviceEpisodicMemory, DESIGN.md
+section 16); without it the replay strategy runs the host-side EpisodicMemory and prints what it always printed."""
 import argparse
 from pathlib import Path
 
@@ -20,7 +22,7 @@ from torch.utils.data import DataLoader, TensorDataset
 
 from _common import make_optimizer, pick_device, shard
 from nerve_cl import metrics, ops, parallel
-from nerve_cl.continual import EWC, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
+from nerve_cl.continual import EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 
 OFFSETS = {"sports": 0.2, "animation": -0.2, "movie": 0.0, "news": 0.1}
@@ -105,6 +107,9 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
     device = next(model.parameters()).device
     optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
     criterion = make_criterion(config)
+    on_device = isinstance(memory, DeviceEpisodicMemory)
+    prioritized = bool(config.get("prioritized"))
+    per_sample = ops.LOSSES[config.get("loss", "mse")]             # reduction="none": one value per sample
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
@@ -112,12 +117,22 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
             model.train()
             idx = torch.randperm(len(lr))[:16]
             lr_b, hr_b = lr[idx].to(device), hr[idx].to(device)
+            n_cur, replayed = len(lr_b), None
             if len(memory) > 0:
-                r_lr, r_hr, _ = memory.sample(batch_size=8, device=device)
-                lr_b, hr_b = torch.cat([lr_b, r_lr]), torch.cat([hr_b, r_hr])
+                if on_device:                                       # one allocation, the replay rows gathered in place
+                    lr_b, hr_b, replayed = memory.replay_batch(lr_b, hr_b, 8, weighted=prioritized)
+                else:
+                    r_lr, r_hr, _ = memory.sample(batch_size=8, device=device)
+                    lr_b, hr_b = torch.cat([lr_b, r_lr]), torch.cat([hr_b, r_hr])
             optimizer.zero_grad()
             out = model(lr_b.unsqueeze(1).expand(-1, 3, -1, -1, -1))["enhanced"]
-            loss = criterion(out, hr_b)
+            if prioritized:
+                values = per_sample(out, hr_b, reduction="none")
+                loss = values.mean()
+                if replayed is not None:                            # the replay rows' losses become their slots' importances
+                    memory.update_importance(replayed, values.detach()[n_cur:], momentum=0.9)
+            else:
+                loss = criterion(out, hr_b)
             loss.backward()
             optimizer.step()
             meter = None
@@ -125,8 +140,12 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
                 meter = metrics.QualityMeter()
                 meter.update(out, hr_b)
             say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f}{metrics_suffix(meter)}")
-        for i in range(min(50, len(lr))):
-            memory.store(lr[i], hr[i], metadata={"content_type": task_name})
+        n_store = min(50, len(lr))
+        if on_device:
+            memory.store_batch(lr[:n_store], hr[:n_store], content_type=task_name)
+        else:
+            for i in range(n_store):
+                memory.store(lr[i], hr[i], metadata={"content_type": task_name})
         say(f"  Memory size: {len(memory)}")
     return model
 
@@ -151,7 +170,15 @@ def main() -> None:
                     help="data term of the training loss (libnvq kernels; default: the reference's MSE)")
     ap.add_argument("--metrics", action="store_true",
                     help="add the global-statistics SSIM and the MAE of each epoch's outputs to its progress line")
+    ap.add_argument("--device-memory", action="store_true",
+                    help="replay strategy: keep the memory in HBM (DeviceEpisodicMemory): batched stores, replay rows gathered behind the task batch by one launch")
+    ap.add_argument("--memory-storage", choices=("fp32", "bf16"), default="fp32",
+                    help="with --device-memory: element type of the stored samples (bf16 halves the footprint)")
+    ap.add_argument("--prioritized", action="store_true",
+                    help="with --device-memory: per-sample losses of the replay rows update their importances (momentum 0.9) and replay draws are weighted by them")
     args = ap.parse_args()
+    if args.prioritized and not args.device_memory:
+        ap.error("--prioritized needs --device-memory")
 
     device, rank, world = pick_device()
     torch.manual_seed(0)
@@ -162,11 +189,15 @@ def main() -> None:
     if world > 1:
         model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
-    config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics}
+    config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized}
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs)
     elif args.strategy == "replay":
-        memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
+        if args.device_memory:
+            memory = DeviceEpisodicMemory(capacity=args.memory_size, strategy="stratified", device=device,
+                                          storage=args.memory_storage)
+        else:
+            memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
         model = train_with_replay(model, tasks, memory, config, rank, args.epochs)
     # ('maml' has no branch in the reference either: it saves the untrained model)
     if rank == 0:

@@ -723,6 +723,39 @@ int nvq_fisher_accumulate(const float* grad, long n, float* fisher, void* stream
 int nvq_si_update(const float* theta, const float* grad, long n, float* p_old, float* W, void* stream);
 int nvq_si_consolidate(const float* theta, long n, float damping, float* p_old, float* W, float* omega, void* stream);
 
+/* ------------------------------------------------------------------ device-resident episodic memory (csrc/replay.hip)
+ * The memory is a set of caller-owned tables with `capacity` rows (capacity <= 65536): lr_store [capacity][lr_per] and
+ * hr_store [capacity][hr_per] (fp32, or bf16 when store_bf16), means [capacity][channels] fp32 (per-channel mean of the LR
+ * sample), importance fp32, time int32 (store counter), access_count int32, type_id int32 (< 0: the slot is empty).
+ * Slot indices come from device memory; a kernel skips an index outside [0, capacity).  No atomics, no workspace. */
+#define NVQ_REPLAY_MEANS_ONLY 1   /* nvq_replay_store flag: write only means[slots[j]] (the other tables may be NULL) */
+/* Sample j of src_lr [n][lr_per] / src_hr [n][hr_per] (fp32) goes to row slots[j] (distinct); bf16 storage rounds to
+ * nearest even (NaN -> 0x7fc0, subnormals kept).  Also: importance / time / type_id [slot] = sample_* [j], access_count
+ * [slot] = 0, and means[slot][c] = mean of LR plane c (second launch; double sums in a fixed order: reproducible bits). */
+int nvq_replay_store(const float* src_lr, const float* src_hr, int n, long lr_per, long hr_per, int channels,
+                     const int* slots, const float* sample_importance, const int* sample_time, const int* sample_type,
+                     void* lr_store, void* hr_store, int store_bf16, int capacity, float* means, float* importance,
+                     int* time, int* access_count, int* type_id, int flags, void* stream);
+/* Rows row0 + j of the fp32 batches = slot idx[j] (j < k, distinct), bf16 widened exactly; access_count[idx[j]] += 1.
+ * idx[j] < 0 (a weighted draw that found no eligible slot): that row is zero-filled.  One launch, grid (LR chunks + HR chunks, j). */
+int nvq_replay_gather(const void* lr_store, const void* hr_store, int store_bf16, int capacity, long lr_per, long hr_per,
+                      const int* idx, int k, float* lr_batch, float* hr_batch, int row0, int* access_count, void* stream);
+/* k <= 256 distinct slots with probability proportional to w_i = (1 - recency_weight) * importance_i + recency_weight /
+ * (1 + now - time_i), without replacement: the k largest keys log(uniforms[i]) / w_i (Efraimidis-Spirakis; uniforms
+ * [capacity] in (0, 1)) over the non-empty slots with w_i > 0 and, for type_filter >= 0, type_id == type_filter.  out_idx in
+ * draw order, ties to the lower index, -1 once no eligible slot is left.  One workgroup. */
+int nvq_replay_sample_weighted(const float* importance, const int* time, const int* type_id, int capacity, int now,
+                               float recency_weight, int type_filter, const float* uniforms, int k, int* out_idx,
+                               void* stream);
+/* importance[idx[j]] = momentum * importance[idx[j]] + (1 - momentum) * value[j] (two rounded products, one rounded sum);
+ * a non-finite value[j] or an idx[j] outside [0, capacity) is skipped.  idx distinct. */
+int nvq_replay_update_importance(float* importance, int capacity, const int* idx, const float* value, int k, float momentum,
+                                 void* stream);
+/* The non-empty slot whose table row [channels] is nearest to query [channels] (Euclidean; lowest index on ties) and that
+ * distance; query NULL (channels = 1): the slot with the smallest table value and that value.  No slot: -1, +inf. */
+int nvq_replay_nearest(const float* query, const float* table, const int* type_id, int capacity, int channels, int* out_idx,
+                       float* out_dist, void* stream);
+
 /* ---- Synchronised BatchNorm (nn.SyncBatchNorm in data-parallel training): every statistics reduction above ends in a
  * finalize step that turns per-block partials into fp64 sums.  These entry points split it at that seam: REDUCE leaves the
  * sums in a caller buffer (fp64), the caller all-reduces that buffer over the ranks, FINISH takes the global sums and reads
