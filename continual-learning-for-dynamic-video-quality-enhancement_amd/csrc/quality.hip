@@ -11,6 +11,9 @@
 // moments of every position to a functor: the forward sums the SSIM map value (never stored), the backward turns them into
 // the map's derivatives A, B, C with respect to mu_x, E[x^2], E[xy], keeps those in LDS and applies the adjoint filter in
 // gather form (one owner thread per dx element, fixed tap order): dx = G^T[A] + 2 x G^T[B] + y G^T[C].
+//
+// Multi-scale SSIM: the same two kernels per scale of a 2 x 2 mean pyramid with a contrast-structure
+// functor, one launch that pools x and y together, and a finalize that forms the clamped weighted product and its derivatives.
 #include "common.h"
 
 namespace nvq {
@@ -192,9 +195,12 @@ struct TileGeom {
 // xy: XY_FLOATS of LDS, hp: HP_FLOATS of LDS.  emit(mr, mc, mu_x, mu_y, E[x^2], E[y^2], E[xy]) runs once per position.
 // xy is dead once the vertical pass starts (emit may overwrite it); hp is still being read when this returns:
 // synchronise before reusing it.
-template <class G, int RV, class Emit>
+// CENTRE (the multi-scale kernels): the moments are those of x - centre and y - centre.  Variances and the covariance do not
+// depend on the centre, and with it at mid-range E[x^2] - mu^2 no longer cancels; the caller adds it back to the means.
+template <class G, int RV, bool CENTRE = false, class Emit>
 __device__ __forceinline__ void moments_tile(const float* __restrict__ xp, const float* __restrict__ yp, int H, int W,
-                                             int r0, int c0, bool vec, const Taps& t, float* xy, float* hp, Emit emit) {
+                                             int r0, int c0, bool vec, const Taps& t, float* xy, float* hp, Emit emit,
+                                             float centre = 0.f) {
     constexpr int MH = G::MH, MW = G::MW, IH = G::IH, IW = G::IW;
     float* xs = xy;
     float* ys = xy + IH * IW;
@@ -213,6 +219,10 @@ __device__ __forceinline__ void moments_tile(const float* __restrict__ xp, const
                 if (gc + 1 >= 0 && gc + 1 < W) { u.y = xp[o + 1]; v.y = yp[o + 1]; }
                 if (gc + 2 >= 0 && gc + 2 < W) { u.z = xp[o + 2]; v.z = yp[o + 2]; }
                 if (gc + 3 >= 0 && gc + 3 < W) { u.w = xp[o + 3]; v.w = yp[o + 3]; }
+            }
+            if (CENTRE) {   // columns outside the plane become -centre: only masked positions read them
+                u = make_float4(u.x - centre, u.y - centre, u.z - centre, u.w - centre);
+                v = make_float4(v.x - centre, v.y - centre, v.z - centre, v.w - centre);
             }
         }
         st4(xs + row * IW + col, u);
@@ -401,6 +411,269 @@ __global__ __launch_bounds__(256) void ssim_backward_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ multi-scale SSIM
+// Scale j of the pyramid (x_1 = x, x_{j+1} = 2 x 2 mean of x_j) contributes the plane mean of cs = (2 s_xy + C2) / (s_xx + s_yy
+// + C2) (j < M) or of the SSIM map l * cs (j = M).  The kernels below are the SSIM pair with that functor, a per-plane upstream
+// factor and the pooling adjoint folded into the backward's store.  They take their moments about the centre 0.5 L (see
+// moments_tile): a coarse scale has few positions, down to a single one, so the cancellation error of E[x^2] - mu^2 is not
+// averaged away there as it is over a full-size plane, and the weights put most of the product on those scales.
+
+constexpr int kMaxScales = 8;
+
+// tiles of one plane of every scale's forward pass, where its partials start in the workspace, 1 / valid positions
+struct ScaleGeom {
+    int tpp[kMaxScales];
+    long off[kMaxScales];
+    double inv_count[kMaxScales];
+    long total;
+};
+
+ScaleGeom scale_geom(int planes, int H, int W, int scales) {
+    ScaleGeom g;
+    long off = 0;
+    for (int j = 0; j < kMaxScales; ++j) {
+        const int h = H >> j, w = W >> j;
+        const bool on = j < scales && h >= kTaps && w >= kTaps;
+        g.tpp[j] = on ? ceil_div(h - kHalo, 32) * ceil_div(w - kHalo, 64) : 0;
+        g.off[j] = off;
+        g.inv_count[j] = on ? 1.0 / ((double)(h - kHalo) * (double)(w - kHalo)) : 0.0;
+        off += (long)planes * g.tpp[j];
+    }
+    g.total = off;
+    return g;
+}
+
+// PyTorch's avg_pool2d order: ((a + b) + c) + d over the window's rows, then / 4
+__device__ __forceinline__ float pool4(float a, float b, float c, float d) { return (((a + b) + c) + d) * 0.25f; }
+
+// 2 x 2 mean, stride 2, of the H x W planes of x and y in one launch (an odd last row or column is dropped).  Workgroup
+// blockIdx.x covers a strided share of plane blockIdx.x / nbp: it never straddles two planes.  VEC (W % 4 == 0): an item is
+// two neighbouring outputs from two 16-byte loads per tensor.
+template <bool VEC>
+__global__ __launch_bounds__(256) void avgpool2_pair_kernel(const float* __restrict__ x, const float* __restrict__ y, int H,
+                                                            int W, int nbp, float* __restrict__ px, float* __restrict__ py) {
+    const int plane = blockIdx.x / nbp, blk = blockIdx.x % nbp;
+    const int OH = H >> 1, OW = W >> 1;
+    const long pi = (long)plane * H * W, po = (long)plane * OH * OW;
+    const float* xs = x + pi;
+    const float* ys = y + pi;
+    float* pxs = px + po;
+    float* pys = py + po;
+    if (VEC) {
+        const int hw = OW >> 1, n2 = OH * hw;
+        for (int i = blk * 256 + threadIdx.x; i < n2; i += nbp * 256) {
+            const int r = i / hw, c = i % hw;
+            const long o = (long)(2 * r) * W + 4 * c;
+            const float4 a = ld4(xs + o), b = ld4(xs + o + W), u = ld4(ys + o), v = ld4(ys + o + W);
+            const long e = (long)r * OW + 2 * c;
+            *reinterpret_cast<float2*>(pxs + e) = make_float2(pool4(a.x, a.y, b.x, b.y), pool4(a.z, a.w, b.z, b.w));
+            *reinterpret_cast<float2*>(pys + e) = make_float2(pool4(u.x, u.y, v.x, v.y), pool4(u.z, u.w, v.z, v.w));
+        }
+    } else {
+        const int n = OH * OW;
+        for (int i = blk * 256 + threadIdx.x; i < n; i += nbp * 256) {
+            const int r = i / OW, c = i % OW;
+            const long o = (long)(2 * r) * W + 2 * c;
+            pxs[i] = pool4(xs[o], xs[o + 1], xs[o + W], xs[o + W + 1]);
+            pys[i] = pool4(ys[o], ys[o + 1], ys[o + W], ys[o + W + 1]);
+        }
+    }
+}
+
+// ssim_forward_kernel on centred moments: part[tile] = sum over the tile's valid positions of cs (CS) or of l * cs
+template <bool CS>
+__global__ __launch_bounds__(256) void msssim_forward_kernel(const float* __restrict__ x, const float* __restrict__ y, int H,
+                                                             int W, int tiles_x, int tiles_y, int vec, float c1, float c2,
+                                                             float centre, Taps t, float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float xy[FwdGeom::XY_FLOATS];
+    __shared__ __attribute__((aligned(16))) float hp[FwdGeom::HP_FLOATS];
+    __shared__ float scratch[4];
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, plane = tile / (tiles_x * tiles_y);
+    const int r0 = ty * kFTH, c0 = tx * kFTW, OH = H - kHalo, OW = W - kHalo;
+    const long po = (long)plane * H * W;
+    float s = 0.f;
+    moments_tile<FwdGeom, 8, true>(x + po, y + po, H, W, r0, c0, vec != 0, t, xy, hp,
+                                   [&](int mr, int mc, float mx, float my, float exx, float eyy, float exy) {
+                                       const float sxy = exy - mx * my, s2 = (exx - mx * mx) + (eyy - my * my);
+                                       float v;
+                                       if (CS) {
+                                           v = (2.f * sxy + c2) / (s2 + c2);
+                                       } else {
+                                           const float ux = mx + centre, uy = my + centre;
+                                           const float mxy = ux * uy, m2 = ux * ux + uy * uy;
+                                           v = ((2.f * mxy + c1) * (2.f * sxy + c2)) / ((m2 + c1) * (s2 + c2));
+                                       }
+                                       if (r0 + mr < OH && c0 + mc < OW) s += v;
+                                   },
+                                   centre);
+    s = block_sum_256(s, scratch);
+    if (threadIdx.x == 0) part[tile] = s;
+}
+
+// One workgroup of 16 waves; a wave owns whole samples (b = wave, wave + 16, ...).  Per plane and scale it adds the tile
+// partials in double (lane-strided, then a butterfly: a fixed order), lane j keeps m_j; the clamp, the powers, the product and
+// its derivatives are formed in double by lanes 0 .. M-1.  mt[j][plane] = m_j, dt[j][plane] = d ms(b) / d m_j(b, c) (0 where a
+// term is clamped: never 0 * inf).  out: (B,) or (1,), the value or 1 - value.
+__global__ __launch_bounds__(1024) void msssim_finalize_kernel(const float* __restrict__ part, ScaleGeom g, int M, int B, int C,
+                                                               const float* __restrict__ w, int per_sample, int as_loss,
+                                                               float* __restrict__ out, float* __restrict__ mt,
+                                                               float* __restrict__ dt) {
+    __shared__ double wave_sum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long planes = (long)B * C;
+    const double wj = lane < M ? (double)w[lane] : 0.0;
+    double acc = 0.0;
+    for (int b = wave; b < B; b += 16) {
+        double vs = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const long plane = (long)b * C + c;
+            double m = 1.0;
+            for (int j = 0; j < M; ++j) {
+                const int n = g.tpp[j];
+                const float* q = part + g.off[j] + plane * n;
+                double s = 0.0;
+                for (int k = lane; k < n; k += 64) s += (double)q[k];
+                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                if (lane == j) m = s * g.inv_count[j];
+            }
+            const double pw = lane < M ? (m > 0.0 ? pow(m, wj) : 0.0) : 1.0;
+            double v = 1.0, others = 1.0;
+            for (int k = 0; k < M; ++k) {
+                const double pk = __shfl(pw, k, 64);
+                v *= pk;
+                if (k != lane) others *= pk;
+            }
+            if (lane < M) {
+                mt[lane * planes + plane] = (float)m;
+                dt[lane * planes + plane] = m > 0.0 ? (float)(wj * (pw / m) * others / (double)C) : 0.f;
+            }
+            vs += v;
+        }
+        const double ms = vs / (double)C;
+        if (per_sample) {
+            if (lane == 0) out[b] = (float)(as_loss ? 1.0 - ms : ms);
+        } else {
+            acc += ms;
+        }
+    }
+    if (per_sample) return;
+    if (lane == 0) wave_sum[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < 16; ++k) s += wave_sum[k];
+        s /= (double)B;
+        out[0] = (float)(as_loss ? 1.0 - s : s);
+    }
+}
+
+// ssim_backward_kernel for one scale of the pyramid.  The upstream factor is per plane: scale * go[b or 0] * dplane[plane]
+// (dplane: this scale's row of the finalize's derivative table); CS selects the contrast-structure functor
+//   d cs / d mu_x = (2 mu_x cs - 2 mu_y) / b2,  d cs / d E[x^2] = -cs / b2,  d cs / d E[xy] = 2 / b2,  b2 = s_xx + s_yy + C2
+// and the store adds the pooling adjoint of the next coarser scale's gradient dxc (HC x WC planes, may be NULL):
+// dx[r][c] = own + 0.25 dxc[r / 2][c / 2] wherever that element exists.  The moments are centred: the derivatives are those
+// with respect to x - centre, which are those with respect to x; only the luminance term sees the uncentred means.
+template <bool CS>
+__global__ __launch_bounds__(256) void msssim_backward_kernel(const float* __restrict__ x, const float* __restrict__ y, int C,
+                                                              int H, int W, int tiles_x, int tiles_y, int vec, float c1, float c2,
+                                                              float centre, Taps t, const float* __restrict__ dplane,
+                                                              const float* __restrict__ go, int go_per_sample, float scale,
+                                                              const float* __restrict__ dxc, int HC, int WC,
+                                                              float* __restrict__ dx) {
+    constexpr int MH = BwdGeom::MH, MW = BwdGeom::MW;
+    __shared__ __attribute__((aligned(16))) float r1[kBwdR1];               // staged x, y; then A, B, C
+    __shared__ __attribute__((aligned(16))) float r2[BwdGeom::HP_FLOATS];   // horizontal pass; then that of the adjoint
+    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, plane = tile / (tiles_x * tiles_y);
+    const int r0 = ty * kBTH - kHalo, c0 = tx * kBTW - kBLead, OH = H - kHalo, OW = W - kHalo;
+    const long po = (long)plane * H * W;
+    const float sc = scale * (go ? go[go_per_sample ? plane / C : 0] : 1.f) * dplane[plane];
+
+    moments_tile<BwdGeom, 9, true>(x + po, y + po, H, W, r0, c0, vec != 0, t, r1, r2,
+                                   [&](int mr, int mc, float mx, float my, float exx, float eyy, float exy) {
+                                       const int pr = r0 + mr, pc = c0 + mc;
+                                       float a = 0.f, b = 0.f, c = 0.f;
+                                       if (pr >= 0 && pr < OH && pc >= 0 && pc < OW) {
+                                           const float a2 = 2.f * (exy - mx * my) + c2;
+                                           const float b2 = (exx - mx * mx) + (eyy - my * my) + c2, ib2 = 1.f / b2;
+                                           if (CS) {
+                                               const float cs = a2 * ib2;
+                                               a = sc * (2.f * mx * cs - 2.f * my) * ib2;
+                                               b = -sc * cs * ib2;
+                                               c = sc * 2.f * ib2;
+                                           } else {
+                                               // l = a1 / b1 in the uncentred means ux, uy; cs = a2 / b2 in the centred ones
+                                               const float ux = mx + centre, uy = my + centre;
+                                               const float a1 = 2.f * ux * uy + c1, b1 = ux * ux + uy * uy + c1;
+                                               const float ib1 = 1.f / b1, ib = ib1 * ib2, S = a1 * a2 * ib;
+                                               a = sc * (2.f * (uy * a2 - my * a1) * ib + 2.f * S * (mx * ib2 - ux * ib1));
+                                               b = -sc * S * ib2;
+                                               c = sc * 2.f * a1 * ib;
+                                           }
+                                       }
+                                       r1[(0 * MH + mr) * MW + mc] = a;
+                                       r1[(1 * MH + mr) * MW + mc] = b;
+                                       r1[(2 * MH + mr) * MW + mc] = c;
+                                   },
+                                   centre);
+    __syncthreads();
+    // adjoint, horizontal: element column j gathers positions m = j + 2 .. j + 12 with tap (j + 12 - m)
+    for (int it = threadIdx.x; it < MH * (kBTW / 4); it += 256) {
+        const int row = it / (kBTW / 4), col = 4 * (it % (kBTW / 4));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            float a[16];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 u = ld4(r1 + (q * MH + row) * MW + col + 4 * k);
+                a[4 * k] = u.x; a[4 * k + 1] = u.y; a[4 * k + 2] = u.z; a[4 * k + 3] = u.w;
+            }
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < kTaps; ++k)
+#pragma unroll
+                for (int o = 0; o < 4; ++o) acc[o] = fmaf(t.g[k], a[o + kBLead - k], acc[o]);
+            st4(r2 + (q * MH + row) * kBTW + col, make_float4(acc[0], acc[1], acc[2], acc[3]));
+        }
+    }
+    __syncthreads();
+    // adjoint, vertical: element row i gathers position rows i .. i + 10 (tile-relative) with tap (i + 10 - row)
+    {
+        constexpr int RO = kBTH / 4;
+        const int col = threadIdx.x & 63, ib = (threadIdx.x >> 6) * RO;
+        float acc[RO][3];
+#pragma unroll
+        for (int o = 0; o < RO; ++o) acc[o][0] = acc[o][1] = acc[o][2] = 0.f;
+#pragma unroll
+        for (int r = 0; r < RO + kHalo; ++r) {
+            float v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) v[q] = r2[(q * MH + ib + r) * kBTW + col];
+#pragma unroll
+            for (int o = 0; o < RO; ++o) {
+                const int k = o + kHalo - r;
+                if (k >= 0 && k < kTaps) {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) acc[o][q] = fmaf(t.g[k], v[q], acc[o][q]);
+                }
+            }
+        }
+        const int gc = tx * kBTW + col;
+        const long pc = (long)plane * HC * WC;
+#pragma unroll
+        for (int o = 0; o < RO; ++o) {
+            const int gr = ty * kBTH + ib + o;
+            if (gr < H && gc < W) {
+                const long e = po + (long)gr * W + gc;
+                float d = acc[o][0] + 2.f * (x[e] - centre) * acc[o][1] + (y[e] - centre) * acc[o][2];
+                if (dxc && (gr >> 1) < HC && (gc >> 1) < WC) d += 0.25f * dxc[pc + (long)(gr >> 1) * WC + (gc >> 1)];
+                dx[e] = d;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 }  // namespace nvq
@@ -511,6 +784,99 @@ int nvq_ssim_backward(const float* x, const float* y, int B, int C, int H, int W
     hipLaunchKernelGGL(ssim_backward_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, tx, ty,
                        (int)((W & 3) == 0), c1, c2, gaussian_taps(), grad_out_dev, grad_per_sample, (float)(scale / count), dx);
     return check_launch("ssim_backward");
+}
+
+int nvq_avgpool2_pair(const float* x, const float* y, int planes, int H, int W, float* px, float* py, void* stream) {
+    NVQ_REQUIRE(planes > 0 && H >= 2 && W >= 2 && (long)H * W <= 0x7fffffffL && aligned16(x) && aligned16(y) && aligned16(px) &&
+                    aligned16(py),
+                "avgpool2_pair: planes > 0, H, W >= 2, H * W < 2^31, 16-byte aligned tensors");
+    const bool vec = (W & 3) == 0;
+    const long items = (long)(H >> 1) * (vec ? W >> 2 : W >> 1);
+    int nbp = ceil_div(items, 256L * 4);
+    if (nbp > 1024) nbp = 1024;
+    NVQ_REQUIRE((long)planes * nbp <= 0x7fffffffL, "avgpool2_pair: too many planes");
+    const dim3 grid((unsigned)(planes * nbp));
+    if (vec)
+        hipLaunchKernelGGL(avgpool2_pair_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, y, H, W, nbp, px, py);
+    else
+        hipLaunchKernelGGL(avgpool2_pair_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, y, H, W, nbp, px, py);
+    return check_launch("avgpool2_pair");
+}
+
+static int msssim_check(const char* what, long planes, int H, int W, int scales, int scale, float data_range) {
+    NVQ_REQUIRE(planes > 0 && planes <= 0x7fffffffL && scales >= 1 && scales <= kMaxScales && scale >= 0 && scale < scales &&
+                    data_range > 0.f,
+                "%s: planes > 0, 1 <= scales <= 8, 0 <= scale < scales, data_range > 0", what);
+    NVQ_REQUIRE(H > 0 && W > 0 && (H >> (scales - 1)) >= kTaps && (W >> (scales - 1)) >= kTaps,
+                "%s: the coarsest of %d scales of %d x %d holds no 11 x 11 window", what, scales, H, W);
+    return NVQ_OK;
+}
+
+size_t nvq_msssim_workspace_bytes(int planes, int H, int W, int scales) {
+    if (planes <= 0 || H <= 0 || W <= 0 || scales < 1 || scales > kMaxScales) return 0;
+    return (size_t)scale_geom(planes, H, W, scales).total * sizeof(float);
+}
+
+int nvq_msssim_scale_forward(const float* xs, const float* ys, int planes, int H, int W, int scales, int scale,
+                             float data_range, float* workspace, size_t workspace_bytes, void* stream) {
+    int rc = msssim_check("msssim_scale_forward", planes, H, W, scales, scale, data_range);
+    if (rc) return rc;
+    NVQ_REQUIRE(aligned16(xs) && aligned16(ys), "msssim_scale_forward: 16-byte aligned tensors");
+    const ScaleGeom g = scale_geom(planes, H, W, scales);
+    if ((size_t)g.total * sizeof(float) > workspace_bytes) { set_error("msssim_scale_forward: workspace"); return NVQ_EWORKSPACE; }
+    const int h = H >> scale, w = W >> scale;
+    const long tiles = (long)planes * g.tpp[scale];
+    NVQ_REQUIRE(tiles <= 0x7fffffffL, "msssim_scale_forward: too many tiles");
+    const int tx = ceil_div(w - kHalo, kFTW), ty = ceil_div(h - kHalo, kFTH);
+    const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
+    float* part = workspace + g.off[scale];
+    if (scale + 1 < scales)
+        hipLaunchKernelGGL(msssim_forward_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, xs, ys, h, w, tx,
+                           ty, (int)((w & 3) == 0), c1, c2, 0.5f * data_range, gaussian_taps(), part);
+    else
+        hipLaunchKernelGGL(msssim_forward_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, xs, ys, h, w, tx,
+                           ty, (int)((w & 3) == 0), c1, c2, 0.5f * data_range, gaussian_taps(), part);
+    return check_launch("msssim_scale_forward");
+}
+
+int nvq_msssim_finalize(const float* workspace, int B, int C, int H, int W, int scales, const float* weights, int per_sample,
+                        int as_loss, float* out, float* mtable, float* dtable, void* stream) {
+    NVQ_REQUIRE(B > 0 && C > 0, "msssim_finalize: B, C > 0");
+    int rc = msssim_check("msssim_finalize", (long)B * C, H, W, scales, 0, 1.f);
+    if (rc) return rc;
+    NVQ_REQUIRE(workspace && weights && out && mtable && dtable, "msssim_finalize: NULL argument");
+    hipLaunchKernelGGL(msssim_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, workspace,
+                       scale_geom(B * C, H, W, scales), scales, B, C, weights, per_sample, as_loss, out, mtable, dtable);
+    return check_launch("msssim_finalize");
+}
+
+int nvq_msssim_scale_backward(const float* xs, const float* ys, int B, int C, int H, int W, int scales, int scale,
+                              float data_range, const float* dtable, const float* grad_out_dev, int grad_per_sample,
+                              float sign, const float* dx_coarser, float* dx, void* stream) {
+    NVQ_REQUIRE(B > 0 && C > 0, "msssim_scale_backward: B, C > 0");
+    const long planes = (long)B * C;
+    int rc = msssim_check("msssim_scale_backward", planes, H, W, scales, scale, data_range);
+    if (rc) return rc;
+    NVQ_REQUIRE(aligned16(xs) && aligned16(ys) && aligned16(dx) && dtable, "msssim_scale_backward: 16-byte aligned tensors");
+    NVQ_REQUIRE(dx_coarser == nullptr || scale + 1 < scales, "msssim_scale_backward: the coarsest scale has no coarser gradient");
+    const int h = H >> scale, w = W >> scale;
+    const int tx = ceil_div(w, kBTW), ty = ceil_div(h, kBTH);
+    const long tiles = planes * tx * ty;
+    NVQ_REQUIRE(tiles <= 0x7fffffffL, "msssim_scale_backward: too many tiles");
+    const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
+    const double count = (double)(grad_per_sample ? 1 : B) * (double)(h - kHalo) * (double)(w - kHalo);
+    const float* dplane = dtable + (long)scale * planes;
+    const dim3 grid((unsigned)tiles);
+    hipStream_t s = (hipStream_t)stream;
+    if (scale + 1 < scales)
+        hipLaunchKernelGGL(msssim_backward_kernel<true>, grid, dim3(256), 0, s, xs, ys, C, h, w, tx, ty, (int)((w & 3) == 0), c1,
+                           c2, 0.5f * data_range, gaussian_taps(), dplane, grad_out_dev, grad_per_sample, (float)(sign / count), dx_coarser, h >> 1,
+                           w >> 1, dx);
+    else
+        hipLaunchKernelGGL(msssim_backward_kernel<false>, grid, dim3(256), 0, s, xs, ys, C, h, w, tx, ty, (int)((w & 3) == 0), c1,
+                           c2, 0.5f * data_range, gaussian_taps(), dplane, grad_out_dev, grad_per_sample, (float)(sign / count), dx_coarser, h >> 1,
+                           w >> 1, dx);
+    return check_launch("msssim_scale_backward");
 }
 
 }  // extern "C"

@@ -206,6 +206,11 @@ SIGNATURES = {
     "nvq_pixel_loss_backward": (ci, [vp, vp, ci, cl, ci, cf, vp, vp, vp]),
     "nvq_ssim_forward": (ci, [vp, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, sz, vp]),
     "nvq_ssim_backward": (ci, [vp, vp, ci, ci, ci, ci, cf, vp, ci, cf, vp, vp]),
+    "nvq_avgpool2_pair": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
+    "nvq_msssim_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "nvq_msssim_scale_forward": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+    "nvq_msssim_finalize": (ci, [vp, ci, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp]),
+    "nvq_msssim_scale_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, ci, cf, vp, vp, vp]),
     "nvq_axpy_slice": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, cl, cf, ci, ci, vp]),
     "nvq_colsum": (ci, [vp, ci, ci, ci, cl, cf, vp, vp, sz, ci, vp]),
     "nvq_ewc_penalty": (ci, [vp, vp, vp, cl, cf, vp, vp, sz, vp]),
@@ -1184,6 +1189,36 @@ def ssim_backward(x: torch.Tensor, y: torch.Tensor, data_range: float, go_dev: t
     B, Cc, H, W = x.shape
     check(lib().nvq_ssim_backward(ptr(x), ptr(y), B, Cc, H, W, data_range, ptr(go_dev), int(go_dev.numel() != 1 or B == 1),
                                   scale, ptr(dx), stream()), "nvq_ssim_backward")
+
+
+def avgpool2_pair(x: torch.Tensor, y: torch.Tensor, px: torch.Tensor, py: torch.Tensor):
+    """px, py (..., H // 2, W // 2) = the 2 x 2 means of x, y (..., H, W), both in one launch"""
+    H, W = x.shape[-2:]
+    check(lib().nvq_avgpool2_pair(ptr(x), ptr(y), x.numel() // (H * W), H, W, ptr(px), ptr(py), stream()), "nvq_avgpool2_pair")
+
+
+def msssim_scale_forward(xs: torch.Tensor, ys: torch.Tensor, H: int, W: int, scales: int, scale: int, data_range: float,
+                         ws: torch.Tensor):
+    """tile sums of scale `scale` of an M-scale pyramid whose finest planes are H x W; xs, ys: that scale's (B, C, h, w)"""
+    check(lib().nvq_msssim_scale_forward(ptr(xs), ptr(ys), xs.shape[0] * xs.shape[1], H, W, scales, scale, data_range, ptr(ws),
+                                         ws.numel() * 4, stream()), "nvq_msssim_scale_forward")
+
+
+def msssim_finalize(ws: torch.Tensor, B: int, Cc: int, H: int, W: int, weights: torch.Tensor, as_loss: bool, out: torch.Tensor,
+                    mtable: torch.Tensor, dtable: torch.Tensor):
+    """out (B,) per sample or (1,) over the batch; mtable, dtable (M, B * C); weights (M,) on the device"""
+    check(lib().nvq_msssim_finalize(ptr(ws), B, Cc, H, W, weights.numel(), ptr(weights), int(out.numel() != 1 or B == 1),
+                                    int(as_loss), ptr(out), ptr(mtable), ptr(dtable), stream()), "nvq_msssim_finalize")
+
+
+def msssim_scale_backward(xs: torch.Tensor, ys: torch.Tensor, H: int, W: int, scales: int, scale: int, data_range: float,
+                          dtable: torch.Tensor, go_dev: torch.Tensor, sign: float, dx_coarser: Optional[torch.Tensor],
+                          dx: torch.Tensor):
+    """dx = sign * go * d ms / d xs through m_scale, plus the pooling adjoint of dx_coarser; go_dev (B,) or (1,)"""
+    B, Cc = xs.shape[:2]
+    check(lib().nvq_msssim_scale_backward(ptr(xs), ptr(ys), B, Cc, H, W, scales, scale, data_range, ptr(dtable), ptr(go_dev),
+                                          int(go_dev.numel() != 1 or B == 1), sign, ptr(dx_coarser), ptr(dx), stream()),
+          "nvq_msssim_scale_backward")
 
 
 # ----------------------------------------------------------------------------- EWC

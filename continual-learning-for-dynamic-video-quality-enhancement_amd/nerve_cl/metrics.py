@@ -3,16 +3,16 @@
 ``quality_sums`` is ONE libnvq pass over a prediction and its target that leaves eight float64 numbers per sample on the
 device; ``mse``, ``mae``, ``psnr`` and ``ssim_global`` are pure functions of such sums, so they work on one row, on the sum
 of rows (sums add: a dataset's metric is the metric of its summed rows) and on CPU tensors alike.  ``ssim`` is the windowed
-SSIM of ``nerve_cl.ops.ssim_loss`` as a metric.  ``QualityMeter`` accumulates over an epoch without a host synchronisation.
+SSIM of ``nerve_cl.ops.ssim_loss`` as a metric, ``ms_ssim`` the multi-scale one.  ``QualityMeter`` accumulates over an epoch without a host synchronisation.
 No autograd here; HIP tensors only for everything that reads images (there is no CPU fallback).
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 
-from nerve_cl import _engine, _nvq
+from nerve_cl import _engine, _nvq, ops
 
 # columns of a sums row
 N, SX, SY, SXX, SYY, SXY, SABS, SSQ = range(8)
@@ -93,6 +93,16 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, redu
     with _nvq.device_guard(a.device):
         _nvq.ssim_forward(a, b, float(data_range), False, out, _engine.workspace(a.device))
     return out if reduction == "none" else out.reshape(())
+
+
+def ms_ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, weights: Optional[Sequence[float]] = None,
+            reduction: str = "mean") -> torch.Tensor:
+    """Multi-scale SSIM of (B, C, H, W) tensors, the forward of ``nerve_cl.ops.ms_ssim_loss`` as a metric (its definition and
+    arguments): ``"mean"``: a scalar over the batch, ``"none"``: (B,) per sample."""
+    per_sample = ops._check_reduction(reduction)
+    w, a, b = ops._ms_ssim_args("ms_ssim", pred, target, weights)
+    out, _, _ = ops._ms_ssim_forward(a, b, float(data_range), w, per_sample, False)
+    return out if per_sample else out.reshape(())
 
 
 class QualityMeter:

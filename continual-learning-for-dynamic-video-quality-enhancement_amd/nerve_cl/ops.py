@@ -9,8 +9,12 @@ HIP tensors only; there is no CPU fallback.
 with respect to the prediction only.  Every loss takes ``reduction="mean"`` (a scalar) or ``reduction="none"``, which here
 means PER SAMPLE: a ``(B,)`` tensor holding the mean over each sample's elements (what an importance-weighted replay
 needs), not one value per element.
+
+``ms_ssim_loss`` / ``MSSSIMLoss`` (multi-scale SSIM) and the ``ms_ssim_l1_loss`` mix follow the same rules.
 """
 from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -119,6 +123,123 @@ def _check_ssim_shape(name: str, x: torch.Tensor) -> None:
                            f"got {tuple(x.shape)}")
 
 
+# the five standard MS-SSIM scale weights (Wang, Simoncelli, Bovik 2003), finest scale first
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+_ms_weight_cache = {}
+
+
+def ms_ssim_weights(scales: int) -> Tuple[float, ...]:
+    """The first ``scales`` (1 to 5) standard weights divided by their sum (the published five sum to 1.0001, so
+    ``ms_ssim_weights(5)`` is the standard tuple to four digits)."""
+    if not 1 <= int(scales) <= len(MS_SSIM_WEIGHTS):
+        raise ValueError(f"ms_ssim_weights: scales must be 1 to {len(MS_SSIM_WEIGHTS)}, got {scales}")
+    head = MS_SSIM_WEIGHTS[:int(scales)]
+    return tuple(w / sum(head) for w in head)
+
+
+def ms_ssim_max_scales(H: int, W: int) -> int:
+    """The largest number of scales M <= 5 whose coarsest scale still holds an 11 x 11 window: min(H, W) >> (M - 1) >= 11
+    (0 when not even one scale fits)."""
+    m = 0
+    while m < len(MS_SSIM_WEIGHTS) and (min(H, W) >> m) >= 11:
+        m += 1
+    return m
+
+
+def _ms_ssim_args(name: str, pred: torch.Tensor, target: torch.Tensor, weights: Optional[Sequence[float]]):
+    """The checked weights as a tuple and the aligned inputs; every argument error comes before anything touches the device"""
+    w = MS_SSIM_WEIGHTS if weights is None else tuple(float(v) for v in weights)
+    if not 1 <= len(w) <= 8 or not all(0.0 < v < float("inf") for v in w):
+        raise ValueError(f"{name}: weights must be 1 to 8 positive numbers, got {w}")
+    if pred.dim() != 4 or (min(pred.shape[2], pred.shape[3]) >> (len(w) - 1)) < 11:
+        raise RuntimeError(f"{name}: needs (B, C, H, W) with min(H, W) >> {len(w) - 1} >= 11 (the coarsest of {len(w)} scales "
+                           f"must hold an 11 x 11 window: H, W >= {11 << (len(w) - 1)}), got {tuple(pred.shape)}")
+    a, b = _pair(name, pred, target)
+    return w, a, b
+
+
+def _ms_weights_on(device: torch.device, w: Tuple[float, ...]) -> torch.Tensor:
+    key = (device, w)
+    t = _ms_weight_cache.get(key)
+    if t is None:
+        t = _ms_weight_cache[key] = torch.tensor(w, dtype=torch.float32, device=device)
+    return t
+
+
+def _pool_pair(x: torch.Tensor, y: torch.Tensor):
+    """the 2 x 2 means of x and y (one launch) as temporaries of PyTorch's allocator"""
+    shape = (*x.shape[:-2], x.shape[-2] // 2, x.shape[-1] // 2)
+    px, py = x.new_empty(shape), x.new_empty(shape)
+    _nvq.avgpool2_pair(x, y, px, py)
+    return px, py
+
+
+def _ms_ssim_forward(a: torch.Tensor, b: torch.Tensor, data_range: float, w: Tuple[float, ...], per_sample: bool, as_loss: bool):
+    """(out, mtable, dtable) of nvq_msssim_finalize: 2 M launches (M scale passes, M - 1 poolings, the finalize)"""
+    B, Cc, H, W = a.shape
+    M = len(w)
+    out = torch.empty(B if per_sample else 1, dtype=torch.float32, device=a.device)
+    mt = torch.empty(M, B * Cc, dtype=torch.float32, device=a.device)
+    dt = torch.empty_like(mt)
+    with _nvq.device_guard(a.device):
+        ws = _engine.workspace(a.device)
+        x, y = a, b
+        for j in range(M):
+            _nvq.msssim_scale_forward(x, y, H, W, M, j, data_range, ws)
+            if j + 1 < M:
+                x, y = _pool_pair(x, y)
+        _nvq.msssim_finalize(ws, B, Cc, H, W, _ms_weights_on(a.device, w), as_loss, out, mt, dt)
+    return out, mt, dt
+
+
+class _MSSSIMLossFn(torch.autograd.Function):
+    """1 - MS-SSIM; saves the two inputs and the finalize's two (M, B * C) tables, the backward recomputes the pyramid"""
+
+    @staticmethod
+    def forward(ctx, pred, target, data_range: float, weights, per_sample: bool):
+        w, a, b = _ms_ssim_args("ms_ssim_loss", pred, target, weights)
+        out, mt, dt = _ms_ssim_forward(a, b, data_range, w, per_sample, True)
+        ctx.save_for_backward(a, b, mt, dt)
+        ctx.meta = (pred.shape, data_range, len(w))
+        return out if per_sample else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        a, b, _, dt = ctx.saved_tensors
+        shape, data_range, M = ctx.meta
+        H, W = a.shape[2:]
+        go = go.detach().float().reshape(-1).contiguous()
+        with _nvq.device_guard(a.device):
+            levels = [(a, b)]
+            for _ in range(M - 1):
+                levels.append(_pool_pair(*levels[-1]))
+            dx = None
+            for j in range(M - 1, -1, -1):           # coarsest first: each launch folds in the pooling adjoint of the one before
+                x, y = levels[j]
+                d = torch.empty_like(x)
+                _nvq.msssim_scale_backward(x, y, H, W, M, j, data_range, dt, go, -1.0, dx, d)
+                dx = d
+        return dx.view(shape), None, None, None, None
+
+
+def ms_ssim_loss(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, weights: Optional[Sequence[float]] = None,
+                 reduction: str = "mean") -> torch.Tensor:
+    """1 - MS-SSIM on (B, C, H, W).  Scale j of the 2 x 2 mean pyramid gives, per plane, the mean over the valid positions of
+    cs = (2 s_xy + C2) / (s_xx + s_yy + C2) (the last scale: of the SSIM map, window and constants of ``ssim_loss``); a plane's
+    value is prod_j max(mean_j, 0)^w_j, a sample's the mean over its channels.  ``weights``: 1 to 8 positive numbers, default
+    the five standard ones; the coarsest scale must hold a window (``ms_ssim_max_scales``, ``ms_ssim_weights``).  A clamped
+    term gives the value 0 and a zero gradient."""
+    per_sample = _check_reduction(reduction)
+    return _MSSSIMLossFn.apply(pred, target, float(data_range), weights, per_sample)
+
+
+def ms_ssim_l1_loss(pred: torch.Tensor, target: torch.Tensor, alpha: float = 0.84, data_range: float = 1.0,
+                    weights: Optional[Sequence[float]] = None, reduction: str = "mean") -> torch.Tensor:
+    """alpha * ms_ssim_loss + (1 - alpha) * l1_loss (Zhao et al. 2017, without the Gaussian weighting of the L1 term)"""
+    return (alpha * ms_ssim_loss(pred, target, data_range, weights, reduction)
+            + (1.0 - alpha) * l1_loss(pred, target, reduction))
+
+
 def mse_loss(pred: torch.Tensor, target: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
     """mean((pred - target)^2) as two libnvq launches forward and one backward; ``reduction="none"``: one mean per sample."""
     if _check_reduction(reduction):
@@ -180,6 +301,16 @@ class SSIMLoss(_Reduced):
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return ssim_loss(pred, target, self.data_range, self.reduction)
+
+
+class MSSSIMLoss(_Reduced):
+    def __init__(self, data_range: float = 1.0, weights: Optional[Sequence[float]] = None, reduction: str = "mean"):
+        super().__init__(reduction)
+        self.data_range = data_range
+        self.weights = None if weights is None else tuple(float(v) for v in weights)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return ms_ssim_loss(pred, target, self.data_range, self.weights, self.reduction)
 
 
 LOSSES = {"mse": mse_loss, "l1": l1_loss, "charbonnier": charbonnier_loss, "ssim": ssim_loss}

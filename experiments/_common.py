@@ -18,6 +18,23 @@ def compute_psnr(pred: torch.Tensor, target: torch.Tensor) -> float:
     return 20 * torch.log10(1.0 / torch.sqrt(mse)).item()
 
 
+LOSS_CHOICES = ("mse", "l1", "charbonnier", "ssim", "ms_ssim", "ms_ssim_l1")
+
+
+def resolve_loss(name: str):
+    """The libnvq loss f(pred, target, reduction="mean") that --loss names.  The multi-scale ones take as many scales as the
+    target frame allows (ops.ms_ssim_max_scales: 4 at 128 x 128) with the standard weights renormalised."""
+    from nerve_cl import ops
+    if name in ops.LOSSES:
+        return ops.LOSSES[name]
+    fn = {"ms_ssim": ops.ms_ssim_loss, "ms_ssim_l1": ops.ms_ssim_l1_loss}[name]
+
+    def loss(pred, target, reduction="mean"):
+        weights = ops.ms_ssim_weights(ops.ms_ssim_max_scales(*target.shape[-2:]))
+        return fn(pred, target, weights=weights, reduction=reduction)
+    return loss
+
+
 def pick_device():
     """'cuda' when a HIP device is visible (reference train_baseline.py:37); the SR path has no CPU mode."""
     from nerve_cl import parallel

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
-from _common import compute_psnr, make_optimizer, pick_device, shard
+from _common import LOSS_CHOICES, compute_psnr, make_optimizer, pick_device, resolve_loss, shard
 from nerve_cl import metrics, ops, parallel
 from nerve_cl.models import SuperResolutionNet
 
@@ -46,7 +46,7 @@ def train(args) -> None:
     optimizer = make_optimizer(torch.optim.AdamW, model.parameters(), lr=args.lr, weight_decay=1e-5)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=args.epochs)
     # nn.MSELoss() of the reference, as libnvq kernels; --loss picks another libnvq loss
-    criterion = ops.MSELoss() if args.loss == "mse" else ops.LOSSES[args.loss]
+    criterion = ops.MSELoss() if args.loss == "mse" else resolve_loss(args.loss)
 
     say(f"\nTraining for {args.epochs} epochs...")
     say("-" * 60)
@@ -102,7 +102,7 @@ def train(args) -> None:
     say("  Model saved: checkpoints/best_model.pt")
 
 
-def main() -> None:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Train NERVE baseline")
     ap.add_argument("--data-dir", type=str, default="data")
     ap.add_argument("--batch-size", type=int, default=16)
@@ -110,11 +110,15 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--sync-bn", action="store_true",
                     help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
-    ap.add_argument("--loss", choices=("mse", "l1", "charbonnier", "ssim"), default="mse",
+    ap.add_argument("--loss", choices=LOSS_CHOICES, default="mse",
                     help="training and validation loss (libnvq kernels; default: the reference's MSE)")
     ap.add_argument("--metrics", action="store_true",
                     help="add the global-statistics SSIM and the MAE of the validation set to the progress line")
-    args = ap.parse_args()
+    return ap
+
+
+def main() -> None:
+    args = build_parser().parse_args()
     Path("checkpoints").mkdir(exist_ok=True)
     train(args)
 

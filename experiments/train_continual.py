@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
-from _common import make_optimizer, pick_device, shard
+from _common import LOSS_CHOICES, make_optimizer, pick_device, resolve_loss, shard
 from nerve_cl import metrics, ops, parallel
 from nerve_cl.continual import EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
@@ -57,7 +57,7 @@ def configure_precision(model: EnhancementEngine, precision: str, graphs: str) -
 def make_criterion(config):
     """nn.MSELoss() of the reference as libnvq kernels, or the libnvq loss that --loss names"""
     name = config.get("loss", "mse")
-    return ops.MSELoss() if name == "mse" else ops.LOSSES[name]
+    return ops.MSELoss() if name == "mse" else resolve_loss(name)
 
 
 def metrics_suffix(meter, world: int = 1) -> str:
@@ -109,7 +109,7 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
     criterion = make_criterion(config)
     on_device = isinstance(memory, DeviceEpisodicMemory)
     prioritized = bool(config.get("prioritized"))
-    per_sample = ops.LOSSES[config.get("loss", "mse")]             # reduction="none": one value per sample
+    per_sample = resolve_loss(config.get("loss", "mse"))            # reduction="none": one value per sample
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
@@ -150,7 +150,7 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
     return model
 
 
-def main() -> None:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--strategy", choices=["ewc", "replay", "maml"], default="ewc")
     ap.add_argument("--memory-size", type=int, default=200)
@@ -166,7 +166,7 @@ def main() -> None:
                     help="HIP-graph replay of the training step (auto: for launch-bound frame sizes only)")
     ap.add_argument("--sync-bn", action="store_true",
                     help="synchronise BatchNorm statistics over the ranks (nn.SyncBatchNorm; only with a launcher such as torch.distributed.run, WORLD_SIZE > 1).  Steps with synchronised layers run eagerly: HIP-graph replay is off for them")
-    ap.add_argument("--loss", choices=("mse", "l1", "charbonnier", "ssim"), default="mse",
+    ap.add_argument("--loss", choices=LOSS_CHOICES, default="mse",
                     help="data term of the training loss (libnvq kernels; default: the reference's MSE)")
     ap.add_argument("--metrics", action="store_true",
                     help="add the global-statistics SSIM and the MAE of each epoch's outputs to its progress line")
@@ -176,6 +176,11 @@ def main() -> None:
                     help="with --device-memory: element type of the stored samples (bf16 halves the footprint)")
     ap.add_argument("--prioritized", action="store_true",
                     help="with --device-memory: per-sample losses of the replay rows update their importances (momentum 0.9) and replay draws are weighted by them")
+    return ap
+
+
+def main() -> None:
+    ap = build_parser()
     args = ap.parse_args()
     if args.prioritized and not args.device_memory:
         ap.error("--prioritized needs --device-memory")

@@ -564,6 +564,35 @@ int nvq_ssim_forward(const float* x, const float* y, int B, int C, int H, int W,
  * Recomputes the moments per tile (nothing is saved by the forward); gather form, fixed tap order. */
 int nvq_ssim_backward(const float* x, const float* y, int B, int C, int H, int W, float data_range,
                       const float* grad_out_dev, int grad_per_sample, float scale, float* dx, void* stream);
+/* Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) of `planes` = B * C planes of H x W over `scales` <= 8 scales, scale j
+ * (0-based) being (H >> j) x (W >> j): x_0 = x, x_{j+1} = 2 x 2 mean of x_j.  With the window and constants of nvq_ssim_*,
+ * m_j(plane) = mean over the valid positions of cs = (2 s_xy + C2) / (s_xx + s_yy + C2) for j < scales - 1 and of the SSIM map
+ * for the last scale; v(plane) = prod_j max(m_j, 0)^weights[j]; ms(b) = mean over b's channels of v.  The coarsest scale must
+ * hold a window: min(H, W) >> (scales - 1) >= 11.  The caller owns the pyramid; every call is one launch, deterministic.
+ * The local moments are taken about 0.5 * data_range (variances do not depend on the centre; E[x^2] - mu^2 then does not
+ * cancel), so a coarse scale of a few positions is as accurate as the mean over a full-size plane.
+ * px, py [planes][H / 2][W / 2] = 2 x 2 mean, stride 2, of x, y [planes][H][W] (H, W >= 2; an odd last row or column is
+ * dropped), summed in avg_pool2d's order. */
+int nvq_avgpool2_pair(const float* x, const float* y, int planes, int H, int W, float* px, float* py, void* stream);
+/* Bytes of the forward's workspace (one float per tile of every scale); 0 for arguments out of range. */
+size_t nvq_msssim_workspace_bytes(int planes, int H, int W, int scales);
+/* Tile sums of scale `scale` (xs, ys: that scale's planes; H, W: the finest scale's size) into its part of the workspace.
+ * workspace >= nvq_msssim_workspace_bytes(planes, H, W, scales); all scales of one forward share it. */
+int nvq_msssim_scale_forward(const float* xs, const float* ys, int planes, int H, int W, int scales, int scale,
+                             float data_range, float* workspace, size_t workspace_bytes, void* stream);
+/* After every scale's forward: out[b] = ms(b) (per_sample != 0: B floats) or out[0] = mean_b ms(b); as_loss != 0 writes 1 - that.
+ * mtable [scales][B * C] = m_j, dtable [scales][B * C] = d ms(b) / d m_j(b, c), 0 where m_j <= 0 (a clamped term has value 0 and
+ * gradient 0, never 0 * inf).  weights: `scales` positive device floats.  Sums and powers in double, fixed order. */
+int nvq_msssim_finalize(const float* workspace, int B, int C, int H, int W, int scales, const float* weights, int per_sample,
+                        int as_loss, float* out, float* mtable, float* dtable, void* stream);
+/* dx [B * C][H >> scale][W >> scale] = sign * grad_out_dev[b] * d ms(b) / d xs (grad_per_sample != 0: B device floats), or
+ * sign * grad_out_dev[0] * d(mean_b ms(b)) / d xs; NULL grad_out_dev reads as 1.  Only this scale's own term m_`scale` is
+ * differentiated here; dx_coarser (NULL, or the gradient with respect to scale + 1's planes) enters through the pooling
+ * adjoint: dx[r][c] += 0.25 dx_coarser[r / 2][c / 2] where that element exists.  Called from the coarsest scale to the finest,
+ * the last call leaves the whole gradient.  No workspace. */
+int nvq_msssim_scale_backward(const float* xs, const float* ys, int B, int C, int H, int W, int scales, int scale,
+                              float data_range, const float* dtable, const float* grad_out_dev, int grad_per_sample,
+                              float sign, const float* dx_coarser, float* dx, void* stream);
 
 /* ------------------------------------------------------------------ FrameRecoveryNet layers (csrc/fr_ops.hip)
  * Generic NHWC kernels for reference nerve_cl/models/frame_recovery.py:23-446 (+ efficient_layers.py:109-151,

@@ -1,10 +1,13 @@
 """Time the quality kernels (csrc/quality.hip) at 8 x 3 x 1080 x 1920 fp32 against the torch-op composition of the same
 formulas, which is what a user of the package would otherwise run.
-usage: python tools/quality_probe.py [--mode time|kernels|ssim] [--iters 10] [--rounds 3]
+usage: python tools/quality_probe.py [--mode time|kernels|ssim|msssim] [--iters 10] [--rounds 3]
   time    : fused and composed forms alternated, device events around `iters` calls, `rounds` rounds; prints a table with the
             algorithmic bytes and the share of the 8 TB/s HBM peak
   kernels : a few calls of every fused op and nothing else, for `rocprofv3 --kernel-trace --stats`
-  ssim    : the SSIM forward and backward alone, for a `rocprofv3 --pmc` run of their own"""
+  ssim    : the SSIM forward and backward alone, for a `rocprofv3 --pmc` run of their own
+  msssim  : the five-scale MS-SSIM loss beside the torch-op composition of the same formula and beside the single-scale
+            ssim_loss pair, forward and forward+backward, alternated in one run (profiles/ms_ssim.txt);
+            --mode msssim-kernels: a few calls of the MS-SSIM loss alone, for `rocprofv3 --kernel-trace --stats`"""
 import argparse
 import os
 import sys
@@ -36,6 +39,69 @@ def torch_ssim(x, y, g):
     sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
     m = ((2 * mx * my + 1e-4) * (2 * sxy + 9e-4)) / ((mx * mx + my * my + 1e-4) * (sxx + syy + 9e-4))
     return 1 - m.mean()
+
+
+def torch_ms_ssim(x, y, g, weights):
+    """1 - MS-SSIM with stock ops: per scale five separable valid convolutions and the element-wise map, avg_pool2d between"""
+    x, y = x.reshape(B * C, 1, H, W), y.reshape(B * C, 1, H, W)
+
+    def blur(t):
+        return F.conv2d(F.conv2d(t, g.view(1, 1, 1, 11)), g.view(1, 1, 11, 1))
+    v = None
+    for j, w in enumerate(weights):
+        mx, my = blur(x), blur(y)
+        sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
+        m = (2 * sxy + 9e-4) / (sxx + syy + 9e-4)
+        if j == len(weights) - 1:
+            m = m * (2 * mx * my + 1e-4) / (mx * mx + my * my + 1e-4)
+        term = torch.relu(m.mean(dim=(1, 2, 3))) ** w
+        v = term if v is None else v * term
+        if j < len(weights) - 1:
+            x, y = F.avg_pool2d(x, 2), F.avg_pool2d(y, 2)
+    return 1 - v.reshape(B, C).mean(1).mean()
+
+
+def ms_rows(x, y, g):
+    """name -> (MS-SSIM loss, its torch-op composition, the single-scale ssim_loss), five scales, standard weights"""
+    xr = x.clone().requires_grad_(True)
+
+    def fb(fn):
+        def run():
+            xr.grad = None
+            fn(xr, y).backward()
+        return run
+
+    composed = lambda a, b: torch_ms_ssim(a, b, g, ops.MS_SSIM_WEIGHTS)        # noqa: E731
+    return {
+        "ms_ssim fwd": (lambda: ops.ms_ssim_loss(x, y), lambda: composed(x, y), lambda: ops.ssim_loss(x, y)),
+        "ms_ssim fwd+bwd": (fb(ops.ms_ssim_loss), fb(composed), fb(ops.ssim_loss)),
+    }
+
+
+def ms_main(args, x, y, g):
+    table = ms_rows(x, y, g)
+    if args.mode == "msssim-kernels":
+        for _ in range(3):
+            table["ms_ssim fwd+bwd"][0]()
+        torch.cuda.synchronize()
+        return
+    with torch.no_grad():
+        fused, composed = ops.ms_ssim_loss(x, y).item(), torch_ms_ssim(x, y, g, ops.MS_SSIM_WEIGHTS).item()
+    print(f"{B} x {C} x {H} x {W} fp32, 5 scales, {args.iters} calls per timing, {args.rounds} alternated rounds (us per call); "
+          f"loss {fused:.7f} (torch ops {composed:.7f})")
+    for name, fns in table.items():
+        for _ in range(2):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        times = [[], [], []]
+        for _ in range(args.rounds):
+            for t, fn in zip(times, fns):
+                t.append(timed(fn, args.iters))
+        bm, bt, bs = (min(t) for t in times)
+        print(f"{name:18s} fused {' '.join(f'{t:9.1f}' for t in times[0])} | torch ops {' '.join(f'{t:9.1f}' for t in times[1])} | "
+              f"single-scale ssim {' '.join(f'{t:9.1f}' for t in times[2])} | torch / fused {bt / bm:6.2f}x | "
+              f"fused / single-scale {bm / bs:5.2f}x", flush=True)
 
 
 def torch_sums(x, y):
@@ -84,7 +150,7 @@ def timed(fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["time", "kernels", "ssim"], default="time")
+    ap.add_argument("--mode", choices=["time", "kernels", "ssim", "msssim", "msssim-kernels"], default="time")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
@@ -94,6 +160,8 @@ def main():
     y = torch.rand(B, C, H, W, device=dev, generator=gen)
     x = (y + 0.05 * torch.randn(B, C, H, W, device=dev, generator=gen)).clamp(0, 1)
     g = gauss(dev)
+    if args.mode.startswith("msssim"):
+        return ms_main(args, x, y, g)
     table = rows(x, y, g)
     if args.mode != "time":
         for name, (fused, _, _) in table.items():
