@@ -69,6 +69,11 @@ class StepGraphs:
         self.replays = 0
         self.eager_fallbacks = 0
 
+    def __deepcopy__(self, memo):
+        # captured graphs bake in the parameter addresses of the module they were captured for (and a HIP graph cannot be
+        # copied): a deep copy of that module (a distillation teacher, a MAML clone) starts with an empty cache
+        return type(self)()
+
     # ------------------------------------------------------------------ forward
     def forward(self, net, frames: torch.Tensor, need_grad: bool, act_dtype, deterministic: bool = False, plan=None):
         """-> (out, entry, token, gen) or None when this call has to run eagerly.  plan: the backward plan of a step that needs

@@ -211,6 +211,11 @@ SIGNATURES = {
     "nvq_msssim_scale_forward": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
     "nvq_msssim_finalize": (ci, [vp, ci, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp]),
     "nvq_msssim_scale_backward": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, ci, cf, vp, vp, vp]),
+    # distillation losses (csrc/distill.hip)
+    "nvq_distill_forward": (ci, [vp, vp, vp, ci, cl, cf, cf, vp, vp, sz, vp]),
+    "nvq_distill_backward": (ci, [vp, vp, vp, ci, cl, cf, cf, vp, vp, vp]),
+    "nvq_cosine_distill_forward": (ci, [vp, vp, ci, ci, ci, cf, ci, vp, vp, sz, vp]),
+    "nvq_cosine_distill_backward": (ci, [vp, vp, ci, ci, ci, cf, vp, ci, vp, vp]),
     "nvq_axpy_slice": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, cl, cf, ci, ci, vp]),
     "nvq_colsum": (ci, [vp, ci, ci, ci, cl, cf, vp, vp, sz, ci, vp]),
     "nvq_ewc_penalty": (ci, [vp, vp, vp, cl, cf, vp, vp, sz, vp]),
@@ -1219,6 +1224,38 @@ def msssim_scale_backward(xs: torch.Tensor, ys: torch.Tensor, H: int, W: int, sc
     check(lib().nvq_msssim_scale_backward(ptr(xs), ptr(ys), B, Cc, H, W, scales, scale, data_range, ptr(dtable), ptr(go_dev),
                                           int(go_dev.numel() != 1 or B == 1), sign, ptr(dx_coarser), ptr(dx), stream()),
           "nvq_msssim_scale_backward")
+
+
+# ----------------------------------------------------------------------------- distillation
+def distill_forward(s: torch.Tensor, t: torch.Tensor, y: Optional[torch.Tensor], wt: float, wy: float, out: torch.Tensor,
+                    ws: torch.Tensor):
+    """out (3, G): wt d + wy m, d = mean (s - t)^2, m = mean (s - y)^2 (0 without y); G = 1 the whole tensor, G = s.shape[0]
+    one column per sample"""
+    G = out.shape[1]
+    check(lib().nvq_distill_forward(ptr(s), ptr(t), ptr(y), G, s.numel() // G, wt, wy, ptr(out), ptr(ws), ws.numel() * 4,
+                                    stream()), "nvq_distill_forward")
+
+
+def distill_backward(s: torch.Tensor, t: torch.Tensor, y: Optional[torch.Tensor], wt: float, wy: float, go_dev: torch.Tensor,
+                     ds: torch.Tensor):
+    G = go_dev.numel()
+    check(lib().nvq_distill_backward(ptr(s), ptr(t), ptr(y), G, s.numel() // G, wt, wy, ptr(go_dev), ptr(ds), stream()),
+          "nvq_distill_backward")
+
+
+def cosine_distill_forward(s: torch.Tensor, t: torch.Tensor, eps: float, per_sample: bool, out: torch.Tensor, ws: torch.Tensor):
+    """s, t (B, C, H, W) fp32; out (B,) per sample or (1,) over the batch"""
+    B, Cc, H, W = s.shape
+    check(lib().nvq_cosine_distill_forward(ptr(s), ptr(t), B, Cc, H * W, eps, int(per_sample), ptr(out), ptr(ws),
+                                           ws.numel() * 4, stream()), "nvq_cosine_distill_forward")
+
+
+def cosine_distill_backward(s: torch.Tensor, t: torch.Tensor, eps: float, go_dev: torch.Tensor, per_sample: bool,
+                            ds: torch.Tensor):
+    """go_dev (B,) per sample or (1,) for the batch mean"""
+    B, Cc, H, W = s.shape
+    check(lib().nvq_cosine_distill_backward(ptr(s), ptr(t), B, Cc, H * W, eps, ptr(go_dev), int(per_sample), ptr(ds), stream()),
+          "nvq_cosine_distill_backward")
 
 
 # ----------------------------------------------------------------------------- EWC

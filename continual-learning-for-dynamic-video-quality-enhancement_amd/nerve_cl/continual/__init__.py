@@ -1,6 +1,7 @@
 """Continual-learning components around the SR hot path (reference nerve_cl/continual/__init__.py: the same names).
 EWC and SynapticIntelligence run their penalty / Fisher arithmetic as flat-bucket HIP kernels; DeviceEpisodicMemory keeps the replay samples in
-HBM behind the libnvq replay kernels; the others are host-side loops that only need forward / backward / deepcopy of the model."""
+HBM behind the libnvq replay kernels; ContinualDistillation takes its output and feature terms from the fused kernels of
+csrc/distill.hip; the others are host-side loops that only need forward / backward / deepcopy of the model."""
 from nerve_cl.continual.memory import EpisodicMemory, StreamingEpisodicMemory
 from nerve_cl.continual.device_memory import DeviceEpisodicMemory
 from nerve_cl.continual.ewc import EWC, OnlineEWC, SynapticIntelligence

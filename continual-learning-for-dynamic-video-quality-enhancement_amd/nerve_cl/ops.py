@@ -11,10 +11,14 @@ means PER SAMPLE: a ``(B,)`` tensor holding the mean over each sample's elements
 needs), not one value per element.
 
 ``ms_ssim_loss`` / ``MSSSIMLoss`` (multi-scale SSIM) and the ``ms_ssim_l1_loss`` mix follow the same rules.
+
+``distill_loss`` / ``DistillLoss`` (the output term of a distillation step: teacher and target terms from one pass over the
+student output) and ``cosine_feature_loss`` / ``CosineFeatureLoss`` (feature distillation on ``return_intermediate`` tensors)
+are csrc/distill.hip; their gradient is with respect to the student only.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -240,6 +244,142 @@ def ms_ssim_l1_loss(pred: torch.Tensor, target: torch.Tensor, alpha: float = 0.8
             + (1.0 - alpha) * l1_loss(pred, target, reduction))
 
 
+# ------------------------------------------------------------------------------------------------ distillation (section 18)
+
+def _distill_args(name: str, student: torch.Tensor, teacher: torch.Tensor, target: Optional[torch.Tensor], per_sample: bool):
+    """every argument error of the output term, then the refusal of CPU tensors, before anything touches the device"""
+    if student.shape != teacher.shape:
+        raise RuntimeError(f"{name}: shapes differ, student {tuple(student.shape)} vs teacher {tuple(teacher.shape)}")
+    if target is not None and target.shape != student.shape:
+        raise RuntimeError(f"{name}: shapes differ, student {tuple(student.shape)} vs target {tuple(target.shape)}")
+    if student.numel() == 0:
+        raise RuntimeError(f"{name}: empty tensors")
+    if per_sample and student.dim() < 1:
+        raise RuntimeError(f"{name}: reduction='none' needs a batch dimension")
+    _nvq.require_device(student, "student output")
+    _nvq.require_device(teacher, "teacher output")
+    if target is not None:
+        _nvq.require_device(target, "target")
+
+
+class _DistillFn(torch.autograd.Function):
+    """wt * mean (s - t)^2 + wy * mean (s - y)^2 from one pass over s, t, y (two launches); the backward is one launch that
+    writes ds once.  Outputs (value, d, m); d and m are report values without a gradient."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, target, wt: float, wy: float, per_sample: bool):
+        s, t = _aligned(student), _aligned(teacher)
+        y = None if target is None else _aligned(target)
+        G = s.shape[0] if per_sample else 1
+        out = torch.empty(3, G, dtype=torch.float32, device=s.device)
+        with _nvq.device_guard(s.device):
+            _nvq.distill_forward(s, t, y, wt, wy, out, _engine.workspace(s.device))
+        if y is None:
+            ctx.save_for_backward(s, t)
+        else:
+            ctx.save_for_backward(s, t, y)
+        ctx.meta = (student.shape, wt, wy)
+        value, d, m = (out[0], out[1], out[2]) if per_sample else (out[0, 0], out[1, 0], out[2, 0])
+        ctx.mark_non_differentiable(d, m)
+        ctx.set_materialize_grads(False)     # (no zero tensors for d and m; the value's gradient is never None in backward)
+        return value, d, m
+
+    @staticmethod
+    def backward(ctx, go, _gd, _gm):
+        s, t, *rest = ctx.saved_tensors
+        shape, wt, wy = ctx.meta
+        ds = torch.empty_like(s)
+        with _nvq.device_guard(s.device):
+            _nvq.distill_backward(s, t, rest[0] if rest else None, wt, wy, go.detach().float().reshape(-1).contiguous(), ds)
+        return ds.view(shape), None, None, None, None, None
+
+
+def _distill_weighted(student: torch.Tensor, teacher: torch.Tensor, target: Optional[torch.Tensor], wt: float, wy: float,
+                      reduction: str = "mean", name: str = "distill_loss"):
+    """(wt * mse(s, t) + wy * mse(s, y), mse(s, t), mse(s, y)) with free weights: ``distill_loss`` is (alpha, 1 - alpha), a
+    distillation step with its MSE task term folded in is (alpha, 2 - alpha)"""
+    per_sample = _check_reduction(reduction)
+    _distill_args(name, student, teacher, target, per_sample)
+    return _DistillFn.apply(student, teacher, target, float(wt), float(wy) if target is not None else 0.0, per_sample)
+
+
+def distill_loss(student: torch.Tensor, teacher: torch.Tensor, target: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                 reduction: str = "mean", return_terms: bool = False):
+    """alpha * mse(student, teacher) + (1 - alpha) * mse(student, target), or mse(student, teacher) without a target: one
+    autograd node, one pass over the tensors forward and one backward.  The gradient is with respect to ``student`` only.
+    ``return_terms``: also the two means d = mse(student, teacher) and m = mse(student, target) (0 without a target), which
+    carry no gradient."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"distill_loss: alpha must be in [0, 1], got {alpha}")
+    wt, wy = (1.0, 0.0) if target is None else (alpha, 1.0 - alpha)
+    value, d, m = _distill_weighted(student, teacher, target, wt, wy, reduction)
+    return (value, d, m) if return_terms else value
+
+
+def _cosine_args(name: str, student: torch.Tensor, teacher: torch.Tensor) -> None:
+    if student.dim() != 4:
+        raise RuntimeError(f"{name}: needs (B, C, H, W) feature tensors, got {tuple(student.shape)}")
+    if student.shape != teacher.shape:
+        raise RuntimeError(f"{name}: shapes differ, student {tuple(student.shape)} vs teacher {tuple(teacher.shape)}")
+    if student.numel() == 0:
+        raise RuntimeError(f"{name}: empty tensors")
+
+
+class _CosineFn(torch.autograd.Function):
+    """mean over the positions of 1 - cos(s_p, t_p); saves the two inputs only, the backward recomputes the moments"""
+
+    @staticmethod
+    def forward(ctx, student, teacher, eps: float, per_sample: bool):
+        s, t = _aligned(student), _aligned(teacher)
+        out = torch.empty(s.shape[0] if per_sample else 1, dtype=torch.float32, device=s.device)
+        with _nvq.device_guard(s.device):
+            _nvq.cosine_distill_forward(s, t, eps, per_sample, out, _engine.workspace(s.device))
+        ctx.save_for_backward(s, t)
+        ctx.meta = (student.shape, eps, per_sample)
+        return out if per_sample else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        s, t = ctx.saved_tensors
+        shape, eps, per_sample = ctx.meta
+        ds = torch.empty_like(s)
+        with _nvq.device_guard(s.device):
+            _nvq.cosine_distill_backward(s, t, eps, go.detach().float().reshape(-1).contiguous(), per_sample, ds)
+        return ds.view(shape), None, None, None
+
+
+Features = Union[torch.Tensor, Sequence[torch.Tensor]]
+
+
+def cosine_feature_loss(student: Features, teacher: Features, eps: float = 1e-8, reduction: str = "mean") -> torch.Tensor:
+    """Feature distillation on (B, C, H, W) tensors: v_p = 1 - <s_p, t_p> / (max(|s_p|, eps) max(|t_p|, eps)) over the channels
+    of every position, averaged over the positions (of the batch, or of each sample with ``reduction="none"``).  Lists of such
+    tensors (the ``features`` and ``aligned`` entries of ``return_intermediate``) give the mean over the list's entries, one
+    launch pair per entry.  The gradient is with respect to ``student`` only; where |s_p| <= eps the norm is the constant eps."""
+    per_sample = _check_reduction(reduction)
+    eps = float(eps)
+    if not eps > 0.0:
+        raise ValueError(f"cosine_feature_loss: eps must be > 0, got {eps}")
+    is_list = not isinstance(student, torch.Tensor)
+    if is_list != (not isinstance(teacher, torch.Tensor)):
+        raise TypeError("cosine_feature_loss: student and teacher must both be tensors or both be lists of tensors")
+    ss: List[torch.Tensor] = list(student) if is_list else [student]
+    ts: List[torch.Tensor] = list(teacher) if is_list else [teacher]
+    if len(ss) != len(ts) or not ss:
+        raise RuntimeError(f"cosine_feature_loss: needs two non-empty lists of equal length, got {len(ss)} and {len(ts)}")
+    for a, b in zip(ss, ts):
+        _cosine_args("cosine_feature_loss", a, b)
+    for a, b in zip(ss, ts):
+        _nvq.require_device(a, "student features")
+        _nvq.require_device(b, "teacher features")
+    total = None
+    for a, b in zip(ss, ts):
+        v = _CosineFn.apply(a, b, eps, per_sample)
+        total = v if total is None else total + v
+    return total / len(ss) if len(ss) > 1 else total
+
+
 def mse_loss(pred: torch.Tensor, target: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
     """mean((pred - target)^2) as two libnvq launches forward and one backward; ``reduction="none"``: one mean per sample."""
     if _check_reduction(reduction):
@@ -311,6 +451,32 @@ class MSSSIMLoss(_Reduced):
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return ms_ssim_loss(pred, target, self.data_range, self.weights, self.reduction)
+
+
+class DistillLoss(_Reduced):
+    """``distill_loss`` as a module: forward(student, teacher, target=None)"""
+
+    def __init__(self, alpha: float = 0.5, reduction: str = "mean"):
+        super().__init__(reduction)
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"DistillLoss: alpha must be in [0, 1], got {alpha}")
+        self.alpha = float(alpha)
+
+    def forward(self, student: torch.Tensor, teacher: torch.Tensor, target: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return distill_loss(student, teacher, target, self.alpha, self.reduction)
+
+
+class CosineFeatureLoss(_Reduced):
+    """``cosine_feature_loss`` as a module: forward(student, teacher) on (B, C, H, W) tensors or lists of them"""
+
+    def __init__(self, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(reduction)
+        if not float(eps) > 0.0:
+            raise ValueError(f"CosineFeatureLoss: eps must be > 0, got {eps}")
+        self.eps = float(eps)
+
+    def forward(self, student: Features, teacher: Features) -> torch.Tensor:
+        return cosine_feature_loss(student, teacher, self.eps, self.reduction)
 
 
 LOSSES = {"mse": mse_loss, "l1": l1_loss, "charbonnier": charbonnier_loss, "ssim": ssim_loss}

@@ -11,7 +11,10 @@ reference prints.  ``--tasks`` / ``--samples`` / ``--epochs`` are additions (def
 in its throughput mode by default - bf16 MFMA operands with fp32 accumulation and, for such small frames, HIP-graph replay of the
 step (``net.use_hip_graphs = "auto"``); ``--precision fp32 --graphs off`` is the exact-fp32 parity mode the package defaults to.
 ``--device-memory`` (with ``--memory-storage`` / ``--prioritized``) keeps the replay memory in HBM (DeviceEpisodicMemory, DESIGN.md
-section 16); without it the replay strategy runs the host-side EpisodicMemory and prints what it always printed."""
+section 16); without it the replay strategy runs the host-side EpisodicMemory and prints what it always printed.
+``--strategy distill`` (with ``--distill-alpha`` / ``--feature-distill``) is the reference's fourth method, which its own script
+imports and never runs: after every task the SR network is frozen into a teacher, and the next task's loss adds the fused
+output and cosine feature distillation terms of csrc/distill.hip."""
 import argparse
 from pathlib import Path
 
@@ -42,6 +45,20 @@ class _ClipAdapter(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.engine(x.unsqueeze(1).expand(-1, 3, -1, -1, -1))["enhanced"]
+
+
+class _SRClipAdapter(nn.Module):
+    """4-D frame batch -> the engine's SR network on the repeated-frame clip, forwarding ``return_intermediate``: the student
+    (and, deep-copied, the teacher) of the distill strategy.  enhancement_strength is 1 in this script, so the SR output is the
+    engine's 'enhanced'.  Shares the engine's parameters."""
+
+    def __init__(self, sr: nn.Module):
+        super().__init__()
+        self.sr = sr
+
+    def forward(self, x: torch.Tensor, return_intermediate: bool = False):
+        clip = x.unsqueeze(1).expand(-1, self.sr.num_frames, -1, -1, -1)
+        return self.sr(clip, return_intermediate=True) if return_intermediate else self.sr(clip)
 
 
 def configure_precision(model: EnhancementEngine, precision: str, graphs: str) -> None:
@@ -150,9 +167,48 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
     return model
 
 
+def train_with_distill(model, tasks, config, rank=0, epochs=5):
+    """Single process, unsharded.  With the MSE criterion the task term is folded into the distillation kernel (fold_task)."""
+    device = next(model.parameters()).device
+    distill = ContinualDistillation(_SRClipAdapter(model.super_resolution), alpha=config.get("distill_alpha", 0.5),
+                                    feature_weight=config.get("feature_distill", 0.0),
+                                    fold_task=config.get("loss", "mse") == "mse" and config.get("fold_task", True))
+    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    criterion = make_criterion(config)
+    say = print if rank == 0 else (lambda *a, **k: None)
+    for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        say(f"\n=== Training on Task {task_id}: {task_name} ===")
+        loader = DataLoader(TensorDataset(lr, hr), batch_size=16, shuffle=True)
+        for epoch in range(epochs):
+            model.train()
+            parts = torch.zeros(4, device=device)                   # total, task, distill, feature: one host read per epoch
+            meter = metrics.QualityMeter() if config.get("metrics") else None
+            for lr_b, hr_b in loader:
+                lr_b, hr_b = lr_b.to(device), hr_b.to(device)
+                optimizer.zero_grad()
+                losses = distill.compute_loss(lr_b, hr_b, criterion)
+                losses["total"].backward()
+                optimizer.step()
+                feature = losses.get("feature", parts.new_zeros(()))
+                parts += torch.stack([losses[k].detach().float() for k in ("total", "task", "distill")] + [feature.detach().float()])
+                if meter is not None:
+                    meter.update(distill.last_output, hr_b)
+            total, task, dist, feat = (parts / len(loader)).tolist()
+            say(f"  Epoch {epoch + 1}: Loss={total:.4f} Task={task:.4f} Distill={dist:.6f} Feature={feat:.6f}"
+                f"{metrics_suffix(meter)}")
+        distill.register_task()
+        say(f"  Registered task {task_id} as the distillation teacher")
+    return model
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--strategy", choices=["ewc", "replay", "maml"], default="ewc")
+    ap.add_argument("--strategy", choices=["ewc", "replay", "maml", "distill"], default="ewc")
+    ap.add_argument("--distill-alpha", type=float, default=0.5,
+                    help="distill strategy: weight of the teacher term, alpha * mse(s, teacher) + (1 - alpha) * mse(s, target)")
+    ap.add_argument("--feature-distill", type=float, default=0.0, metavar="W",
+                    help="distill strategy: weight of the cosine feature distillation on the SR network's aggregated features "
+                         "(0: output distillation only)")
     ap.add_argument("--memory-size", type=int, default=200)
     ap.add_argument("--ewc-lambda", type=float, default=5000)
     ap.add_argument("--tasks", type=int, default=4)
@@ -194,7 +250,8 @@ def main() -> None:
     if world > 1:
         model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
-    config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized}
+    config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized,
+              "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill}
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs)
     elif args.strategy == "replay":
@@ -204,6 +261,10 @@ def main() -> None:
         else:
             memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
         model = train_with_replay(model, tasks, memory, config, rank, args.epochs)
+    elif args.strategy == "distill":
+        if world > 1:
+            ap.error("--strategy distill runs in a single process")
+        model = train_with_distill(model, tasks, config, rank, args.epochs)
     # ('maml' has no branch in the reference either: it saves the untrained model)
     if rank == 0:
         Path("checkpoints").mkdir(exist_ok=True)

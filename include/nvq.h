@@ -594,6 +594,28 @@ int nvq_msssim_scale_backward(const float* xs, const float* ys, int B, int C, in
                               float data_range, const float* dtable, const float* grad_out_dev, int grad_per_sample,
                               float sign, const float* dx_coarser, float* dx, void* stream);
 
+/* ------------------------------------------------------------------ distillation losses (csrc/distill.hip)
+ * s = student, t = teacher, y = target: contiguous fp32, 16-byte aligned; the gradient is with respect to s only.  No float
+ * atomics: every entry point is deterministic. */
+/* One pass over s, t and y (y may be NULL: its term is 0).  Per group g of `per` elements (groups = 1: the whole tensor;
+ * groups = B: one per sample) d = mean (s - t)^2 and m = mean (s - y)^2; out [3][groups] = wt d + wy m, d, m.
+ * workspace >= groups * 16 KiB. */
+int nvq_distill_forward(const float* s, const float* t, const float* y, int groups, long per, float wt, float wy, float* out,
+                        float* workspace, size_t workspace_bytes, void* stream);
+/* ds = grad_out_dev[g] * (2 / per) * (wt (s - t) + wy (s - y))  (grad_out_dev: `groups` device floats, NULL for 1); one
+ * launch, ds written once */
+int nvq_distill_backward(const float* s, const float* t, const float* y, int groups, long per, float wt, float wy,
+                         const float* grad_out_dev, float* ds, void* stream);
+/* Cosine distance of [B][C][hw] feature tensors over the channels of every position p: a = sum_c s^2, b = sum_c t^2,
+ * ab = sum_c s t, v_p = 1 - ab / (max(sqrt a, eps) max(sqrt b, eps)).  out[b] = mean of v_p over sample b's positions
+ * (per_sample != 0: B floats) or out[0] = the mean over all B * hw positions.  workspace >= B * 4 KiB. */
+int nvq_cosine_distill_forward(const float* s, const float* t, int B, int C, int hw, float eps, int per_sample, float* out,
+                               float* workspace, size_t workspace_bytes, void* stream);
+/* ds_c = -(grad_out_dev[b or 0] / N) * (t_c / (ns nt) - [sqrt a > eps] cos_p s_c / a), N = hw (per_sample != 0) or B * hw;
+ * NULL grad_out_dev reads as 1.  The moments are recomputed (two sweeps over C); no workspace. */
+int nvq_cosine_distill_backward(const float* s, const float* t, int B, int C, int hw, float eps, const float* grad_out_dev,
+                                int per_sample, float* ds, void* stream);
+
 /* ------------------------------------------------------------------ FrameRecoveryNet layers (csrc/fr_ops.hip)
  * Generic NHWC kernels for reference nerve_cl/models/frame_recovery.py:23-446 (+ efficient_layers.py:109-151,
  * 231-294).  Tensors are [N,H,W,ld], logical channel count C <= ld, ld % 4 == 0, channels [C, ld) kept 0; fp32, or -
