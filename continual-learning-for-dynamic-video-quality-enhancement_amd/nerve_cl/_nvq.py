@@ -223,6 +223,10 @@ SIGNATURES = {
     "nvq_fisher_accumulate": (ci, [vp, cl, vp, vp]),
     "nvq_si_update": (ci, [vp, vp, cl, vp, vp, vp]),
     "nvq_si_consolidate": (ci, [vp, cl, cf, vp, vp, vp, vp]),
+    # gradient projection (A-GEM) and global-norm clipping on flat buckets (csrc/bucket_ops.hip)
+    "nvq_bucket_moments": (ci, [vp, vp, cl, vp, ci, ci, vp, sz, vp]),
+    "nvq_bucket_project": (ci, [vp, vp, cl, vp, vp]),
+    "nvq_bucket_clip": (ci, [vp, cl, vp, cf, vp, vp]),
     # device-resident episodic memory (csrc/replay.hip)
     "nvq_replay_store": (ci, [vp, vp, ci, cl, cl, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
     "nvq_replay_gather": (ci, [vp, vp, ci, ci, cl, cl, vp, ci, vp, vp, ci, vp, vp]),
@@ -1280,6 +1284,33 @@ def si_consolidate(theta, damping: float, p_old, W, omega):
 
 def fisher_accumulate(grad, fisher):
     check(lib().nvq_fisher_accumulate(ptr(grad), grad.numel(), ptr(fisher), stream()), "nvq_fisher_accumulate")
+
+
+def _bucket_acc(acc: torch.Tensor) -> int:
+    assert acc.dtype == torch.float64 and acc.numel() >= 5, "acc: 5 float64 slots (g.r, r.r, g.g, c, projections)"
+    return ptr(acc)
+
+
+def bucket_moments(g: torch.Tensor, r: Optional[torch.Tensor], acc: torch.Tensor, ws: torch.Tensor, accumulate: bool = False,
+                   coefficient: bool = False):
+    """acc[0..2] (+)= g.r, r.r, g.g over two flat fp32 tensors (r None: g.g only); ``coefficient``: also the A-GEM decision
+    acc[3] = c, acc[4] += (c != 0) (nvq_bucket_moments)"""
+    assert g.dtype == torch.float32 and (r is None or (r.dtype == torch.float32 and r.numel() == g.numel()))
+    check(lib().nvq_bucket_moments(ptr(g), ptr(r), g.numel(), _bucket_acc(acc), int(accumulate), int(coefficient), ptr(ws),
+                                   ws.numel() * 4, stream()), "nvq_bucket_moments")
+
+
+def bucket_project(g: torch.Tensor, r: torch.Tensor, acc: torch.Tensor):
+    """g -= acc[3] * r in place (untouched when acc[3] == 0)"""
+    assert g.dtype == torch.float32 and r.dtype == torch.float32 and r.numel() == g.numel()
+    check(lib().nvq_bucket_project(ptr(g), ptr(r), g.numel(), _bucket_acc(acc), stream()), "nvq_bucket_project")
+
+
+def bucket_clip(g: torch.Tensor, acc: torch.Tensor, max_norm: float, norm_out: Optional[torch.Tensor]):
+    """g *= max_norm / (sqrt(acc[2]) + 1e-6) in place when that is < 1; norm_out (fp32 device scalar) = sqrt(acc[2])"""
+    assert g.dtype == torch.float32
+    check(lib().nvq_bucket_clip(ptr(g), g.numel(), _bucket_acc(acc), float(max_norm), ptr(norm_out), stream()),
+          "nvq_bucket_clip")
 
 
 # ----------------------------------------------------------------------------- device-resident episodic memory

@@ -15,6 +15,9 @@ needs), not one value per element.
 ``distill_loss`` / ``DistillLoss`` (the output term of a distillation step: teacher and target terms from one pass over the
 student output) and ``cosine_feature_loss`` / ``CosineFeatureLoss`` (feature distillation on ``return_intermediate`` tensors)
 are csrc/distill.hip; their gradient is with respect to the student only.
+
+``clip_grad_norm_`` is not a loss: global 2-norm gradient clipping on the flat gradient buckets without a host read
+(csrc/bucket_ops.hip).
 """
 from __future__ import annotations
 
@@ -480,3 +483,20 @@ class CosineFeatureLoss(_Reduced):
 
 
 LOSSES = {"mse": mse_loss, "l1": l1_loss, "charbonnier": charbonnier_loss, "ssim": ssim_loss}
+
+
+def clip_grad_norm_(module_or_parameters, max_norm: float, refresh: bool = False) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` for the 2-norm, in place: every gradient is scaled by ``max_norm / (total_norm + 1e-6)``
+    when that is below 1 and left untouched otherwise.  Returns the total norm as a 0-dim tensor on the gradients' device; the
+    decision is taken on the device, so the call never synchronises with the host.
+
+    Given a module, every bucketed network inside whose ``.grad`` tensors are the views of its last gradient bucket (the plain
+    zero_grad -> backward -> step loop) costs two reduction launches and one scale launch on the bucket in place; loose
+    parameters, accumulated gradients and a plain iterable of parameters go per tensor.  The sums are taken in double from
+    exact squares.  Gradients on the CPU defer to ``torch.nn.utils.clip_grad_norm_``.  In a data-parallel run a parameter outside
+    the bucketed networks that carries a gradient raises: its gradient is not synchronised, so the ranks would scale differently.
+
+    A module's split into bucketed networks and loose parameters is worked out on the first call and kept (as ``AGEM`` and ``EWC``
+    keep theirs from construction); ``refresh=True`` repeats it after parameters were added to or removed from the module."""
+    from nerve_cl.continual.agem import clip_grad_norm_ as impl       # (nerve_cl.continual imports this module)
+    return impl(module_or_parameters, max_norm, refresh)

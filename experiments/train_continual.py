@@ -14,7 +14,11 @@ step (``net.use_hip_graphs = "auto"``); ``--precision fp32 --graphs off`` is the
 section 16); without it the replay strategy runs the host-side EpisodicMemory and prints what it always printed.
 ``--strategy distill`` (with ``--distill-alpha`` / ``--feature-distill``) is the reference's fourth method, which its own script
 imports and never runs: after every task the SR network is frozen into a teacher, and the next task's loss adds the fused
-output and cosine feature distillation terms of csrc/distill.hip."""
+output and cosine feature distillation terms of csrc/distill.hip.
+``--strategy agem`` (with ``--agem-ref-batch``; the memory flags of the replay strategy apply) is A-GEM: before every step the
+gradient on a batch from the memory is taken as the reference, and a conflicting step gradient is projected onto its orthogonal
+complement in place in the gradient bucket, decision included on the device (csrc/bucket_ops.hip).
+``--clip-grad-norm X`` clips the global gradient norm before every optimizer step of any strategy with the same kernels."""
 import argparse
 from pathlib import Path
 
@@ -25,7 +29,7 @@ from torch.utils.data import DataLoader, TensorDataset
 
 from _common import LOSS_CHOICES, make_optimizer, pick_device, resolve_loss, shard
 from nerve_cl import metrics, ops, parallel
-from nerve_cl.continual import EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
+from nerve_cl.continual import AGEM, EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 
 OFFSETS = {"sports": 0.2, "animation": -0.2, "movie": 0.0, "news": 0.1}
@@ -77,6 +81,13 @@ def make_criterion(config):
     return ops.MSELoss() if name == "mse" else resolve_loss(name)
 
 
+def clip_gradients(model, config) -> None:
+    """--clip-grad-norm: global 2-norm clipping on the gradient buckets, no host read (nothing without the flag)"""
+    max_norm = config.get("clip_grad_norm")
+    if max_norm is not None:
+        ops.clip_grad_norm_(model, max_norm)
+
+
 def metrics_suffix(meter, world: int = 1) -> str:
     """' SSIM=... MAE=...' of the epoch's (detached) outputs against their targets; '' without --metrics"""
     if meter is None:
@@ -108,6 +119,7 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
                 out = model(lr_b.unsqueeze(1).expand(-1, 3, -1, -1, -1))["enhanced"]
                 loss = criterion(out, hr_b) + ewc.penalty()
                 loss.backward()
+                clip_gradients(model, config)
                 optimizer.step()
                 total += loss.item()
                 if meter is not None:
@@ -151,19 +163,57 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
             else:
                 loss = criterion(out, hr_b)
             loss.backward()
+            clip_gradients(model, config)
             optimizer.step()
             meter = None
             if config.get("metrics"):
                 meter = metrics.QualityMeter()
                 meter.update(out, hr_b)
             say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f}{metrics_suffix(meter)}")
-        n_store = min(50, len(lr))
-        if on_device:
-            memory.store_batch(lr[:n_store], hr[:n_store], content_type=task_name)
-        else:
-            for i in range(n_store):
-                memory.store(lr[i], hr[i], metadata={"content_type": task_name})
+        store_task(memory, lr, hr, task_name)
         say(f"  Memory size: {len(memory)}")
+    return model
+
+
+def store_task(memory, lr, hr, task_name) -> None:
+    """the first 50 samples of a finished task go to the memory (host or device class)"""
+    n_store = min(50, len(lr))
+    if isinstance(memory, DeviceEpisodicMemory):
+        memory.store_batch(lr[:n_store], hr[:n_store], content_type=task_name)
+    else:
+        for i in range(n_store):
+            memory.store(lr[i], hr[i], metadata={"content_type": task_name})
+
+
+def train_with_agem(model, tasks, memory, config, rank=0, epochs=5):
+    """Shaped like train_with_replay: the memory's samples are not mixed into the batch, their gradient constrains the step's."""
+    device = next(model.parameters()).device
+    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    criterion = make_criterion(config)
+    adapter = _ClipAdapter(model)
+    agem = AGEM(adapter, memory, ref_batch_size=config.get("agem_ref_batch", 8))
+    say = print if rank == 0 else (lambda *a, **k: None)
+    for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        say(f"\n=== Training on Task {task_id}: {task_name} ===")
+        for epoch in range(epochs):
+            model.train()
+            idx = torch.randperm(len(lr))[:16]
+            lr_b, hr_b = lr[idx].to(device), hr[idx].to(device)
+            agem.compute_reference(criterion)                       # False (and no constraint) while the memory is empty
+            optimizer.zero_grad()
+            out = adapter(lr_b)
+            loss = criterion(out, hr_b)
+            loss.backward()
+            agem.project()
+            clip_gradients(model, config)
+            optimizer.step()
+            meter = None
+            if config.get("metrics"):
+                meter = metrics.QualityMeter()
+                meter.update(out, hr_b)
+            say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f} cos(g,ref)={agem.cosine().item():+.4f}{metrics_suffix(meter)}")
+        store_task(memory, lr, hr, task_name)
+        say(f"  Memory size: {len(memory)}  projections so far: {agem.num_projections()}")
     return model
 
 
@@ -188,6 +238,7 @@ def train_with_distill(model, tasks, config, rank=0, epochs=5):
                 optimizer.zero_grad()
                 losses = distill.compute_loss(lr_b, hr_b, criterion)
                 losses["total"].backward()
+                clip_gradients(model, config)
                 optimizer.step()
                 feature = losses.get("feature", parts.new_zeros(()))
                 parts += torch.stack([losses[k].detach().float() for k in ("total", "task", "distill")] + [feature.detach().float()])
@@ -203,7 +254,11 @@ def train_with_distill(model, tasks, config, rank=0, epochs=5):
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--strategy", choices=["ewc", "replay", "maml", "distill"], default="ewc")
+    ap.add_argument("--strategy", choices=["ewc", "replay", "maml", "distill", "agem"], default="ewc")
+    ap.add_argument("--agem-ref-batch", type=int, default=8,
+                    help="agem strategy: samples drawn from the memory for the reference gradient of every step")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global 2-norm of the gradient to X before every optimizer step (any strategy; default: no clipping)")
     ap.add_argument("--distill-alpha", type=float, default=0.5,
                     help="distill strategy: weight of the teacher term, alpha * mse(s, teacher) + (1 - alpha) * mse(s, target)")
     ap.add_argument("--feature-distill", type=float, default=0.0, metavar="W",
@@ -251,16 +306,18 @@ def main() -> None:
         model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
     config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized,
-              "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill}
+              "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill,
+              "agem_ref_batch": args.agem_ref_batch, "clip_grad_norm": args.clip_grad_norm}
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs)
-    elif args.strategy == "replay":
+    elif args.strategy in ("replay", "agem"):
         if args.device_memory:
             memory = DeviceEpisodicMemory(capacity=args.memory_size, strategy="stratified", device=device,
                                           storage=args.memory_storage)
         else:
             memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
-        model = train_with_replay(model, tasks, memory, config, rank, args.epochs)
+        train = train_with_replay if args.strategy == "replay" else train_with_agem
+        model = train(model, tasks, memory, config, rank, args.epochs)
     elif args.strategy == "distill":
         if world > 1:
             ap.error("--strategy distill runs in a single process")

@@ -774,6 +774,25 @@ int nvq_fisher_accumulate(const float* grad, long n, float* fisher, void* stream
 int nvq_si_update(const float* theta, const float* grad, long n, float* p_old, float* W, void* stream);
 int nvq_si_consolidate(const float* theta, long n, float damping, float* p_old, float* W, float* omega, void* stream);
 
+/* ------------------------------------------------------------------ gradient projection and clipping (csrc/bucket_ops.hip)
+ * A-GEM (Chaudhry et al. 2019) and global-norm clipping on flat fp32 gradient buckets, without a host read.  `acc` is a
+ * caller-owned device buffer of 5 doubles: acc[0] = g.r, acc[1] = r.r, acc[2] = g.g, acc[3] = projection coefficient c,
+ * acc[4] = number of projections so far (the caller zeroes it once).
+ *
+ * nvq_bucket_moments: one pass over g and r (n floats each, 4-byte aligned): exact products, sums in double, per-block
+ * partials in the workspace (>= 24 KiB, 8-byte aligned) and one finishing block; no atomics, the grid depends on n only, so
+ * the sums are bit-reproducible and do not depend on the alignment of g / r.  acc[0..2] = the sums, or += with `accumulate`
+ * (several segments chained into one acc).  r == NULL: g.g only (acc[0], acc[1] are zeroed, or kept with `accumulate`).
+ * `coefficient` (the last segment's call): then c = acc[0] / acc[1] when acc[0] < 0 and acc[1] > 0, else 0 (a NaN compares
+ * false); acc[4] += 1 when c != 0. */
+int nvq_bucket_moments(const float* g, const float* r, long n, double* acc, int accumulate, int coefficient,
+                       float* workspace, size_t workspace_bytes, void* stream);
+/* g[i] = fmaf(-(float)c, r[i], g[i]) with c = acc[3] read on the device; c == 0 leaves g untouched (bit-identical) */
+int nvq_bucket_project(float* g, const float* r, long n, const double* acc, void* stream);
+/* torch.nn.utils.clip_grad_norm_ (2-norm) from acc[2] = g.g over all segments: coef = max_norm / (sqrt(acc[2]) + 1e-6);
+ * g[i] *= coef only when coef < 1, otherwise g is untouched.  *norm_out (device, may be NULL) = the total norm. */
+int nvq_bucket_clip(float* g, long n, const double* acc, float max_norm, float* norm_out, void* stream);
+
 /* ------------------------------------------------------------------ device-resident episodic memory (csrc/replay.hip)
  * The memory is a set of caller-owned tables with `capacity` rows (capacity <= 65536): lr_store [capacity][lr_per] and
  * hr_store [capacity][hr_per] (fp32, or bf16 when store_bf16), means [capacity][channels] fp32 (per-channel mean of the LR
