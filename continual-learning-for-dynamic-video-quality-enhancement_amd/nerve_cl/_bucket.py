@@ -31,10 +31,18 @@ class _Token:
     __slots__ = ("__weakref__",)
 
 
+_live_nets: "weakref.WeakSet" = weakref.WeakSet()     # every live BucketedNet: nerve_cl.optim finds a parameter's network here
+
+
 class BucketedNet(nn.Module):
     """Mixin-style base: bucket layout, gradient bucket, flat parameter view, deferred bucket additions."""
 
+    def __setstate__(self, state) -> None:
+        super().__setstate__(state)
+        _live_nets.add(self)                   # a deepcopy / unpickled network never ran _init_bucket
+
     def _init_bucket(self) -> None:
+        _live_nets.add(self)
         self._param_names: List[str] = [n for n, _ in self.named_parameters()]
         self._grad_bucket_hook = None          # data-parallel all-reduce (nerve_cl.parallel)
         self._last_grad_bucket: Optional[torch.Tensor] = None

@@ -227,6 +227,8 @@ SIGNATURES = {
     "nvq_bucket_moments": (ci, [vp, vp, cl, vp, ci, ci, vp, sz, vp]),
     "nvq_bucket_project": (ci, [vp, vp, cl, vp, vp]),
     "nvq_bucket_clip": (ci, [vp, cl, vp, cf, vp, vp]),
+    # Adam / AdamW with clipping and weight EMA on flat buffers (csrc/optim.hip)
+    "nvq_adam_step": (ci, [vp, vp, vp, vp, vp, cl, cf, cf, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, cf, vp]),
     # device-resident episodic memory (csrc/replay.hip)
     "nvq_replay_store": (ci, [vp, vp, ci, cl, cl, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
     "nvq_replay_gather": (ci, [vp, vp, ci, ci, cl, cl, vp, ci, vp, vp, ci, vp, vp]),
@@ -1311,6 +1313,22 @@ def bucket_clip(g: torch.Tensor, acc: torch.Tensor, max_norm: float, norm_out: O
     assert g.dtype == torch.float32
     check(lib().nvq_bucket_clip(ptr(g), g.numel(), _bucket_acc(acc), float(max_norm), ptr(norm_out), stream()),
           "nvq_bucket_clip")
+
+
+def adam_step(theta: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+              ema: Optional[torch.Tensor], *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+              decoupled: bool, step: int, ema_decay: float = 0.0, acc: Optional[torch.Tensor] = None, max_norm: float = 0.0):
+    """One Adam / AdamW step number ``step`` (>= 1) on flat fp32 tensors in place (nvq_adam_step): optional clipping from
+    ``acc`` (the 5 float64 slots of bucket_moments; ``grad`` is not written) and optional weight EMA.  The bias corrections
+    and 1 - beta are formed here in double, as torch forms its scalars."""
+    n = theta.numel()
+    for t in (theta, grad, exp_avg, exp_avg_sq) + ((ema,) if ema is not None else ()):
+        assert t.dtype == torch.float32 and t.numel() == n, "adam_step: fp32 tensors of one size"
+    bias1 = 1.0 - beta1 ** step
+    bias2_sqrt = (1.0 - beta2 ** step) ** 0.5
+    check(lib().nvq_adam_step(ptr(theta), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), ptr(ema), n, lr, beta1, beta2, 1.0 - beta1,
+                              1.0 - beta2, eps, weight_decay, int(decoupled), bias1, bias2_sqrt, ema_decay,
+                              _bucket_acc(acc) if acc is not None else None, max_norm, stream()), "nvq_adam_step")
 
 
 # ----------------------------------------------------------------------------- device-resident episodic memory

@@ -45,15 +45,52 @@ def pick_device():
     return torch.device("cuda", local), rank, world
 
 
-def make_optimizer(cls, params, **kw):
-    """The reference's `torch.optim.Adam / AdamW(model.parameters(), ...)` call (train_continual.py:27,51, train_baseline.py:41)
-    with PyTorch's fused single-kernel implementation when every parameter is an fp32 tensor on the GPU: the same update rule;
-    the default (foreach) form is ~10 launches and 0.6 ms of host time per step over the network's 131 tensors, which the
-    launch-bound 64x64 steps feel."""
+OPTIMIZER_IMPLS = ("torch", "bucket")
+
+
+def make_optimizer(cls, params, impl: str = "torch", **kw):
+    """The reference's `torch.optim.Adam / AdamW(model.parameters(), ...)` call (train_continual.py:27,51, train_baseline.py:41).
+
+    impl "torch" (the default): PyTorch's fused single-kernel implementation when every parameter is an fp32 tensor on the GPU:
+    the same update rule; the default (foreach) form is ~10 launches and 0.6 ms of host time per step over the network's 131
+    tensors, which the launch-bound 64x64 steps feel.
+
+    impl "bucket": nerve_cl.optim.BucketAdam / BucketAdamW for Adam / AdamW - the same rule as one libnvq launch per run of
+    parameters on the flat buckets; takes max_grad_norm= / ema_decay= / model= on top of torch's arguments."""
+    if impl == "bucket":
+        from nerve_cl import optim
+        bucket = {torch.optim.Adam: optim.BucketAdam, torch.optim.AdamW: optim.BucketAdamW}.get(cls)
+        if bucket is None:
+            raise NotImplementedError(f"--optimizer-impl bucket: no flat-bucket form of {cls.__name__} (Adam and AdamW only)")
+        return bucket(params, **kw)
+    if impl != "torch":
+        raise ValueError(f"optimizer impl {impl!r}: one of {OPTIMIZER_IMPLS}")
     params = list(params)
     if params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         kw.setdefault("fused", True)
     return cls(params, **kw)
+
+
+def add_optimizer_arguments(ap, ema_note: str = "evaluate / save with it") -> None:
+    """--optimizer-impl / --ema-decay of the training scripts; ema_note: what the script does with the average"""
+    ap.add_argument("--optimizer-impl", choices=OPTIMIZER_IMPLS, default="torch",
+                    help="torch: torch.optim's fused Adam (default); bucket: nerve_cl.optim on the flat parameter / gradient "
+                         "buckets, one launch per step")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights with decay D inside the optimizer launch and "
+                         f"{ema_note} (implies --optimizer-impl bucket)")
+
+
+def optimizer_impl(args) -> str:
+    return "bucket" if getattr(args, "ema_decay", None) is not None else getattr(args, "optimizer_impl", "torch")
+
+
+def ema_weights(optimizer):
+    """Context for an evaluation pass: the optimizer's weight average in place of the weights (nothing without --ema-decay)"""
+    import contextlib
+    if getattr(optimizer, "ema_decay", None) is not None:
+        return optimizer.swap_ema()
+    return contextlib.nullcontext()
 
 
 def shard(n: int, rank: int, world: int) -> slice:

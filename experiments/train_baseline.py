@@ -4,6 +4,7 @@ T=3 `expand` trick, progress line and best-checkpoint rule as the reference's
 experiments/train_baseline.py (:35-147), running on libnvq.  Launch with torch.distributed.run for
 data-parallel training (each rank trains on its shard; gradients are all-reduced inside backward)."""
 import argparse
+import copy
 import time
 from pathlib import Path
 
@@ -12,7 +13,8 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
-from _common import LOSS_CHOICES, compute_psnr, make_optimizer, pick_device, resolve_loss, shard
+from _common import (LOSS_CHOICES, add_optimizer_arguments, compute_psnr, ema_weights, make_optimizer, optimizer_impl, pick_device,
+                     resolve_loss, shard)
 from nerve_cl import metrics, ops, parallel
 from nerve_cl.models import SuperResolutionNet
 
@@ -43,7 +45,9 @@ def train(args) -> None:
     if world > 1:
         model = parallel.enable_data_parallel(model, sync_bn=args.sync_bn)
     say(f"  Parameters: {sum(p.numel() for p in model.parameters()):,}")
-    optimizer = make_optimizer(torch.optim.AdamW, model.parameters(), lr=args.lr, weight_decay=1e-5)
+    impl = optimizer_impl(args)
+    extra_kw = dict(ema_decay=args.ema_decay, model=model) if impl == "bucket" else {}
+    optimizer = make_optimizer(torch.optim.AdamW, model.parameters(), impl, lr=args.lr, weight_decay=1e-5, **extra_kw)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=args.epochs)
     # nn.MSELoss() of the reference, as libnvq kernels; --loss picks another libnvq loss
     criterion = ops.MSELoss() if args.loss == "mse" else resolve_loss(args.loss)
@@ -66,7 +70,7 @@ def train(args) -> None:
         model.eval()
         val_loss = val_psnr = 0.0
         meter = metrics.QualityMeter() if args.metrics else None
-        with torch.no_grad():
+        with torch.no_grad(), ema_weights(optimizer):       # --ema-decay: validate the weight average
             for lr, hr in val_loader:
                 lr, hr = lr.to(device), hr.to(device)
                 out = model(as_clip(lr))
@@ -92,7 +96,11 @@ def train(args) -> None:
             if world > 1:
                 parallel.average_bn_buffers_(model)
             if rank == 0:
-                torch.save({"epoch": epoch, "model_state_dict": model.state_dict(),
+                model_state = model.state_dict()
+                if args.ema_decay is not None:              # the checkpoint holds the weights that were validated
+                    with ema_weights(optimizer):
+                        model_state = copy.deepcopy(model_state)
+                torch.save({"epoch": epoch, "model_state_dict": model_state,
                             "optimizer_state_dict": optimizer.state_dict(), "psnr": best_psnr},
                            "checkpoints/best_model.pt")
     say("-" * 60)
@@ -114,6 +122,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="training and validation loss (libnvq kernels; default: the reference's MSE)")
     ap.add_argument("--metrics", action="store_true",
                     help="add the global-statistics SSIM and the MAE of the validation set to the progress line")
+    add_optimizer_arguments(ap)
     return ap
 
 

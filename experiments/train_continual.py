@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, TensorDataset
 
-from _common import LOSS_CHOICES, make_optimizer, pick_device, resolve_loss, shard
+from _common import (LOSS_CHOICES, add_optimizer_arguments, ema_weights, make_optimizer, optimizer_impl, pick_device, resolve_loss,
+                     shard)
 from nerve_cl import metrics, ops, parallel
 from nerve_cl.continual import AGEM, EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
@@ -81,10 +82,21 @@ def make_criterion(config):
     return ops.MSELoss() if name == "mse" else resolve_loss(name)
 
 
+def build_optimizer(model, config):
+    """Adam(lr=1e-4) of the reference through --optimizer-impl; the bucket form takes --clip-grad-norm as its max_grad_norm (the
+    clip then costs no pass of its own and leaves .grad unscaled) and --ema-decay."""
+    impl = config.get("optimizer_impl", "torch")
+    kw = {}
+    if impl == "bucket":
+        kw = dict(max_grad_norm=config.get("clip_grad_norm"), ema_decay=config.get("ema_decay"), model=model)
+    return make_optimizer(torch.optim.Adam, model.parameters(), impl, lr=1e-4, **kw)
+
+
 def clip_gradients(model, config) -> None:
-    """--clip-grad-norm: global 2-norm clipping on the gradient buckets, no host read (nothing without the flag)"""
+    """--clip-grad-norm: global 2-norm clipping on the gradient buckets, no host read (nothing without the flag, and nothing
+    with --optimizer-impl bucket, whose update launch clips)"""
     max_norm = config.get("clip_grad_norm")
-    if max_norm is not None:
+    if max_norm is not None and config.get("optimizer_impl", "torch") != "bucket":
         ops.clip_grad_norm_(model, max_norm)
 
 
@@ -98,11 +110,12 @@ def metrics_suffix(meter, world: int = 1) -> str:
     return f" SSIM={m['ssim_global']:.4f} MAE={m['mae']:.4f}"
 
 
-def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
+def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5, optimizer=None):
     device = next(model.parameters()).device
     adapter = _ClipAdapter(model)
     ewc = EWC(adapter, ewc_lambda=config.get("ewc_lambda", 5000))
-    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    if optimizer is None:
+        optimizer = build_optimizer(model, config)
     criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
@@ -132,9 +145,10 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5):
     return model
 
 
-def train_with_replay(model, tasks, memory, config, rank=0, epochs=5):
+def train_with_replay(model, tasks, memory, config, rank=0, epochs=5, optimizer=None):
     device = next(model.parameters()).device
-    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    if optimizer is None:
+        optimizer = build_optimizer(model, config)
     criterion = make_criterion(config)
     on_device = isinstance(memory, DeviceEpisodicMemory)
     prioritized = bool(config.get("prioritized"))
@@ -185,10 +199,11 @@ def store_task(memory, lr, hr, task_name) -> None:
             memory.store(lr[i], hr[i], metadata={"content_type": task_name})
 
 
-def train_with_agem(model, tasks, memory, config, rank=0, epochs=5):
+def train_with_agem(model, tasks, memory, config, rank=0, epochs=5, optimizer=None):
     """Shaped like train_with_replay: the memory's samples are not mixed into the batch, their gradient constrains the step's."""
     device = next(model.parameters()).device
-    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    if optimizer is None:
+        optimizer = build_optimizer(model, config)
     criterion = make_criterion(config)
     adapter = _ClipAdapter(model)
     agem = AGEM(adapter, memory, ref_batch_size=config.get("agem_ref_batch", 8))
@@ -217,13 +232,14 @@ def train_with_agem(model, tasks, memory, config, rank=0, epochs=5):
     return model
 
 
-def train_with_distill(model, tasks, config, rank=0, epochs=5):
+def train_with_distill(model, tasks, config, rank=0, epochs=5, optimizer=None):
     """Single process, unsharded.  With the MSE criterion the task term is folded into the distillation kernel (fold_task)."""
     device = next(model.parameters()).device
     distill = ContinualDistillation(_SRClipAdapter(model.super_resolution), alpha=config.get("distill_alpha", 0.5),
                                     feature_weight=config.get("feature_distill", 0.0),
                                     fold_task=config.get("loss", "mse") == "mse" and config.get("fold_task", True))
-    optimizer = make_optimizer(torch.optim.Adam, model.parameters(), lr=1e-4)
+    if optimizer is None:
+        optimizer = build_optimizer(model, config)
     criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
@@ -287,6 +303,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --device-memory: element type of the stored samples (bf16 halves the footprint)")
     ap.add_argument("--prioritized", action="store_true",
                     help="with --device-memory: per-sample losses of the replay rows update their importances (momentum 0.9) and replay draws are weighted by them")
+    add_optimizer_arguments(ap, ema_note="write it to checkpoints/continual_model_ema.pt at the end (this script has no "
+                                         "evaluation pass to run under it)")
     return ap
 
 
@@ -295,6 +313,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.prioritized and not args.device_memory:
         ap.error("--prioritized needs --device-memory")
+    if args.strategy == "maml" and (args.ema_decay is not None or args.optimizer_impl != "torch"):
+        ap.error("--strategy maml trains nothing: --optimizer-impl / --ema-decay have no effect there")
 
     device, rank, world = pick_device()
     torch.manual_seed(0)
@@ -307,9 +327,11 @@ def main() -> None:
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
     config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized,
               "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill,
-              "agem_ref_batch": args.agem_ref_batch, "clip_grad_norm": args.clip_grad_norm}
+              "agem_ref_batch": args.agem_ref_batch, "clip_grad_norm": args.clip_grad_norm,
+              "optimizer_impl": optimizer_impl(args), "ema_decay": args.ema_decay}
+    optimizer = build_optimizer(model, config)      # (the reference loops each build their own; the steps are the same)
     if args.strategy == "ewc":
-        model = train_with_ewc(model, tasks, config, rank, world, args.epochs)
+        model = train_with_ewc(model, tasks, config, rank, world, args.epochs, optimizer=optimizer)
     elif args.strategy in ("replay", "agem"):
         if args.device_memory:
             memory = DeviceEpisodicMemory(capacity=args.memory_size, strategy="stratified", device=device,
@@ -317,15 +339,18 @@ def main() -> None:
         else:
             memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
         train = train_with_replay if args.strategy == "replay" else train_with_agem
-        model = train(model, tasks, memory, config, rank, args.epochs)
+        model = train(model, tasks, memory, config, rank, args.epochs, optimizer=optimizer)
     elif args.strategy == "distill":
         if world > 1:
             ap.error("--strategy distill runs in a single process")
-        model = train_with_distill(model, tasks, config, rank, args.epochs)
+        model = train_with_distill(model, tasks, config, rank, args.epochs, optimizer=optimizer)
     # ('maml' has no branch in the reference either: it saves the untrained model)
     if rank == 0:
         Path("checkpoints").mkdir(exist_ok=True)
         torch.save(model.state_dict(), "checkpoints/continual_model.pt")
+        if args.ema_decay is not None:                 # the weight average, for evaluation
+            with ema_weights(optimizer):
+                torch.save(model.state_dict(), "checkpoints/continual_model_ema.pt")
         print("\nTraining complete!")
 
 

@@ -793,6 +793,26 @@ int nvq_bucket_project(float* g, const float* r, long n, const double* acc, void
  * g[i] *= coef only when coef < 1, otherwise g is untouched.  *norm_out (device, may be NULL) = the total norm. */
 int nvq_bucket_clip(float* g, long n, const double* acc, float max_norm, float* norm_out, void* stream);
 
+/* ------------------------------------------------------------------ Adam / AdamW on flat buffers (csrc/optim.hip)
+ * torch.optim.Adam / AdamW (amsgrad = False, maximize = False) over n floats of theta, grad, exp_avg (m), exp_avg_sq (v) and,
+ * when ema != NULL, an exponential moving average of theta, in one launch.  Per element, every operation rounded once:
+ *   clip      acc != NULL (the 5 doubles of nvq_bucket_moments): coef = max_norm / (sqrt(acc[2]) + 1e-6);
+ *             g = grad * (float)coef only when coef < 1 (a NaN compares false: unscaled), as nvq_bucket_clip decides; else g = grad.
+ *             grad itself is never written.
+ *   decay     decoupled (AdamW): theta *= (float)(1 - lr * weight_decay);  else (L2): g = fma(weight_decay, theta, g)
+ *   moments   m = fma(g - m, one_minus_beta1, m);  v = fma(one_minus_beta2 * g, g, beta2 * v)
+ *   update    theta = fma(-(float)(lr / bias1), m / (sqrt(v) / bias2_sqrt + eps), theta)
+ *   ema       ema = fma(theta - ema, (float)(1 - ema_decay), ema)      [= ema_decay * ema + (1 - ema_decay) * theta]
+ * bias1 = 1 - beta1^t, bias2_sqrt = sqrt(1 - beta2^t), one_minus_beta1 = 1 - beta1 and one_minus_beta2 = 1 - beta2 are formed by
+ * the caller in double from the integer step count t and the betas and passed rounded to float, as torch's scalars are (1 - beta2
+ * formed from a float beta2 would be off by 2^-16 relative at beta2 = 0.999).
+ * The pointers need 4-byte alignment only: float4 accesses when all of them are 16-byte aligned, else four scalar accesses of the
+ * same quads - the same bits either way.  The grid depends on n only; no atomics, no workspace.  n == 0 succeeds without a
+ * launch.  Zeros in theta, grad, m, v and ema (bucket padding) stay exactly zero. */
+int nvq_adam_step(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, long n, float lr, float beta1,
+                  float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, int decoupled,
+                  float bias1, float bias2_sqrt, float ema_decay, const double* acc, float max_norm, void* stream);
+
 /* ------------------------------------------------------------------ device-resident episodic memory (csrc/replay.hip)
  * The memory is a set of caller-owned tables with `capacity` rows (capacity <= 65536): lr_store [capacity][lr_per] and
  * hr_store [capacity][hr_per] (fp32, or bf16 when store_bf16), means [capacity][channels] fp32 (per-channel mean of the LR
