@@ -13,6 +13,9 @@ Every such network is ONE autograd node whose backward writes all parameter grad
 For the last point the parameters themselves must be readable as one flat tensor in the same layout: ``flat_theta()``
 re-homes every ``param.data`` as a view of one persistent buffer (checked by address on every call, rebuilt after
 ``.to()`` / ``deepcopy``; in-place optimizer and ``load_state_dict`` updates keep it valid).
+
+Below the class is what the consumers of the gradient bucket share (EWC, SynapticIntelligence, AGEM, ``ops.clip_grad_norm_``,
+``optim.BucketAdam``); ``BucketedNet.grad_alias_mask()`` is the one place that compares addresses.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from nerve_cl import _nvq
+from nerve_cl import _nvq, parallel
 
 
 class _Token:
@@ -57,7 +60,7 @@ class BucketedNet(nn.Module):
         with add_module): the cached parameter / buffer slots, the bucket layout, the parameter names, the backward plans and
         the synchronised-BatchNorm list are rebuilt on their next use."""
         d = self.__dict__
-        for k in ("_slot_cache", "_sync_cache", "_plan_cache"):
+        for k in ("_slot_cache", "_sync_cache", "_plan_cache", "_alias_cache"):
             d.pop(k, None)
         if "_layout" in d:
             d["_layout"] = None
@@ -138,6 +141,24 @@ class BucketedNet(nn.Module):
         flat = torch.zeros(total, dtype=torch.float32, device=dev)
         return flat, self._bucket_views(flat)
 
+    def grad_alias_mask(self) -> Optional[List[bool]]:
+        """Per parameter, in bucket order: is its ``.grad`` the fp32 view of ``_last_grad_bucket`` at its slot (the plain
+        zero_grad -> backward -> step loop; not after gradient accumulation)?  None without a usable bucket: none yet, or one on
+        another device, of another size or type.  The bucket IS the gradients when ``mask is not None and all(mask)``."""
+        bucket = self._last_grad_bucket
+        if bucket is None:
+            return None
+        c = self.__dict__.get("_alias_cache")          # [(owner._parameters, key, byte offset of the slot)], see _slots()
+        if c is None:
+            c = [(d, k, 4 * o) for (_, d, k), (o, _) in zip(self._slots()[0], self._bucket_layout()[0].values())]
+            self.__dict__["_alias_cache"] = c
+        d0, k0, _ = c[0]
+        f32 = torch.float32
+        if bucket.device != d0[k0].device or bucket.numel() != self._bucket_layout()[1] or bucket.dtype != f32:
+            return None
+        base = bucket.data_ptr()                       # every step runs this loop: one .grad read per parameter
+        return [(g := d[k].grad) is not None and g.data_ptr() == base + o and g.dtype is f32 for d, k, o in c]
+
     # ------------------------------------------------------------------ flat parameters
     def flat_theta(self) -> torch.Tensor:
         """All parameters as one flat fp32 tensor in bucket layout (padding = 0); the parameters are views of it."""
@@ -190,3 +211,130 @@ class BucketedNet(nn.Module):
             self._deferred_adds = []
         self._pending = None
         self._last_grad_bucket = flat
+
+
+class Segment:
+    """One flat bucket of a module's trainable parameters: either all parameters of one bucketed network (``net`` set: Fisher /
+    theta* / A-GEM's reference are stored in that network's gradient-bucket layout, so a kernel over the bucket needs no
+    gather) or a plain concatenation of loose parameters (``net`` None: e.g. the engine's ``enhancement_strength``)."""
+
+    def __init__(self, net: Optional[BucketedNet], named: "List[tuple]"):
+        self.net, self.named = net, named          # named: [(full name, parameter)]
+        self.names = [n for n, _ in named]
+
+    def numel(self) -> int:
+        if self.net is not None:
+            return self.net._bucket_layout()[1]
+        return sum(p.numel() for _, p in self.named)
+
+    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        if self.net is None:
+            parts = flat.split([p.numel() for _, p in self.named])
+            return {n: v.view(p.shape) for (n, p), v in zip(self.named, parts)}
+        local = self.net._bucket_views(flat)
+        return {full: local[loc] for (full, _), loc in zip(self.named, self.net._param_names)}
+
+    def theta(self) -> torch.Tensor:
+        if self.net is not None:
+            return self.net.flat_theta()           # persistent flat view of the parameters: no per-step cat
+        return torch.cat([p.detach().reshape(-1).float() for _, p in self.named])
+
+    def aliased(self) -> bool:
+        """a bucketed network whose last gradient bucket IS its gradients (``grad_alias_mask``)"""
+        mask = self.net.grad_alias_mask() if self.net is not None else None
+        return mask is not None and all(mask)
+
+    def grads(self) -> Optional[torch.Tensor]:
+        """Flat gradient of the last backward in this segment's layout (None when nothing arrived)."""
+        if self.aliased():
+            return self.net._last_grad_bucket
+        if all(p.grad is None for _, p in self.named):
+            return None
+        flat = torch.zeros(self.numel(), dtype=torch.float32, device=self.named[0][1].device)
+        views = self.views(flat)
+        for n, p in self.named:
+            if p.grad is not None:
+                views[n].copy_(p.grad.detach())
+        return flat
+
+
+def segments_of(model: nn.Module) -> "List[Segment]":
+    """Split model.named_parameters() (requires_grad only, reference ewc.py:67-71) into bucketed networks + loose rest.  A
+    network with a frozen parameter is no segment: its parameters are loose.  The walk costs > 1 ms: consumers keep the result."""
+    owner: Dict[int, "tuple[BucketedNet, str]"] = {}
+    for prefix, m in model.named_modules():
+        if isinstance(m, BucketedNet) and all(p.requires_grad for p in m.parameters()):
+            for p in m.parameters():
+                owner.setdefault(id(p), (m, prefix))
+    segs: "Dict[int, Segment]" = {}
+    order: "List[Segment]" = []
+    loose: "List[tuple]" = []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        own = owner.get(id(p))
+        if own is None:
+            loose.append((name, p))
+            continue
+        net = own[0]
+        if id(net) not in segs:
+            segs[id(net)] = Segment(net, [])
+            order.append(segs[id(net)])
+        segs[id(net)].named.append((name, p))
+    for sg in order:
+        sg.names = [n for n, _ in sg.named]
+        assert len(sg.named) == len(sg.net._param_names)
+    if loose:
+        order.append(Segment(None, loose))
+    return order
+
+
+def flat_grad(g: torch.Tensor) -> "Tuple[torch.Tensor, Optional[torch.Tensor]]":
+    """(flat, dst): the gradient's own memory as ``view(-1)`` and None when it is contiguous and fp32 (on the CPU, where the
+    torch compositions run: of any type), else a contiguous fp32 copy and ``g``, for a caller that changes the copy to write back."""
+    g = g.detach()
+    want = torch.float32 if g.is_cuda else g.dtype
+    if g.dtype == want and g.is_contiguous():
+        return g.view(-1), None
+    return g.to(want).contiguous().view(-1), g
+
+
+def refuse_loose_gradients(named, what: str, group=None) -> None:
+    """``named``: the loose (name, parameter) pairs.  Data parallel: the bucket hook leaves the same averaged gradient on every
+    rank, but nothing synchronises a gradient outside the bucketed networks - the ranks would form different sums and drift."""
+    if parallel.world_size(group) > 1:
+        for n, p in named:
+            if p.grad is not None:
+                raise RuntimeError(f"{what}: parameter {n!r} lies outside the bucketed networks and carries a gradient; this "
+                                   "package does not synchronise such gradients over the ranks, so every rank would compute "
+                                   "a different result")
+
+
+def grad_pairs(segs: "List[Segment]", refs: "Optional[List[torch.Tensor]]", what: str, group=None) -> "List[Tuple]":
+    """[(g, r, dst)]: the flat gradients the kernels update in place, each with its slice of the reference (None without
+    ``refs``).  A bucketed network whose ``.grad`` tensors are the views of its last gradient bucket is ONE pair, the bucket
+    itself; otherwise (loose parameters, gradients accumulated over several backwards) one pair per parameter that has a
+    gradient, with ``flat_grad``'s ``dst``."""
+    out = []
+    for i, sg in enumerate(segs):
+        if sg.net is None:
+            refuse_loose_gradients(sg.named, what, group)
+        ref = refs[i] if refs is not None else None
+        if sg.aliased():
+            out.append((sg.net._last_grad_bucket, ref, None))
+            continue
+        views = sg.views(ref) if ref is not None else None
+        for n, p in sg.named:
+            if p.grad is not None and p.numel():
+                g, dst = flat_grad(p.grad)
+                out.append((g, views[n].view(-1) if views is not None else None, dst))
+    return out
+
+
+def sum_moments(pairs, acc: torch.Tensor, ws: torch.Tensor, coefficient: bool = False) -> None:
+    """acc[0..2] = g.r, r.r, g.g over ``pairs`` (``grad_pairs`` tuples, or bare flat gradients: g.g only), one ``nvq_bucket_moments``
+    each, all but the first accumulating; ``coefficient``: the last one forms A-GEM's c in acc[3].  Under the caller's guard."""
+    last = len(pairs) - 1
+    for k, pair in enumerate(pairs):
+        g, r = pair[:2] if isinstance(pair, tuple) else (pair, None)
+        _nvq.bucket_moments(g, r, acc, ws, accumulate=k > 0, coefficient=coefficient and k == last)

@@ -22,80 +22,7 @@ import torch
 import torch.nn as nn
 
 from nerve_cl import _engine, _nvq, ops, parallel
-from nerve_cl._bucket import BucketedNet
-
-
-def _flat_views(flat: torch.Tensor, named: "List[tuple]") -> Dict[str, torch.Tensor]:
-    out, off = {}, 0
-    for name, p in named:
-        out[name] = flat[off:off + p.numel()].view(p.shape)
-        off += p.numel()
-    return out
-
-
-class _Segment:
-    """One flat bucket of the penalty: either all parameters of one bucketed network (``net`` set: Fisher / theta* are
-    stored in that network's gradient-bucket layout, so the penalty gradient is ONE accumulate kernel into the bucket) or
-    a plain concatenation of loose parameters (``net`` None: e.g. the engine's ``enhancement_strength``)."""
-
-    def __init__(self, net: Optional[BucketedNet], named: "List[tuple]"):
-        self.net, self.named = net, named          # named: [(full name, parameter)]
-        self.names = [n for n, _ in named]
-
-    def numel(self) -> int:
-        if self.net is not None:
-            return self.net._bucket_layout()[1]
-        return sum(p.numel() for _, p in self.named)
-
-    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        if self.net is None:
-            return _flat_views(flat, self.named)
-        local = self.net._bucket_views(flat)
-        return {full: local[loc] for (full, _), loc in zip(self.named, self.net._param_names)}
-
-    def theta(self) -> torch.Tensor:
-        if self.net is not None:
-            return self.net.flat_theta()           # persistent flat view of the parameters: no per-step cat
-        return torch.cat([p.detach().reshape(-1).float() for _, p in self.named])
-
-    def grads(self) -> Optional[torch.Tensor]:
-        """Flat gradient of the last backward in this segment's layout (None when nothing arrived)."""
-        if self.net is not None:
-            return self.net._last_grad_bucket
-        if all(p.grad is None for _, p in self.named):
-            return None
-        return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
-                          for _, p in self.named])
-
-
-def segments_of(model: nn.Module) -> "List[_Segment]":
-    """Split model.named_parameters() (requires_grad only, reference ewc.py:67-71) into bucketed networks + loose rest."""
-    owner: Dict[int, "tuple[BucketedNet, str]"] = {}
-    for prefix, m in model.named_modules():
-        if isinstance(m, BucketedNet) and all(p.requires_grad for p in m.parameters()):
-            for p in m.parameters():
-                owner.setdefault(id(p), (m, prefix))
-    segs: "Dict[int, _Segment]" = {}
-    order: "List[_Segment]" = []
-    loose: "List[tuple]" = []
-    for name, p in model.named_parameters():
-        if not p.requires_grad:
-            continue
-        own = owner.get(id(p))
-        if own is None:
-            loose.append((name, p))
-            continue
-        net = own[0]
-        if id(net) not in segs:
-            segs[id(net)] = _Segment(net, [])
-            order.append(segs[id(net)])
-        segs[id(net)].named.append((name, p))
-    for sg in order:
-        sg.names = [n for n, _ in sg.named]
-        assert len(sg.named) == len(sg.net._param_names)
-    if loose:
-        order.append(_Segment(None, loose))
-    return order
+from nerve_cl._bucket import BucketedNet, Segment, flat_grad, segments_of
 
 
 class _PenaltyFn(torch.autograd.Function):
@@ -109,7 +36,7 @@ class _PenaltyFn(torch.autograd.Function):
     views are returned."""
 
     @staticmethod
-    def forward(ctx, seg: _Segment, lam: float, star: torch.Tensor, fisher: torch.Tensor, *params):
+    def forward(ctx, seg: Segment, lam: float, star: torch.Tensor, fisher: torch.Tensor, *params):
         theta = seg.theta() if seg is not None else torch.cat([p.detach().reshape(-1).float() for p in params])
         out = torch.empty(1, dtype=torch.float32, device=theta.device)
         with _nvq.device_guard(theta.device):
@@ -163,7 +90,7 @@ class EWC:
         # key ('online' | task id) -> [(segment, fisher_flat, optpar_flat)]
         self._flat: Dict[object, "List[tuple]"] = {}
         self._live: Dict[object, "List[bool]"] = {}      # per key: which segments ever received a gradient
-        self._segs: "Optional[List[_Segment]]" = None
+        self._segs: "Optional[List[Segment]]" = None
 
     # ------------------------------------------------------------------ helpers
     def _get_params(self) -> Iterator[tuple]:
@@ -171,7 +98,7 @@ class EWC:
             if param.requires_grad:
                 yield name, param
 
-    def _segments(self) -> "List[_Segment]":
+    def _segments(self) -> "List[Segment]":
         if self._segs is None:
             self._segs = segments_of(self.model)
         return self._segs
@@ -412,33 +339,20 @@ class SynapticIntelligence:
             self.omega.update(sg.views(o))
             self.p_old.update(sg.views(p))
 
-    @staticmethod
-    def _bucket_is_grad(sg: _Segment) -> bool:
-        """Are the parameters' .grad tensors the views of the network's last gradient bucket (the plain zero_grad ->
-        backward -> step loop)?  Otherwise (gradient accumulation over several backwards) .grad is gathered instead."""
-        flat = sg.net._last_grad_bucket
-        if flat is None:
-            return False
-        lay, _ = sg.net._bucket_layout()
-        base = flat.data_ptr()
-        for (_, p), loc in zip(sg.named, sg.net._param_names):
-            if p.grad is None or p.grad.data_ptr() != base + 4 * lay[loc][0]:
-                return False
-        return True
-
     def update_importance(self) -> None:
-        """Call after each optimizer step (parameters without a gradient contribute nothing, as in the reference)."""
+        """Call after each optimizer step (parameters without a gradient contribute nothing, as in the reference).  One launch on
+        the gradient bucket while ``.grad`` aliases it; loose parameters and accumulated gradients go per tensor."""
         for sg, W, p_old in zip(self._segs, self._W, self._p_old):
             theta = sg.theta()
             with _nvq.device_guard(theta.device):
-                if sg.net is not None and self._bucket_is_grad(sg):
+                if sg.aliased():
                     _nvq.si_update(theta, sg.net._last_grad_bucket, p_old, W)
                     continue
                 views_w, views_p = sg.views(W), sg.views(p_old)
-                for n, p in sg.named:                         # loose parameters / accumulated gradients: per tensor
+                for n, p in sg.named:
                     if p.grad is not None and p.numel() > 0:
-                        g = p.grad.detach().float().contiguous()
-                        _nvq.si_update(p.detach().float().contiguous(), g, views_p[n].view(-1), views_w[n].view(-1))
+                        _nvq.si_update(p.detach().float().contiguous(), flat_grad(p.grad)[0], views_p[n].view(-1),
+                                       views_w[n].view(-1))
 
     def register_task(self) -> None:
         for sg, W, p_old, omega in zip(self._segs, self._W, self._p_old, self._omega):

@@ -21,12 +21,14 @@ are csrc/distill.hip; their gradient is with respect to the s
 """
 from __future__ import annotations
 
+import weakref
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
 
 from nerve_cl import _engine, _nvq
+from nerve_cl._bucket import Segment, grad_pairs, segments_of, sum_moments
 
 
 class _MSEFn(torch.autograd.Function):
@@ -485,6 +487,9 @@ class CosineFeatureLoss(_Reduced):
 LOSSES = {"mse": mse_loss, "l1": l1_loss, "charbonnier": charbonnier_loss, "ssim": ssim_loss}
 
 
+_clip_segments: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()      # module -> its segments (the walk costs > 1 ms)
+
+
 def clip_grad_norm_(module_or_parameters, max_norm: float, refresh: bool = False) -> torch.Tensor:
     """``torch.nn.utils.clip_grad_norm_`` for the 2-norm, in place: every gradient is scaled by ``max_norm / (total_norm + 1e-6)``
     when that is below 1 and left untouched otherwise.  Returns the total norm as a 0-dim tensor on the gradients' device; the
@@ -498,5 +503,25 @@ def clip_grad_norm_(module_or_parameters, max_norm: float, refresh: bool = False
 
     A module's split into bucketed networks and loose parameters is worked out on the first call and kept (as ``AGEM`` and ``EWC``
     keep theirs from construction); ``refresh=True`` repeats it after parameters were added to or removed from the module."""
-    from nerve_cl.continual.agem import clip_grad_norm_ as impl       # (nerve_cl.continual imports this module)
-    return impl(module_or_parameters, max_norm, refresh)
+    if isinstance(module_or_parameters, nn.Module):
+        segs = None if refresh else _clip_segments.get(module_or_parameters)
+        if segs is None:
+            segs = _clip_segments[module_or_parameters] = segments_of(module_or_parameters)
+        params = [p for sg in segs for _, p in sg.named]
+    else:
+        params = [module_or_parameters] if isinstance(module_or_parameters, torch.Tensor) else list(module_or_parameters)
+        segs = [Segment(None, [(str(i), p) for i, p in enumerate(params)])]
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads or not grads[0].is_cuda:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm)
+    dev = grads[0].device
+    pairs = grad_pairs(segs, None, "clip_grad_norm_")
+    acc = torch.empty(5, dtype=torch.float64, device=dev)        # the first moments call writes the slots that are read
+    norm = torch.empty((), dtype=torch.float32, device=dev)
+    with _nvq.device_guard(dev):
+        sum_moments(pairs, acc, _engine.workspace(dev))
+        for g, _, dst in pairs:
+            _nvq.bucket_clip(g, acc, float(max_norm), norm)
+            if dst is not None:
+                dst.copy_(g.view(dst.shape))
+    return norm

@@ -29,8 +29,8 @@ import torch
 import torch.nn as nn
 from torch.optim import Optimizer
 
-from nerve_cl import _engine, _nvq, parallel
-from nerve_cl._bucket import BucketedNet, _live_nets
+from nerve_cl import _engine, _nvq
+from nerve_cl._bucket import BucketedNet, _live_nets, flat_grad, refuse_loose_gradients, sum_moments
 
 __all__ = ["BucketAdam", "BucketAdamW", "Slot", "plan_runs"]
 
@@ -239,33 +239,20 @@ class BucketAdam(Optimizer):
         return st
 
     # ------------------------------------------------------------------ step
-    @staticmethod
-    def _flat_grad(g: torch.Tensor) -> torch.Tensor:
-        g = g.detach()
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()          # a copy: the update never writes the gradient
-        return g.view(-1)
-
     def _collect(self) -> list:
         """[(theta, grad, exp_avg, exp_avg_sq, ema or None, group, step number)]: flat fp32 tensors, one entry per launch; the
-        step counts are advanced here (``_refuse()`` has run)."""
+        step counts are advanced here (``_refuse()`` has run).  A gradient that is not fp32 or not contiguous is read from
+        ``flat_grad``'s copy; nothing is copied back, the update never writes the gradient."""
         work = []
         for ns in self._nets:
             net = ns.net
             flat = net.flat_theta()
             self._home(ns, flat)
             bucket = net._last_grad_bucket
-            bbase = None
-            if flat.is_cuda and bucket is not None and bucket.device == flat.device and bucket.numel() == ns.total \
-                    and bucket.dtype == torch.float32:
-                bbase = bucket.data_ptr()
-            slots = []
-            for i, p in enumerate(ns.params):
-                gi = ns.group_of[i]
-                g = p.grad if gi is not None else None
-                fused = g is not None and bbase is not None and g.data_ptr() == bbase + 4 * ns.offsets[i] \
-                    and g.dtype == torch.float32
-                slots.append(Slot(gi, ns.steps[i], g is not None, fused))
+            mask = net.grad_alias_mask() if flat.is_cuda else None        # the one-launch runs are the kernel's: GPU only
+            mask = mask or [False] * len(ns.params)
+            slots = [Slot(gi, step, gi is not None and (fused or p.grad is not None), fused)        # fused: .grad was just read
+                     for p, gi, step, fused in zip(ns.params, ns.group_of, ns.steps, mask)]
             runs, singles = plan_runs(slots)
             for a, b in runs:
                 lo, hi = ns.offsets[a], ns.offsets[b] + ns.numels[b]
@@ -285,7 +272,7 @@ class BucketAdam(Optimizer):
                     self._bind(ns, i)
                 ns.steps[i] += 1
                 ns.steps_t[i] += 1
-                work.append((flat[lo:hi], self._flat_grad(p.grad), ns.m[lo:hi], ns.v[lo:hi],
+                work.append((flat[lo:hi], flat_grad(p.grad)[0], ns.m[lo:hi], ns.v[lo:hi],
                              ns.ema[lo:hi] if ns.ema is not None else None, self.param_groups[ns.group_of[i]], ns.steps[i]))
         for p, gi in self._loose:
             if p.grad is None or p.numel() == 0:
@@ -298,7 +285,7 @@ class BucketAdam(Optimizer):
                 if st[k].device != p.device:
                     st[k] = st[k].to(p.device)
             st["step"] += 1
-            work.append((p.data.view(-1), self._flat_grad(p.grad), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
+            work.append((p.data.view(-1), flat_grad(p.grad)[0], st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
                          ema.view(-1) if ema is not None else None, self.param_groups[gi], int(st["step"].item())))
         return work
 
@@ -320,14 +307,9 @@ class BucketAdam(Optimizer):
         if len(devs) > 1:
             raise NotImplementedError(f"{type(self).__name__}: max_grad_norm over parameters on several devices "
                                       f"{sorted(map(str, devs))}")
-        if clip and parallel.world_size(self.process_group) > 1:
-            names = None
-            for p, _ in self._loose:
-                if p.grad is not None:
-                    names = names or self._names()
-                    raise RuntimeError(f"{type(self).__name__}(max_grad_norm): parameter {names.get(p, '?')!r} lies outside the "
-                                       "bucketed networks and carries a gradient; this package does not synchronise such "
-                                       "gradients over the ranks, so every rank would compute a different result")
+        if clip:                                          # the names are looked up only when there is something to refuse
+            refuse_loose_gradients(((self._names().get(p, "?"), p) for p, _ in self._loose if p.grad is not None),
+                                   f"{type(self).__name__}(max_grad_norm)", self.process_group)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -366,10 +348,8 @@ class BucketAdam(Optimizer):
             self._acc = torch.zeros(5, dtype=torch.float64, device=dev)
         acc = self._acc
         if dev.type == "cuda":
-            ws = _engine.workspace(dev)
             with _nvq.device_guard(dev):
-                for k, w in enumerate(work):
-                    _nvq.bucket_moments(w[1], None, acc, ws, accumulate=k > 0)
+                sum_moments([w[1] for w in work], acc, _engine.workspace(dev))
         else:
             acc[2] = sum((w[1].double() ** 2).sum() for w in work)
         return acc
