@@ -6,6 +6,8 @@ __version__ = "0.1.0"
 from nerve_cl.models import (FrameRecoveryNet, SuperResolutionNet, LightweightSuperResolution, EnhancementEngine,
                              AdaptiveEnhancementEngine, EnhancementConfig)
 from nerve_cl.continual import EpisodicMemory, EWC, MAML
+from nerve_cl.drift import DriftDetector, DriftResult, ModelDriftMonitor
 
 __all__ = ["FrameRecoveryNet", "SuperResolutionNet", "LightweightSuperResolution", "EnhancementEngine",
-           "AdaptiveEnhancementEngine", "EnhancementConfig", "EpisodicMemory", "EWC", "MAML"]
+           "AdaptiveEnhancementEngine", "EnhancementConfig", "EpisodicMemory", "EWC", "MAML",
+           "DriftDetector", "DriftResult", "ModelDriftMonitor"]

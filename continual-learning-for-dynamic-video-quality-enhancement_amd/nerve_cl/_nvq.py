@@ -235,6 +235,14 @@ SIGNATURES = {
     "nvq_replay_sample_weighted": (ci, [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp, vp]),
     "nvq_replay_update_importance": (ci, [vp, ci, vp, vp, ci, cf, vp]),
     "nvq_replay_nearest": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    # drift detection (csrc/drift.hip)
+    "nvq_rbf_gram_workspace_bytes": (sz, [ci, ci, ci]),
+    "nvq_rbf_gram_sum": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, sz, vp]),
+    "nvq_mmd_finish": (ci, [vp, ci, ci, cf, vp, vp, vp]),
+    "nvq_psi_counts": (ci, [vp, cl, vp, ci, vp, vp]),
+    "nvq_psi_finish": (ci, [vp, vp, ci, cl, cl, vp, vp, vp]),
+    "nvq_cell_descriptor": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "nvq_metric_window_update": (ci, [vp, vp, vp, ci, cf, cf, vp, vp, vp]),
 }
 
 
@@ -1401,3 +1409,58 @@ def replay_nearest(query: Optional[torch.Tensor], table: torch.Tensor, type_id: 
     cap = type_id.numel()
     check(lib().nvq_replay_nearest(ptr(query), ptr(table), ptr(type_id), cap, table.numel() // cap, ptr(out), ptr(out, 1),
                                    stream()), "nvq_replay_nearest")
+
+
+# ----------------------------------------------------------------------------- drift detection (csrc/drift.hip)
+def _rows(x: torch.Tensor, index: Optional[torch.Tensor]) -> int:
+    assert x.dtype == torch.float32 and x.dim() == 2, "rbf_gram_sum: (rows, d) fp32 matrices"
+    assert index is None or (index.dtype == torch.int32 and index.dim() == 1), "rbf_gram_sum: int32 row indices"
+    return x.shape[0] if index is None else index.numel()
+
+
+def rbf_gram_sum(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, ws: torch.Tensor, *, a_index: Optional[torch.Tensor] = None,
+                 b_index: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None, symmetric: bool = False) -> None:
+    """out (one float64 element) = sum_ij exp(-gamma |a_i - b_j|^2) over the rows of a, b (rows, d) fp32, or over the rows the
+    int32 index tensors name; gamma: a float64 device scalar, None = 1 / d (nvq_rbf_gram_sum)"""
+    na, nb = _rows(a, a_index), _rows(b, b_index)
+    assert a.shape[1] == b.shape[1] and out.dtype == torch.float64 and out.numel() == 1
+    assert gamma is None or (gamma.dtype == torch.float64 and gamma.numel() == 1)
+    check(lib().nvq_rbf_gram_sum(ptr(a), ptr(b), ptr(a_index), ptr(b_index), na, nb, a.shape[0], b.shape[0], a.shape[1], ptr(gamma),
+                                 int(symmetric), ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream()), "nvq_rbf_gram_sum")
+
+
+def mmd_finish(sums: torch.Tensor, na: int, nb: int, threshold: float, score: torch.Tensor, flag: torch.Tensor) -> None:
+    """score (float64 scalar), flag (bool scalar) from sums (3,) float64 = sum K(a,a), sum K(b,b), sum K(a,b)"""
+    assert sums.dtype == torch.float64 and sums.numel() == 3 and score.dtype == torch.float64 and flag.dtype == torch.bool
+    check(lib().nvq_mmd_finish(ptr(sums), na, nb, float(threshold), ptr(score), ptr(flag), stream()), "nvq_mmd_finish")
+
+
+def psi_counts(x: torch.Tensor, edges: torch.Tensor, counts: torch.Tensor) -> None:
+    """counts (edges - 1,) int32 = np.histogram(x, bins=edges)[0]; x flat fp32, edges float64 on the device"""
+    assert x.dtype == torch.float32 and edges.dtype == torch.float64 and counts.dtype == torch.int32
+    assert counts.numel() == edges.numel() - 1
+    check(lib().nvq_psi_counts(ptr(x), x.numel(), ptr(edges), edges.numel(), ptr(counts), stream()), "nvq_psi_counts")
+
+
+def psi_finish(cur_counts: torch.Tensor, ref_counts: torch.Tensor, len_cur: int, len_ref: int, score: torch.Tensor,
+               flag: torch.Tensor) -> None:
+    assert cur_counts.dtype == torch.int32 and ref_counts.dtype == torch.int32 and cur_counts.numel() == ref_counts.numel()
+    assert score.dtype == torch.float64 and flag.dtype == torch.bool
+    check(lib().nvq_psi_finish(ptr(cur_counts), ptr(ref_counts), cur_counts.numel(), len_cur, len_ref, ptr(score), ptr(flag),
+                               stream()), "nvq_psi_finish")
+
+
+def cell_descriptor(x: torch.Tensor, gh: int, gw: int, out: torch.Tensor) -> None:
+    """out (B, 2 * C * gh * gw) fp32 = per-cell means, then per-cell population standard deviations of x (B, C, H, W) fp32"""
+    B, Cc, H, W = x.shape
+    assert x.dtype == torch.float32 and out.dtype == torch.float32 and tuple(out.shape) == (B, 2 * Cc * gh * gw)
+    check(lib().nvq_cell_descriptor(ptr(x), B, Cc, H, W, gh, gw, ptr(out), stream()), "nvq_cell_descriptor")
+
+
+def metric_window_update(value: torch.Tensor, ring: torch.Tensor, state: torch.Tensor, baseline: float, threshold: float,
+                         mean: torch.Tensor, flag: torch.Tensor) -> None:
+    """push the fp32 device scalar `value` into `ring`; state (2,) int32; mean float64 scalar, flag bool scalar"""
+    assert value.dtype == torch.float32 and value.numel() == 1 and ring.dtype == torch.float32
+    assert state.dtype == torch.int32 and state.numel() == 2 and mean.dtype == torch.float64 and flag.dtype == torch.bool
+    check(lib().nvq_metric_window_update(ptr(value), ptr(ring), ptr(state), ring.numel(), float(baseline), float(threshold),
+                                         ptr(mean), ptr(flag), stream()), "nvq_metric_window_update")

@@ -18,7 +18,10 @@ output and cosine feature distillation terms of csrc/distill.hip (DESIGN.md sect
 ``--strategy agem`` (with ``--agem-ref-batch``; the memory flags of the replay strategy apply) is A-GEM: before every step the
 gradient on a batch from the memory is taken as the reference, and a conflicting step gradient is projected onto its orthogonal
 complement in place in the gradient bucket, decision included on the device (csrc/bucket_ops.hip).
-``--clip-grad-norm X`` clips the global gradient norm before every optimizer step of any strategy with the same kernels."""
+``--clip-grad-norm X`` clips the global gradient norm before every optimizer step of any strategy with the same kernels.
+``--drift {mmd,psi}`` (with ``--drift-grid G``) reports, before every task but the first, whether the task's LR frames have drifted
+from the previous task's: nerve_cl.drift.DriftDetector on per-cell mean / deviation descriptors of the frames (csrc/drift.hip,
+DESIGN.md section 22).  The script only reports; the task boundaries stay the ones it is given."""
 import argparse
 from pathlib import Path
 
@@ -29,7 +32,7 @@ from torch.utils.data import DataLoader, TensorDataset
 
 from _common import (LOSS_CHOICES, add_optimizer_arguments, ema_weights, make_optimizer, optimizer_impl, pick_device, resolve_loss,
                      shard)
-from nerve_cl import metrics, ops, parallel
+from nerve_cl import drift, metrics, ops, parallel
 from nerve_cl.continual import AGEM, EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 
@@ -110,6 +113,28 @@ def metrics_suffix(meter, world: int = 1) -> str:
     return f" SSIM={m['ssim_global']:.4f} MAE={m['mae']:.4f}"
 
 
+class DriftReport:
+    """--drift: the descriptors of the last task's LR frames are the detector's reference; before the next task trains, its
+    frames' descriptors are tested against them and one line is printed."""
+
+    def __init__(self, method: str, grid: int, device):
+        self.detector = drift.DriftDetector(method=method)
+        self.grid, self.device = grid, device
+
+    def __call__(self, task_id: int, lr: torch.Tensor, say) -> None:
+        desc = drift.frame_descriptor(lr.to(self.device), grid=(self.grid, self.grid))
+        if task_id > 0:
+            r = self.detector.detect(desc)
+            say(f"drift task {task_id - 1} -> {task_id}: method={r.method} score={r.score:.6f} drift={r.is_drift}")
+        self.detector.set_reference(desc)
+
+
+def report_drift(config, task_id: int, lr: torch.Tensor, say) -> None:
+    """called when a task begins: nothing without --drift"""
+    if config.get("drift") is not None:
+        config["drift"](task_id, lr, say)
+
+
 def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5, optimizer=None):
     device = next(model.parameters()).device
     adapter = _ClipAdapter(model)
@@ -119,6 +144,7 @@ def train_with_ewc(model, tasks, config, rank=0, world=1, epochs=5, optimizer=No
     criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        report_drift(config, task_id, lr, say)
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
         sl = shard(len(lr), rank, world)
         loader = DataLoader(TensorDataset(lr[sl], hr[sl]), batch_size=max(16 // world, 1), shuffle=True)
@@ -155,6 +181,7 @@ def train_with_replay(model, tasks, memory, config, rank=0, epochs=5, optimizer=
     per_sample = resolve_loss(config.get("loss", "mse"))            # reduction="none": one value per sample
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        report_drift(config, task_id, lr, say)
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
         for epoch in range(epochs):
             model.train()
@@ -209,6 +236,7 @@ def train_with_agem(model, tasks, memory, config, rank=0, epochs=5, optimizer=No
     agem = AGEM(adapter, memory, ref_batch_size=config.get("agem_ref_batch", 8))
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        report_drift(config, task_id, lr, say)
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
         for epoch in range(epochs):
             model.train()
@@ -243,6 +271,7 @@ def train_with_distill(model, tasks, config, rank=0, epochs=5, optimizer=None):
     criterion = make_criterion(config)
     say = print if rank == 0 else (lambda *a, **k: None)
     for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        report_drift(config, task_id, lr, say)
         say(f"\n=== Training on Task {task_id}: {task_name} ===")
         loader = DataLoader(TensorDataset(lr, hr), batch_size=16, shuffle=True)
         for epoch in range(epochs):
@@ -303,6 +332,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --device-memory: element type of the stored samples (bf16 halves the footprint)")
     ap.add_argument("--prioritized", action="store_true",
                     help="with --device-memory: per-sample losses of the replay rows update their importances (momentum 0.9) and replay draws are weighted by them")
+    ap.add_argument("--drift", choices=["off", "mmd", "psi"], default="off",
+                    help="before every task but the first, test its LR frames' descriptors for drift against the previous task's and "
+                         "print one line (RBF-kernel MMD or population stability index on the device; off: nothing)")
+    ap.add_argument("--drift-grid", type=int, default=8, metavar="G",
+                    help="with --drift: the frames are described by the mean and deviation of every cell of a G x G grid per channel")
     add_optimizer_arguments(ap, ema_note="write it to checkpoints/continual_model_ema.pt at the end (this script has no "
                                          "evaluation pass to run under it)")
     return ap
@@ -328,7 +362,8 @@ def main() -> None:
     config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized,
               "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill,
               "agem_ref_batch": args.agem_ref_batch, "clip_grad_norm": args.clip_grad_norm,
-              "optimizer_impl": optimizer_impl(args), "ema_decay": args.ema_decay}
+              "optimizer_impl": optimizer_impl(args), "ema_decay": args.ema_decay,
+              "drift": DriftReport(args.drift, args.drift_grid, device) if args.drift != "off" else None}
     optimizer = build_optimizer(model, config)      # (the reference loops each build their own; the steps are the same)
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs, optimizer=optimizer)

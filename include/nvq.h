@@ -896,6 +896,42 @@ int nvq_bn2_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld
                             const float* dres, int dres_ld, int relu, const double* sums, const double* count,
                             float* dx, int dx_ld, int bf16, void* stream);
 
+/* ------------------------------------------------------------------ drift detection (csrc/drift.hip)
+ * The reference's mlops/drift/detector.py (MMD with an RBF kernel, PSI, the performance monitor) on device-resident samples.
+ *
+ * nvq_rbf_gram_sum: *out = sum_{i < na, j < nb} exp(-gamma |a_i - b_j|^2) over rows of the row-major fp32 matrices a
+ * (a_rows x d) and b (b_rows x d).  a_index / b_index (device, may be NULL): row i of the sum is matrix row a_index[i]
+ * (a subsample gathered in the kernel); without one the first na / nb rows.  An index outside [0, rows) reads as a zero row.
+ * gamma_dev: one device double, NULL = 1 / d formed in double.  All arithmetic is float64 (inputs widened exactly, a.b and
+ * both squared norms on v_mfma_f64_16x16x4_f64, exp in double), one 64 x 64 tile per workgroup with its sum as one double in
+ * the workspace (nvq_rbf_gram_workspace_bytes, 8-byte aligned), one finishing block: no atomics, the same bits on every call.
+ * symmetric (a == b, same index, na == nb): only tiles on or above the diagonal run and the others are read from their
+ * mirror; the result equals the rectangular call on (a, a) bit for bit. */
+size_t nvq_rbf_gram_workspace_bytes(int na, int nb, int symmetric);
+int nvq_rbf_gram_sum(const float* a, const float* b, const int* a_index, const int* b_index, int na, int nb, int a_rows,
+                     int b_rows, int d, const double* gamma_dev, int symmetric, double* out, float* workspace,
+                     size_t workspace_bytes, void* stream);
+/* sums = {sum K(a, a), sum K(b, b), sum K(a, b)} (device): *score_out = sums[0] / na^2 + sums[1] / nb^2 - 2 sums[2] / (na nb),
+ * the biased estimator (diagonals included); *flag_out (one byte) = score > threshold. */
+int nvq_mmd_finish(const double* sums, int na, int nb, float threshold, double* score_out, unsigned char* flag_out, void* stream);
+/* counts[0 .. nedges - 1) = np.histogram(x, bins = edges)[0] for n fp32 values and 2 .. 11 increasing float64 edges (device):
+ * bin i is [e_i, e_{i+1}), the last bin includes its right edge, values outside [e_0, e_last] and NaN are not counted,
+ * comparisons in double.  counts is zeroed by the call.  Integer atomics only. */
+int nvq_psi_counts(const float* x, long n, const double* edges, int nedges, int* counts, void* stream);
+/* *score_out = sum_i (c_i - r_i) log(c_i / r_i), c_i = cur_counts[i] / len_cur + 1e-10, r_i = ref_counts[i] / len_ref + 1e-10
+ * (the array lengths, not the counted totals); *flag_out = score > 0.2. */
+int nvq_psi_finish(const int* cur_counts, const int* ref_counts, int nbins, long len_cur, long len_ref, double* score_out,
+                   unsigned char* flag_out, void* stream);
+/* x [B][C][H][W] fp32 -> out [B][2][C][gh][gw]: the mean and the population standard deviation of every cell of a gh x gw
+ * grid (gh <= H, gw <= W) with the bounds of adaptive_avg_pool2d: rows floor(i H / gh) .. ceil((i + 1) H / gh).  Sums in
+ * double, stored as fp32.  16-byte loads when x is 16-byte aligned and W % 4 == 0; the scalar form gives the same bits. */
+int nvq_cell_descriptor(const float* x, int B, int C, int H, int W, int gh, int gw, float* out, void* stream);
+/* Push *value (device) into ring [window] at state[0], state = {next position, values held} (device ints, zeroed by the
+ * caller before the first push); *mean_out = the mean of the values held, *flag_out = (baseline - mean) / baseline > threshold
+ * once `window` values are held, 0 before.  One launch, one block. */
+int nvq_metric_window_update(const float* value, float* ring, int* state, int window, float baseline, float threshold,
+                             double* mean_out, unsigned char* flag_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
