@@ -1,0 +1,419 @@
+// Federated rounds and differential privacy on flat fp32 buffers.
+//
+//   nvq_fed_delta_norms   sq[k] = |x_k - base|^2 for the K rows of a client matrix, one pass
+//   nvq_fed_aggregate     out = base + lr * sum_k c_k (x_k - base) (+ Gaussian noise): FedAvg, clipped updates, server step
+//   nvq_dp_segment_norms  sq[s] = |g_s|^2 per slot of a gradient bucket
+//   nvq_dp_clip_noise     g_s = g_s * min(1, C / (|g_s| + 1e-6)) + sigma z per slot, padding kept at zero
+//
+// No atomics; every grid depends on the sizes only; every thread owns whole quads (4 consecutive floats) in the vector and
+// in the scalar form alike and adds in one order, so a result depends neither on pointer alignment nor on the call.  The
+// noise is Philox4x32-10 keyed by (seed), counted by (quad index, offset): a function of (seed, offset, element) alone.
+#include "common.h"
+
+namespace nvq {
+
+__device__ __forceinline__ double fed_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ float4 fed_ldq(const float* p) {
+    if (VEC) return ld4(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void fed_stq(float* p, float4 v) {
+    if (VEC) {
+        st4(p, v);
+    } else {
+        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    }
+}
+
+// one quad per thread and trip, at most 1024 blocks: a function of n only
+static int fed_blocks(long n) {
+    int nb = ceil_div(n, 256L * 4);
+    if (nb > 1024) nb = 1024;
+    if (nb < 1) nb = 1;
+    return nb;
+}
+
+// ------------------------------------------------------------------ Philox4x32-10 and the normals of one quad
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned r[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// u = (m + 0.5) 2^-24 for the 24-bit m.  m + 0.5 is exact in fp32 only below 2^23; above, 1 - u = (2^24 - m - 0.5) 2^-24 is,
+// so ln u = log1p(-(1 - u)) and the angle 2 pi u = -2 pi (1 - u) (mod 2 pi) are formed from the exact complement.
+__device__ __forceinline__ float philox_neg2ln(unsigned w) {
+    const unsigned m = w >> 8;
+    if (m < 0x800000u) return -2.0f * logf(((float)m + 0.5f) * 0x1p-24f);
+    return -2.0f * log1pf(-(((float)(0x1000000u - m) - 0.5f) * 0x1p-24f));
+}
+__device__ __forceinline__ float philox_turns(unsigned w) {          // 2 u in (-1, 1], for sincospif
+    const unsigned m = w >> 8;
+    if (m < 0x800000u) return ((float)m + 0.5f) * 0x1p-23f;
+    return -(((float)(0x1000000u - m) - 0.5f) * 0x1p-23f);
+}
+
+__device__ __forceinline__ float4 quad_normals(long q, long seed, long offset) {
+    unsigned r[4];
+    philox4x32_10((unsigned)q, (unsigned)((unsigned long)q >> 32), (unsigned)offset, (unsigned)((unsigned long)offset >> 32),
+                  (unsigned)seed, (unsigned)((unsigned long)seed >> 32), r);
+    float s0, c0, s1, c1;
+    sincospif(philox_turns(r[1]), &s0, &c0);
+    sincospif(philox_turns(r[3]), &s1, &c1);
+    const float m0 = sqrtf(philox_neg2ln(r[0])), m1 = sqrtf(philox_neg2ln(r[2]));
+    return make_float4(m0 * c0, m0 * s0, m1 * c1, m1 * s1);
+}
+
+// ------------------------------------------------------------------ client-update norms
+#define NVQ_SQDIFF(acc, xv, bv)                                \
+    do {                                                       \
+        const double d_ = (double)(xv) - (double)(bv);         \
+        acc = fma(d_, d_, acc);                                \
+    } while (0)
+
+// part[blockIdx.x * K + k] = this block's share of |x_k - base|^2.  KMAX accumulators live in registers (fully unrolled).
+template <bool VEC, bool HAS_BASE, int KMAX>
+__global__ __launch_bounds__(256) void fed_delta_norms_kernel(const float* __restrict__ clients, long stride, int K,
+                                                              const float* __restrict__ base, long n, double* __restrict__ part) {
+    __shared__ double scratch[4 * KMAX];
+    double acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
+    const long nq = n >> 2;
+    for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        const float4 b = HAS_BASE ? fed_ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            if (k < K) {
+                const float4 x = fed_ldq<VEC>(clients + k * stride + 4 * q);
+                NVQ_SQDIFF(acc[k], x.x, b.x);
+                NVQ_SQDIFF(acc[k], x.y, b.y);
+                NVQ_SQDIFF(acc[k], x.z, b.z);
+                NVQ_SQDIFF(acc[k], x.w, b.w);
+            }
+        }
+    }
+    const long t = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
+    if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
+        const float b = HAS_BASE ? base[t] : 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) NVQ_SQDIFF(acc[k], clients[k * stride + t], b);
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k < K) {
+            const double v = fed_wave_sum(acc[k]);
+            if ((threadIdx.x & 63) == 0) scratch[wave * KMAX + k] = v;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        const int k = threadIdx.x;
+        part[(long)blockIdx.x * K + k] = scratch[k] + scratch[KMAX + k] + scratch[2 * KMAX + k] + scratch[3 * KMAX + k];
+    }
+}
+
+// block k: sq[k] = sum over the blocks' partials, thread t takes blocks t, t + 256, ..., then the block sum: a fixed order
+__global__ __launch_bounds__(256) void fed_delta_norms_final_kernel(const double* __restrict__ part, int nblk, int K,
+                                                                    double* __restrict__ sq) {
+    __shared__ double scratch[4];
+    const int k = blockIdx.x;
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) v += part[(long)b * K + k];
+    v = fed_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) sq[k] = scratch[0] + scratch[1] + scratch[2] + scratch[3];
+}
+
+// ------------------------------------------------------------------ aggregate
+__device__ __forceinline__ float fed_mix(double a, float b, double lr) { return (float)fma(lr, a, (double)b); }
+
+template <bool VEC, bool HAS_BASE, bool NOISE>
+__global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restrict__ clients, long stride, int K,
+                                                            const float* base, const double* __restrict__ weights,
+                                                            const double* __restrict__ sq, float clip_norm, float server_lr,
+                                                            float noise_std, long seed, long offset, long n, float* out) {
+    __shared__ double coef[64];
+    if ((int)threadIdx.x < K) {
+        double W = 0.0;
+        for (int k = 0; k < K; ++k) W += weights[k];
+        const int k = threadIdx.x;
+        double s = 1.0;
+        if (sq != nullptr) {
+            s = (double)clip_norm / (sqrt(sq[k]) + 1e-6);
+            if (!(s < 1.0)) s = 1.0;
+        }
+        coef[k] = weights[k] / W * s;
+    }
+    __syncthreads();
+    const double lr = (double)server_lr;
+    const long nq = n >> 2;
+    for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        const float4 b = HAS_BASE ? fed_ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const float4 x = fed_ldq<VEC>(clients + k * stride + 4 * q);
+            const double c = coef[k];
+            ax = fma(c, (double)x.x - (double)b.x, ax);
+            ay = fma(c, (double)x.y - (double)b.y, ay);
+            az = fma(c, (double)x.z - (double)b.z, az);
+            aw = fma(c, (double)x.w - (double)b.w, aw);
+        }
+        float4 v = make_float4(fed_mix(ax, b.x, lr), fed_mix(ay, b.y, lr), fed_mix(az, b.z, lr), fed_mix(aw, b.w, lr));
+        if (NOISE) {
+            const float4 z = quad_normals(q, seed, offset);
+            v.x = fmaf(noise_std, z.x, v.x);
+            v.y = fmaf(noise_std, z.y, v.y);
+            v.z = fmaf(noise_std, z.z, v.z);
+            v.w = fmaf(noise_std, z.w, v.w);
+        }
+        fed_stq<VEC>(out + 4 * q, v);
+    }
+    const long t = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
+    if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
+        const float b = HAS_BASE ? base[t] : 0.f;
+        double a = 0.0;
+        for (int k = 0; k < K; ++k) a = fma(coef[k], (double)clients[k * stride + t] - (double)b, a);
+        float v = fed_mix(a, b, lr);
+        if (NOISE) {
+            const float4 z = quad_normals(nq, seed, offset);
+            v = fmaf(noise_std, threadIdx.x == 0 ? z.x : (threadIdx.x == 1 ? z.y : z.z), v);
+        }
+        out[t] = v;
+    }
+}
+
+// ------------------------------------------------------------------ per-slot DP on a gradient bucket
+// chunks[c] = {slot, first quad of the bucket, quads}: one block per chunk, sorted by slot.  A chunk that does not lie inside
+// its slot is skipped (the tables are device memory: the host side cannot check them).
+__device__ __forceinline__ bool dp_chunk(const int* __restrict__ chunks, const long* __restrict__ seg_off,
+                                         const long* __restrict__ seg_numel, int S, int& s, long& q0, long& q1, long& e0,
+                                         long& e1) {
+    s = chunks[3 * blockIdx.x];
+    if (s < 0 || s >= S) return false;
+    q0 = chunks[3 * blockIdx.x + 1];
+    q1 = q0 + chunks[3 * blockIdx.x + 2];
+    e0 = seg_off[s];
+    e1 = e0 + seg_numel[s];
+    return q0 >= 0 && q1 >= q0 && (e0 & 3) == 0 && e0 >= 0 && 4 * q0 >= e0 && 4 * q1 <= ((e1 + 3) & ~3L);
+}
+
+__global__ __launch_bounds__(256) void dp_segment_norms_kernel(const float* __restrict__ g, const long* __restrict__ seg_off,
+                                                               const long* __restrict__ seg_numel, int S,
+                                                               const int* __restrict__ chunks, double* __restrict__ part) {
+    __shared__ double scratch[4];
+    int s;
+    long q0, q1, e0, e1;
+    double v = 0.0;
+    if (dp_chunk(chunks, seg_off, seg_numel, S, s, q0, q1, e0, e1)) {
+        for (long q = q0 + threadIdx.x; q < q1; q += 256) {
+            const float4 a = ld4(g + 4 * q);
+            const long e = 4 * q;
+            const double x = (double)a.x, y = e + 1 < e1 ? (double)a.y : 0.0, z = e + 2 < e1 ? (double)a.z : 0.0,
+                         w = e + 3 < e1 ? (double)a.w : 0.0;
+            if (e < e1) v = fma(x, x, v);
+            v = fma(y, y, v);
+            v = fma(z, z, v);
+            v = fma(w, w, v);
+        }
+    }
+    v = fed_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = scratch[0] + scratch[1] + scratch[2] + scratch[3];
+}
+
+// thread s: sq[s] = the sum of slot s's chunks in table order (its first chunk by bisection: the table is sorted by slot)
+__global__ __launch_bounds__(256) void dp_segment_norms_final_kernel(const double* __restrict__ part,
+                                                                     const int* __restrict__ chunks, int n_chunks, int S,
+                                                                     double* __restrict__ sq) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    int lo = 0, hi = n_chunks;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (chunks[3 * mid] < s) lo = mid + 1;
+        else hi = mid;
+    }
+    double v = 0.0;
+    for (int c = lo; c < n_chunks && chunks[3 * c] == s; ++c) v += part[c];
+    sq[s] = v;
+}
+
+template <bool NOISE>
+__global__ __launch_bounds__(256) void dp_clip_noise_kernel(float* __restrict__ g, const long* __restrict__ seg_off,
+                                                            const long* __restrict__ seg_numel, int S,
+                                                            const int* __restrict__ chunks, const double* __restrict__ sq,
+                                                            float max_norm, float noise_scale, long seed, long offset) {
+    int s;
+    long q0, q1, e0, e1;
+    if (!dp_chunk(chunks, seg_off, seg_numel, S, s, q0, q1, e0, e1)) return;
+    double coef = (double)max_norm / (sqrt(sq[s]) + 1e-6);
+    if (!(coef < 1.0)) coef = 1.0;
+    const float cf = (float)coef;
+    if (!NOISE && cf == 1.0f) return;                 // a slot under the bound keeps its bits
+    for (long q = q0 + threadIdx.x; q < q1; q += 256) {
+        float4 a = ld4(g + 4 * q);
+        a.x = __fmul_rn(a.x, cf);
+        a.y = __fmul_rn(a.y, cf);
+        a.z = __fmul_rn(a.z, cf);
+        a.w = __fmul_rn(a.w, cf);
+        if (NOISE) {
+            const float4 z = quad_normals(q, seed, offset);
+            a.x = fmaf(noise_scale, z.x, a.x);
+            a.y = fmaf(noise_scale, z.y, a.y);
+            a.z = fmaf(noise_scale, z.z, a.z);
+            a.w = fmaf(noise_scale, z.w, a.w);
+        }
+        const long e = 4 * q;                          // the slot's padding stays exactly zero: those draws are dropped
+        if (e + 1 >= e1) a.y = 0.f;
+        if (e + 2 >= e1) a.z = 0.f;
+        if (e + 3 >= e1) a.w = 0.f;
+        if (e >= e1) a.x = 0.f;
+        st4(g + 4 * q, a);
+    }
+}
+
+static int dp_check(const char* what, const float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks,
+                    int n_chunks, const double* sq) {
+    NVQ_REQUIRE(g != nullptr && seg_off != nullptr && seg_numel != nullptr && chunks != nullptr && sq != nullptr,
+                "%s: null pointer", what);
+    NVQ_REQUIRE(S >= 1 && n_chunks >= 1, "%s: S = %d, n_chunks = %d", what, S, n_chunks);
+    NVQ_REQUIRE(aligned16(g), "%s: the bucket must be 16-byte aligned (slots are whole quads)", what);
+    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(seg_off) & 7) == 0 && (reinterpret_cast<uintptr_t>(seg_numel) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(sq) & 7) == 0 && (reinterpret_cast<uintptr_t>(chunks) & 3) == 0,
+                "%s: table alignment", what);
+    return NVQ_OK;
+}
+
+}  // namespace nvq
+
+using namespace nvq;
+
+extern "C" {
+
+size_t nvq_fed_workspace_bytes(int K, long n) {
+    if (K < 1 || n < 0) return 0;
+    return (size_t)fed_blocks(n) * (size_t)K * sizeof(double);
+}
+
+#define NVQ_FED_NORMS(KMAX)                                                                                               \
+    do {                                                                                                                  \
+        if (base != nullptr) {                                                                                            \
+            if (vec) hipLaunchKernelGGL((fed_delta_norms_kernel<true, true, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);   \
+            else hipLaunchKernelGGL((fed_delta_norms_kernel<false, true, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);      \
+        } else {                                                                                                          \
+            if (vec) hipLaunchKernelGGL((fed_delta_norms_kernel<true, false, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);  \
+            else hipLaunchKernelGGL((fed_delta_norms_kernel<false, false, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);     \
+        }                                                                                                                 \
+    } while (0)
+
+int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* base, long n, double* sq, float* workspace,
+                        size_t workspace_bytes, void* stream) {
+    NVQ_REQUIRE(clients != nullptr && sq != nullptr && n >= 0, "fed_delta_norms: clients / sq / n");
+    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_delta_norms: K = %d outside 1 .. 64", K);
+    NVQ_REQUIRE(stride >= n, "fed_delta_norms: stride %ld < n %ld", stride, n);
+    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(sq) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+                "fed_delta_norms: sq and workspace must be 8-byte aligned");
+    const int nb = fed_blocks(n);
+    if (workspace == nullptr || (size_t)nb * K * sizeof(double) > workspace_bytes) {
+        set_error("fed_delta_norms: workspace");
+        return NVQ_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* part = reinterpret_cast<double*>(workspace);
+    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base));
+    const dim3 grid(nb), block(256);
+    if (K <= 8) NVQ_FED_NORMS(8);
+    else if (K <= 16) NVQ_FED_NORMS(16);
+    else NVQ_FED_NORMS(64);
+    int rc = check_launch("fed_delta_norms");
+    if (rc) return rc;
+    hipLaunchKernelGGL(fed_delta_norms_final_kernel, dim3(K), dim3(256), 0, s, part, nb, K, sq);
+    return check_launch("fed_delta_norms_final");
+}
+
+#define NVQ_FED_AGG(VEC, HAS_BASE, NOISE)                                                                                 \
+    hipLaunchKernelGGL((fed_aggregate_kernel<VEC, HAS_BASE, NOISE>), grid, block, 0, s, clients, stride, K, base, weights, sq, \
+                       clip_norm, server_lr, noise_std, seed, offset, n, out)
+
+int nvq_fed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, const double* sq,
+                      float clip_norm, float server_lr, float noise_std, long seed, long offset, long n, float* out,
+                      void* stream) {
+    NVQ_REQUIRE(clients != nullptr && weights != nullptr && out != nullptr && n >= 0, "fed_aggregate: clients / weights / out / n");
+    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_aggregate: K = %d outside 1 .. 64", K);
+    NVQ_REQUIRE(stride >= n, "fed_aggregate: stride %ld < n %ld", stride, n);
+    NVQ_REQUIRE(seed >= 0 && offset >= 0, "fed_aggregate: seed and offset are non-negative");
+    NVQ_REQUIRE(noise_std >= 0.f && (sq == nullptr || clip_norm >= 0.f), "fed_aggregate: noise_std / clip_norm");
+    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(weights) & 7) == 0 && (reinterpret_cast<uintptr_t>(sq) & 7) == 0,
+                "fed_aggregate: weights and sq must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base)) && aligned16(out);
+    const bool noise = noise_std != 0.f;
+    const dim3 grid(fed_blocks(n)), block(256);
+    if (base != nullptr) {
+        if (vec) { if (noise) NVQ_FED_AGG(true, true, true); else NVQ_FED_AGG(true, true, false); }
+        else { if (noise) NVQ_FED_AGG(false, true, true); else NVQ_FED_AGG(false, true, false); }
+    } else {
+        if (vec) { if (noise) NVQ_FED_AGG(true, false, true); else NVQ_FED_AGG(true, false, false); }
+        else { if (noise) NVQ_FED_AGG(false, false, true); else NVQ_FED_AGG(false, false, false); }
+    }
+    return check_launch("fed_aggregate");
+}
+
+int nvq_dp_segment_norms(const float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks, int n_chunks,
+                         double* sq, float* workspace, size_t workspace_bytes, void* stream) {
+    int rc = dp_check("dp_segment_norms", g, seg_off, seg_numel, S, chunks, n_chunks, sq);
+    if (rc) return rc;
+    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "dp_segment_norms: workspace must be 8-byte aligned");
+    if (workspace == nullptr || (size_t)n_chunks * sizeof(double) > workspace_bytes) {
+        set_error("dp_segment_norms: workspace");
+        return NVQ_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* part = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(dp_segment_norms_kernel, dim3(n_chunks), dim3(256), 0, s, g, seg_off, seg_numel, S, chunks, part);
+    rc = check_launch("dp_segment_norms");
+    if (rc) return rc;
+    hipLaunchKernelGGL(dp_segment_norms_final_kernel, dim3(ceil_div(S, 256)), dim3(256), 0, s, part, chunks, n_chunks, S, sq);
+    return check_launch("dp_segment_norms_final");
+}
+
+int nvq_dp_clip_noise(float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks, int n_chunks,
+                      const double* sq, float max_norm, float noise_scale, long seed, long offset, void* stream) {
+    int rc = dp_check("dp_clip_noise", g, seg_off, seg_numel, S, chunks, n_chunks, sq);
+    if (rc) return rc;
+    NVQ_REQUIRE(seed >= 0 && offset >= 0, "dp_clip_noise: seed and offset are non-negative");
+    NVQ_REQUIRE(max_norm >= 0.f && noise_scale >= 0.f, "dp_clip_noise: max_norm / noise_scale");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(n_chunks), block(256);
+    if (noise_scale != 0.f)
+        hipLaunchKernelGGL(dp_clip_noise_kernel<true>, grid, block, 0, s, g, seg_off, seg_numel, S, chunks, sq, max_norm,
+                           noise_scale, seed, offset);
+    else
+        hipLaunchKernelGGL(dp_clip_noise_kernel<false>, grid, block, 0, s, g, seg_off, seg_numel, S, chunks, sq, max_norm,
+                           noise_scale, seed, offset);
+    return check_launch("dp_clip_noise");
+}
+
+}  // extern "C"

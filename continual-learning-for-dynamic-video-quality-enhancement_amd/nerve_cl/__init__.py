@@ -7,7 +7,8 @@ from nerve_cl.models import (FrameRecoveryNet, SuperResolutionNet, LightweightSu
                              AdaptiveEnhancementEngine, EnhancementConfig)
 from nerve_cl.continual import EpisodicMemory, EWC, MAML
 from nerve_cl.drift import DriftDetector, DriftResult, ModelDriftMonitor
+from nerve_cl.federated import FederatedTrainer
 
 __all__ = ["FrameRecoveryNet", "SuperResolutionNet", "LightweightSuperResolution", "EnhancementEngine",
            "AdaptiveEnhancementEngine", "EnhancementConfig", "EpisodicMemory", "EWC", "MAML",
-           "DriftDetector", "DriftResult", "ModelDriftMonitor"]
+           "DriftDetector", "DriftResult", "ModelDriftMonitor", "FederatedTrainer"]

@@ -243,6 +243,12 @@ SIGNATURES = {
     "nvq_psi_finish": (ci, [vp, vp, ci, cl, cl, vp, vp, vp]),
     "nvq_cell_descriptor": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "nvq_metric_window_update": (ci, [vp, vp, vp, ci, cf, cf, vp, vp, vp]),
+    # federated aggregation and differential privacy on flat buffers (csrc/federated.hip)
+    "nvq_fed_workspace_bytes": (sz, [ci, cl]),
+    "nvq_fed_delta_norms": (ci, [vp, cl, ci, vp, cl, vp, vp, sz, vp]),
+    "nvq_fed_aggregate": (ci, [vp, cl, ci, vp, vp, vp, cf, cf, cf, cl, cl, cl, vp, vp]),
+    "nvq_dp_segment_norms": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, sz, vp]),
+    "nvq_dp_clip_noise": (ci, [vp, vp, vp, ci, vp, ci, vp, cf, cf, cl, cl, vp]),
 }
 
 
@@ -1464,3 +1470,84 @@ def metric_window_update(value: torch.Tensor, ring: torch.Tensor, state: torch.T
     assert state.dtype == torch.int32 and state.numel() == 2 and mean.dtype == torch.float64 and flag.dtype == torch.bool
     check(lib().nvq_metric_window_update(ptr(value), ptr(ring), ptr(state), ring.numel(), float(baseline), float(threshold),
                                          ptr(mean), ptr(flag), stream()), "nvq_metric_window_update")
+
+
+# ----------------------------------------------------------------------------- federated rounds and differential privacy
+FED_MAX_CLIENTS = 64
+DP_CHUNK_QUADS = 1024   # quads per block of the per-slot kernels: 4 per thread
+
+
+def fed_workspace_bytes(K: int, n: int) -> int:
+    return int(lib().nvq_fed_workspace_bytes(int(K), int(n)))
+
+
+def _fed_rows(clients: torch.Tensor, n: int) -> "tuple[int, int]":
+    assert clients.dtype == torch.float32 and clients.dim() == 2 and clients.stride(1) == 1, "clients: a [K][stride] fp32 matrix"
+    # (the row stride of a one-row matrix is arbitrary in torch and never used by the kernels: any value >= n serves)
+    K, stride = clients.shape[0], (clients.stride(0) if clients.shape[0] > 1 else max(clients.stride(0), clients.shape[1]))
+    assert 1 <= K <= FED_MAX_CLIENTS and stride >= n >= 0 and clients.shape[1] >= n, "clients: 1 .. 64 rows of at least n floats"
+    require_device(clients)
+    return K, stride
+
+
+def fed_delta_norms(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], sq: torch.Tensor, ws: torch.Tensor) -> None:
+    """sq[k] = sum_i (clients[k, i] - base[i])^2 over the first n columns, in double (base None: the rows' own norms)"""
+    K, stride = _fed_rows(clients, n)
+    assert sq.dtype == torch.float64 and sq.numel() >= K and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    check(lib().nvq_fed_delta_norms(clients.data_ptr(), stride, K, ptr(base), n, ptr(sq), ptr(ws), ws.numel() * 4, stream()),
+          "nvq_fed_delta_norms")
+
+
+def fed_aggregate(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], weights: torch.Tensor, sq: Optional[torch.Tensor],
+                  out: torch.Tensor, *, clip_norm: float = 0.0, server_lr: float = 1.0, noise_std: float = 0.0, seed: int = 0,
+                  offset: int = 0) -> None:
+    """out[i] = base[i] + server_lr * sum_k c_k (clients[k, i] - base[i]) + noise_std * z_i (nvq_fed_aggregate); ``out`` may be
+    ``base``"""
+    K, stride = _fed_rows(clients, n)
+    assert weights.dtype == torch.float64 and weights.numel() >= K and (sq is None or (sq.dtype == torch.float64 and sq.numel() >= K))
+    assert out.dtype == torch.float32 and out.numel() >= n and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    check(lib().nvq_fed_aggregate(clients.data_ptr(), stride, K, ptr(base), ptr(weights), ptr(sq), float(clip_norm),
+                                  float(server_lr), float(noise_std), int(seed), int(offset), n, ptr(out), stream()),
+          "nvq_fed_aggregate")
+
+
+class DpTable:
+    """The device tables of the per-slot DP kernels for one bucket layout: slot offsets and sizes (int64), the chunk triples
+    (slot, first quad, quads) with at most DP_CHUNK_QUADS quads each, sorted by slot, and the norms sq (float64)."""
+
+    def __init__(self, offsets: Sequence[int], numels: Sequence[int], device):
+        assert len(offsets) == len(numels) >= 1
+        chunks, end = [], 0
+        for s, (o, k) in enumerate(zip(offsets, numels)):
+            if o % 4 or o < end or k < 0:
+                raise ValueError(f"slot {s} at float offset {o} ({k} floats): slots start at multiples of 4 floats and do not overlap")
+            end = o + k
+            q, nq = o // 4, (k + 3) // 4
+            for c in range(0, nq, DP_CHUNK_QUADS):
+                chunks.append((s, q + c, min(DP_CHUNK_QUADS, nq - c)))
+        if not chunks:
+            raise ValueError("every slot is empty")
+        self.total = (end + 3) // 4 * 4
+        self.S, self.n_chunks = len(offsets), len(chunks)
+        self.seg_off = torch.tensor(list(offsets), dtype=torch.int64).to(device)
+        self.seg_numel = torch.tensor(list(numels), dtype=torch.int64).to(device)
+        self.chunks = torch.tensor(chunks, dtype=torch.int32).to(device)
+        self.sq = torch.zeros(self.S, dtype=torch.float64, device=device)
+
+
+def _dp_bucket(g: torch.Tensor, table: DpTable) -> int:
+    assert g.dtype == torch.float32 and g.numel() >= table.total, "the bucket is fp32 and covers every slot of the table"
+    return ptr(g)
+
+
+def dp_segment_norms(g: torch.Tensor, table: DpTable, ws: torch.Tensor) -> None:
+    """table.sq[s] = sum of g^2 over slot s (nvq_dp_segment_norms)"""
+    check(lib().nvq_dp_segment_norms(_dp_bucket(g, table), ptr(table.seg_off), ptr(table.seg_numel), table.S, ptr(table.chunks),
+                                     table.n_chunks, ptr(table.sq), ptr(ws), ws.numel() * 4, stream()), "nvq_dp_segment_norms")
+
+
+def dp_clip_noise(g: torch.Tensor, table: DpTable, max_norm: float, noise_scale: float, seed: int, offset: int) -> None:
+    """per slot: g = g * min(max_norm / (sqrt(sq) + 1e-6), 1) + noise_scale * z in place, padding kept 0 (nvq_dp_clip_noise)"""
+    check(lib().nvq_dp_clip_noise(_dp_bucket(g, table), ptr(table.seg_off), ptr(table.seg_numel), table.S, ptr(table.chunks),
+                                  table.n_chunks, ptr(table.sq), float(max_norm), float(noise_scale), int(seed), int(offset),
+                                  stream()), "nvq_dp_clip_noise")

@@ -1,0 +1,351 @@
+"""Federated rounds in one process: FedAvg over whole-model weight vectors, optional clipping of the client updates, server
+learning rate and Gaussian noise, as one pass of csrc/federated.hip over a matrix whose rows are the clients' weights
+(DESIGN.md section 23).
+
+The reference's ``FederatedTrainer.train_round`` (reference nerve_cl/federated/server.py:141-193) selects clients and counts
+samples but neither trains nor aggregates; here a round trains every selected client on the model itself (its flat parameter
+buffer is reset to the global weights in place, so parameters are never re-homed and captured graphs stay valid) and averages
+on the device.  ``flwr`` is only the transport between processes and is not needed for any of this.
+"""
+from __future__ import annotations
+
+import random
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+
+from nerve_cl import _engine, _nvq
+from nerve_cl._bucket import segments_of
+from nerve_cl.federated import _philox
+from nerve_cl.federated.privacy import DPOptimizer, PrivacyConfig, _Seg
+
+__all__ = ["aggregate_flat", "fedavg", "weighted_average", "FederatedTrainer", "start_server"]
+
+
+# ----------------------------------------------------------------------------------------------- aggregation
+def _host_weights(weights) -> Optional[List[float]]:
+    if isinstance(weights, torch.Tensor):
+        return None if weights.is_cuda else [float(w) for w in weights.tolist()]
+    return [float(w) for w in weights]
+
+
+def aggregate_flat(clients: torch.Tensor, weights, base: Optional[torch.Tensor] = None, clip_norm: Optional[float] = None,
+                   server_lr: float = 1.0, noise_std: float = 0.0, seed: int = 0, offset: int = 0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[i] = base[i] + server_lr * sum_k c_k (clients[k, i] - base[i]) + noise_std * z_i`` for a ``[K, n]`` fp32 matrix of
+    client weight vectors (a row stride above n is fine), ``c_k = weights[k] / sum(weights) * min(1, clip_norm / (|x_k - base| +
+    1e-6))`` (no ``clip_norm``: no clipping; no ``base``: zeros, so the defaults are plain FedAvg).  ``z`` is the Philox stream
+    (seed, offset) of ``nerve_cl.federated._philox``.  ``out`` may be ``base``.
+
+    On the GPU: ``nvq_fed_delta_norms`` (only with ``clip_norm``) and ``nvq_fed_aggregate``, nothing read back; ``weights`` given
+    as a float64 tensor on the device is used as it is (all-zero weights then give NaN), otherwise it is checked on the host and
+    all-zero weights raise ``ValueError``.  CPU tensors take the same formula in float64 torch operations."""
+    if clients.dim() != 2 or clients.dtype != torch.float32:
+        raise ValueError("clients: a [K, n] float32 matrix")
+    K, n = clients.shape
+    host = _host_weights(weights)
+    if host is not None:
+        if len(host) != K:
+            raise ValueError(f"{len(host)} weights for {K} clients")
+        if any(w < 0 for w in host) or not sum(host) > 0:
+            raise ValueError("aggregate_flat: the weights are non-negative and not all zero")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=clients.device)
+    if clients.is_cuda:
+        dev = clients.device
+        if host is not None:
+            weights = torch.tensor(host, dtype=torch.float64).to(dev)
+        with _nvq.device_guard(dev):
+            sq = None
+            if clip_norm is not None:
+                sq = torch.empty(K, dtype=torch.float64, device=dev)
+                _nvq.fed_delta_norms(clients, n, base, sq, _engine.workspace(dev))
+            _nvq.fed_aggregate(clients, n, base, weights, sq, out, clip_norm=clip_norm or 0.0, server_lr=server_lr,
+                               noise_std=noise_std, seed=seed, offset=offset)
+        return out
+    w = torch.as_tensor(host if host is not None else weights, dtype=torch.float64)
+    x = clients.double()
+    b = base.double().view(1, n) if base is not None else torch.zeros(1, n, dtype=torch.float64)
+    d = x - b
+    c = w / w.sum()
+    if clip_norm is not None:
+        c = c * torch.clamp(clip_norm / (d.pow(2).sum(1).sqrt() + 1e-6), max=1.0)
+    v = (b[0] + server_lr * (c.view(K, 1) * d).sum(0)).to(torch.float32)
+    if noise_std != 0.0:
+        z = torch.from_numpy(_philox.normals(seed, offset, n))
+        v = (v.double() + noise_std * z).to(torch.float32)
+    out.copy_(v)
+    return out
+
+
+def _is_float(t: torch.Tensor) -> bool:
+    return t.is_floating_point()
+
+
+def _int_mean(stack: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """weighted mean of integer tensors truncated toward zero (what a float average cast back to the integer type gives)"""
+    mean = (stack.double() * w.view(-1, *([1] * (stack.dim() - 1)))).sum(0) / w.sum()
+    return mean.trunc().to(stack.dtype)
+
+
+def fedavg(states: "Sequence[Dict[str, torch.Tensor]]", num_examples: Sequence[float]) -> "Dict[str, torch.Tensor]":
+    """Sample-weighted average of state dicts (FedAvg, McMahan et al. 2017): floating tensors through ``aggregate_flat`` as one
+    packed row per client, integer buffers (``num_batches_tracked``) as the weighted mean truncated toward zero."""
+    if len(states) == 0 or len(states) != len(num_examples):
+        raise ValueError("fedavg: one example count per state dict, at least one")
+    host = [float(w) for w in num_examples]
+    if any(w < 0 for w in host) or not sum(host) > 0:
+        raise ValueError("fedavg: the example counts are non-negative and not all zero")
+    keys = list(states[0].keys())
+    fkeys = [k for k in keys if _is_float(states[0][k])]
+    out: "Dict[str, torch.Tensor]" = {}
+    if fkeys:
+        dev = states[0][fkeys[0]].device
+        rows = torch.stack([torch.cat([sd[k].detach().reshape(-1).to(device=dev, dtype=torch.float32) for k in fkeys])
+                            for sd in states])
+        flat = aggregate_flat(rows, host)
+        off = 0
+        for k in fkeys:
+            t = states[0][k]
+            out[k] = flat[off:off + t.numel()].view(t.shape).to(t.dtype)
+            off += t.numel()
+    for k in keys:
+        if k not in out:
+            stack = torch.stack([sd[k].detach() for sd in states])
+            out[k] = _int_mean(stack, torch.tensor(host, dtype=torch.float64).to(stack.device))
+    return {k: out[k] for k in keys}
+
+
+def weighted_average(metrics: "List[Tuple[int, Dict[str, float]]]") -> "Dict[str, float]":
+    """[(num_samples, {name: value})] -> {name: the sample-weighted mean} (reference server.py:99-110)"""
+    total = sum(n for n, _ in metrics)
+    acc: "Dict[str, float]" = {}
+    for n, m in metrics:
+        for k, v in m.items():
+            acc[k] = acc.get(k, 0.0) + n * v
+    return {k: v / total for k, v in acc.items()}
+
+
+def start_server(model: nn.Module, num_rounds: int = 100, server_address: str = "[::]:8080", min_clients: int = 2) -> None:
+    """The networked server is flwr's; this package implements the arithmetic of a round, not the transport."""
+    try:
+        import flwr  # noqa: F401
+    except ImportError as e:
+        raise ImportError("start_server needs the `flwr` package (the transport between server and clients); without it use "
+                          "FederatedTrainer, which runs the same rounds in one process") from e
+    raise NotImplementedError("the flwr server strategy is not part of this package; FederatedTrainer runs the rounds in one process")
+
+
+# ----------------------------------------------------------------------------------------------- the trainer
+class _Pack:
+    """Tensors of a state dict packed into one fp32 row (each at a multiple of 4 floats)"""
+
+    def __init__(self, tensors: "List[torch.Tensor]"):
+        self.tensors = tensors
+        self.offsets, off = [], 0
+        for t in tensors:
+            self.offsets.append(off)
+            off += (t.numel() + 3) // 4 * 4
+        self.total = off
+
+    def views(self, row: torch.Tensor) -> "List[torch.Tensor]":
+        return [row[o:o + t.numel()].view(t.shape) for o, t in zip(self.offsets, self.tensors)]
+
+    def pack(self, row: torch.Tensor) -> None:
+        for v, t in zip(self.views(row), self.tensors):
+            v.copy_(t)
+
+    def unpack(self, row: torch.Tensor) -> None:
+        for v, t in zip(self.views(row), self.tensors):
+            t.copy_(v)
+
+
+class FederatedTrainer:
+    """``FederatedTrainer(model, num_clients=10, clients_per_round=5, local_epochs=5, *, lr=1e-4, batch_size=16, loss=None,
+    privacy=None, update_clip=None, update_noise=0.0, server_lr=1.0, optimizer_impl="torch", seed=None)``
+
+    ``model(inputs) -> outputs`` is trained on every client's ``(inputs, targets)`` (``set_client_data``) with a fresh
+    ``AdamW(lr)`` for ``local_epochs`` passes in batches of ``batch_size``, taken in order; ``loss`` defaults to ``nn.MSELoss()``
+    (the reference client's criterion).  ``privacy`` (a ``PrivacyConfig``) wraps the optimizer in ``DPOptimizer``.  ``update_clip``
+    clips every client's whole update ``x_k - global`` to that 2-norm, ``update_noise`` is the standard deviation of the Gaussian
+    noise added to the aggregated weights, ``server_lr`` scales the aggregated update.  ``optimizer_impl``: ``"torch"`` or ``"bucket"``
+    (``nerve_cl.optim.BucketAdamW``).  ``seed`` fixes the client selection and every noise stream; without it the selection is
+    ``random.sample`` of the global generator, as in the reference.
+
+    On the GPU the weights of every HIP-backed network inside ``model`` are one flat buffer: the clients' results are the rows of a
+    persistent ``[clients_per_round, n]`` matrix and a round ends with one ``nvq_fed_delta_norms`` (only with ``update_clip``) and
+    one ``nvq_fed_aggregate`` writing into ``flat_theta()``.  Everything else in the state dict (BatchNorm statistics, loose
+    parameters) is packed per client into a second, small matrix and takes the same kernel without clipping, noise or server
+    rate; integer buffers take the weighted mean truncated toward zero.  Client data that already lives on the model's device
+    is used in place; then nothing is read back between local training and the aggregated weights (``train_round_device``)."""
+
+    def __init__(self, model: nn.Module, num_clients: int = 10, clients_per_round: int = 5, local_epochs: int = 5, *,
+                 lr: float = 1e-4, batch_size: int = 16, loss=None, privacy: Optional[PrivacyConfig] = None,
+                 update_clip: Optional[float] = None, update_noise: float = 0.0, server_lr: float = 1.0,
+                 optimizer_impl: str = "torch", seed: Optional[int] = None):
+        if optimizer_impl not in ("torch", "bucket"):
+            raise ValueError(f"optimizer_impl {optimizer_impl!r}: 'torch' or 'bucket'")
+        if clients_per_round < 1 or clients_per_round > _nvq.FED_MAX_CLIENTS:
+            raise ValueError(f"clients_per_round: 1 .. {_nvq.FED_MAX_CLIENTS}")
+        if update_clip is not None and not update_clip > 0.0:
+            raise ValueError(f"invalid update_clip: {update_clip}")
+        if update_noise < 0.0:
+            raise ValueError(f"invalid update_noise: {update_noise}")
+        self.model = model
+        self.num_clients = num_clients
+        self.clients_per_round = clients_per_round
+        self.local_epochs = local_epochs
+        self.lr, self.batch_size = lr, batch_size
+        self.loss = loss if loss is not None else nn.MSELoss()
+        self.privacy = privacy
+        self.update_clip, self.update_noise, self.server_lr = update_clip, float(update_noise), float(server_lr)
+        self.optimizer_impl = optimizer_impl
+        self.seed = seed
+        self._rng = random.Random(seed) if seed is not None else random
+        self._noise_seed = random.Random(seed).getrandbits(62) if seed is not None else random.getrandbits(62)
+        self.client_data: Dict[int, Tuple] = {}
+        self.global_round = 0
+        self.last_selected: List[int] = []
+        self._plan = None
+
+    def set_client_data(self, client_id: int, data: Tuple) -> None:
+        """``data``: ``(inputs, targets)`` tensors with one sample per row"""
+        self.client_data[client_id] = data
+
+    # ------------------------------------------------------------------ what a round moves
+    def _build_plan(self):
+        model = self.model
+        segs = segments_of(model)
+        dev = next(model.parameters()).device
+        nets = [sg.net for sg in segs if sg.net is not None] if dev.type == "cuda" else []
+        flat_names = {n for sg in segs if sg.net is not None and dev.type == "cuda" for n in sg.names}
+        sd = model.state_dict()                       # detached tensors that share the parameters' and buffers' memory
+        rest_f = [t for k, t in sd.items() if k not in flat_names and _is_float(t)]
+        rest_i = [t for k, t in sd.items() if k not in flat_names and not _is_float(t)]
+        K = self.clients_per_round
+        plan = {"dev": dev, "nets": nets, "pack": _Pack(rest_f), "ints": rest_i,
+                "rows": [torch.zeros(K, net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
+                "snaps": [torch.zeros(net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
+                "weights": torch.zeros(K, dtype=torch.float64, device=dev),
+                "sq": torch.zeros(K, dtype=torch.float64, device=dev),
+                "dp_segs": [_Seg(sg) for sg in segs] if self.privacy is not None else None}
+        p = plan["pack"]
+        plan["rest_rows"] = torch.zeros(K, max(p.total, 4), dtype=torch.float32, device=dev)
+        plan["rest_snap"] = torch.zeros(max(p.total, 4), dtype=torch.float32, device=dev)
+        plan["int_rows"] = [torch.zeros((K,) + tuple(t.shape), dtype=t.dtype, device=t.device) for t in rest_i]
+        plan["int_snap"] = [torch.zeros_like(t) for t in rest_i]
+        return plan
+
+    def _make_optimizer(self):
+        params = [p for p in self.model.parameters() if p.requires_grad]
+        if self.optimizer_impl == "bucket":
+            from nerve_cl import optim
+            return optim.BucketAdamW(params, lr=self.lr)
+        fused = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
+        return torch.optim.AdamW(params, lr=self.lr, **({"fused": True} if fused else {}))
+
+    def _restore(self, plan) -> None:
+        for net, snap in zip(plan["nets"], plan["snaps"]):
+            net.flat_theta().copy_(snap)
+        plan["pack"].unpack(plan["rest_snap"])
+        for t, s in zip(plan["ints"], plan["int_snap"]):
+            t.copy_(s)
+
+    def _train_client(self, plan, data, seed: int) -> torch.Tensor:
+        """local training on the model in place; returns the sum of batch loss x batch size as a 0-dim tensor on the device"""
+        dev = plan["dev"]
+        xs, ys = data[0], data[1]
+        if xs.device != dev:
+            xs, ys = xs.to(dev), ys.to(dev)
+        opt = self._make_optimizer()
+        dp = None
+        if self.privacy is not None:
+            dp = DPOptimizer(opt, self.model, self.privacy, self.batch_size, max(len(xs), 1), seed=seed, _segments=plan["dp_segs"])
+        stepper = dp if dp is not None else opt
+        self.model.train()
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for _ in range(self.local_epochs):
+            for i in range(0, len(xs), self.batch_size):
+                x, y = xs[i:i + self.batch_size], ys[i:i + self.batch_size]
+                stepper.zero_grad()
+                loss = self.loss(self.model(x), y)
+                loss.backward()
+                stepper.step()
+                total += loss.detach().float() * len(x)
+        return total
+
+    # ------------------------------------------------------------------ a round
+    @torch.no_grad()
+    def _aggregate(self, plan, K: int) -> None:
+        w = plan["weights"][:K]
+        clip = self.update_clip
+        plain = clip is None and self.update_noise == 0.0 and self.server_lr == 1.0
+        for j, (net, rows, snap) in enumerate(zip(plan["nets"], plan["rows"], plan["snaps"])):
+            flat = net.flat_theta()
+            n = flat.numel()
+            with _nvq.device_guard(plan["dev"]):
+                sq = None
+                if clip is not None:
+                    sq = plan["sq"]
+                    _nvq.fed_delta_norms(rows[:K], n, snap, sq, _engine.workspace(plan["dev"]))
+                _nvq.fed_aggregate(rows[:K], n, None if plain else snap, w, sq, flat, clip_norm=clip or 0.0,
+                                   server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed,
+                                   offset=self.global_round * (len(plan["nets"]) + 1) + j)
+        pack = plan["pack"]
+        if pack.total:
+            rest = plan["rest_rows"][:K]
+            if plan["nets"]:                           # next to the flat buffers: statistics and loose parameters, a plain mean
+                with _nvq.device_guard(plan["dev"]):
+                    _nvq.fed_aggregate(rest, rest.shape[1], None, w, None, plan["rest_snap"])
+            else:                                      # no HIP-backed network (a plain module, any device): everything is here
+                aggregate_flat(rest, w if w.is_cuda else w.tolist(), base=None if plain else plan["rest_snap"].clone(),
+                               clip_norm=clip, server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed,
+                               offset=self.global_round, out=plan["rest_snap"])
+            pack.unpack(plan["rest_snap"])
+        for t, rows in zip(plan["ints"], plan["int_rows"]):
+            t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+
+    def train_round_device(self) -> Dict[str, object]:
+        """One round; ``train_loss`` stays a 0-dim tensor on the device, so with client data on the device nothing is read back."""
+        available = list(self.client_data.keys())
+        selected = self._rng.sample(available, min(self.clients_per_round, len(available)))
+        counts = [len(self.client_data[c][0]) for c in selected]
+        if selected and not sum(counts) > 0:
+            raise ValueError("train_round: every selected client has no samples (all-zero aggregation weights)")
+        if self._plan is None:
+            self._plan = self._build_plan()
+        plan = self._plan
+        K = len(selected)
+        seeds = [self._rng.getrandbits(62) for _ in selected] if self.seed is not None else [random.getrandbits(62) for _ in selected]
+        loss_sum = torch.zeros((), dtype=torch.float32, device=plan["dev"])
+        with torch.no_grad():
+            for net, snap in zip(plan["nets"], plan["snaps"]):
+                snap.copy_(net.flat_theta())
+            plan["pack"].pack(plan["rest_snap"])
+            for t, s in zip(plan["ints"], plan["int_snap"]):
+                s.copy_(t)
+        for k, (cid, cnt) in enumerate(zip(selected, counts)):
+            with torch.no_grad():
+                self._restore(plan)
+            loss_sum += self._train_client(plan, self.client_data[cid], seeds[k])
+            with torch.no_grad():
+                for net, rows in zip(plan["nets"], plan["rows"]):
+                    rows[k].copy_(net.flat_theta())
+                plan["pack"].pack(plan["rest_rows"][k])
+                for t, rows in zip(plan["ints"], plan["int_rows"]):
+                    rows[k].copy_(t)
+                plan["weights"][k].fill_(float(cnt))
+        if K:
+            self._aggregate(plan, K)
+        self.global_round += 1
+        self.last_selected = selected
+        steps = max(sum(counts) * self.local_epochs, 1)
+        return {"round": self.global_round, "clients": K, "samples": sum(counts), "train_loss": loss_sum / steps}
+
+    def train_round(self) -> Dict[str, float]:
+        """Execute one federated round: ``{"round", "clients", "samples"}`` as in the reference, plus ``train_loss``, the mean
+        training loss per sample over the clients' local steps."""
+        out = self.train_round_device()
+        out["train_loss"] = float(out["train_loss"])
+        return out

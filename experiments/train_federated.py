@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""Federated training in simulation mode: the reference's experiments/train_federated.py ``--mode simulation`` on libnvq, with the
+rounds actually trained and aggregated (the reference's FederatedTrainer only counts samples).
+
+Every client holds clips drawn around an offset of its own (the reference's create_client_data), shaped as train_continual.py
+shapes its tasks.  A round trains the selected clients one after the other on the one model, whose flat parameter buffer is reset
+to the global weights in place, and ends with one aggregation pass of csrc/federated.hip over the matrix of client weights
+(nerve_cl.federated.FederatedTrainer).  ``--dp-enabled`` wraps the local optimizer in the per-tensor
+clip-and-noise DPOptimizer (two launches on the gradient bucket); ``--update-clip`` / ``--update-noise`` / ``--server-lr`` act on
+the clients' whole updates in the aggregation pass.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
+"""
+import argparse
+from pathlib import Path
+
+import _common  # noqa: F401
+import torch
+
+from _common import OPTIMIZER_IMPLS, pick_device
+from nerve_cl import ops
+from nerve_cl.federated import FederatedTrainer, PrivacyConfig
+from nerve_cl.models import EnhancementConfig, EnhancementEngine
+from train_continual import _ClipAdapter, configure_precision
+
+
+def create_client_data(client_id: int, num_samples: int = 100):
+    """heterogeneous clients: every client's frames sit around an offset of its own, (client_id % 5) * 0.1 as in the reference"""
+    off = (client_id % 5) * 0.1
+    return torch.randn(num_samples, 3, 64, 64) + off, torch.randn(num_samples, 3, 128, 128) + off
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["simulation", "server", "client"], default="simulation")
+    ap.add_argument("--num-clients", type=int, default=10)
+    ap.add_argument("--clients-per-round", type=int, default=5)
+    ap.add_argument("--num-rounds", type=int, default=10)
+    ap.add_argument("--local-epochs", type=int, default=5)
+    ap.add_argument("--dp-enabled", action="store_true", help="per-tensor gradient clipping and Gaussian noise in every local step")
+    ap.add_argument("--dp-noise-multiplier", type=float, default=1.0)
+    ap.add_argument("--dp-max-grad-norm", type=float, default=1.0)
+    ap.add_argument("--update-clip", type=float, default=None, metavar="X",
+                    help="clip every client's whole update to the 2-norm X in the aggregation pass (default: no clipping)")
+    ap.add_argument("--update-noise", type=float, default=0.0, metavar="S",
+                    help="standard deviation of the Gaussian noise added to the aggregated weights")
+    ap.add_argument("--server-lr", type=float, default=1.0, help="the aggregated update is scaled by this before it is applied")
+    ap.add_argument("--samples", type=int, default=100, help="clips per client (the reference's 100)")
+    ap.add_argument("--features", type=int, default=64)
+    ap.add_argument("--blocks", type=int, default=8)
+    ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
+                    help="MFMA operand precision of the convolutions (accumulation fp32; fp32 = the exact parity mode)")
+    ap.add_argument("--optimizer-impl", choices=OPTIMIZER_IMPLS, default="torch",
+                    help="torch: torch.optim's fused AdamW (default); bucket: nerve_cl.optim.BucketAdamW on the flat buckets")
+    ap.add_argument("--seed", type=int, default=0, help="client selection, data and every noise stream")
+    return ap
+
+
+def main() -> None:
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.mode != "simulation":
+        raise SystemExit(f"--mode {args.mode} needs the `flwr` transport, which this package does not wrap; "
+                         "--mode simulation runs the same rounds in one process")
+    device, rank, world = pick_device()
+    if world > 1:
+        ap.error("the federated simulation runs in a single process")
+    torch.manual_seed(args.seed)
+    engine = EnhancementEngine(EnhancementConfig(frame_recovery_enabled=False, super_resolution_enabled=True,
+                                                 sr_num_features=args.features, sr_num_residual_blocks=args.blocks)).to(device)
+    configure_precision(engine, args.precision, "off")
+    privacy = None
+    if args.dp_enabled:
+        privacy = PrivacyConfig(max_grad_norm=args.dp_max_grad_norm, noise_multiplier=args.dp_noise_multiplier)
+    trainer = FederatedTrainer(_ClipAdapter(engine), num_clients=args.num_clients, clients_per_round=args.clients_per_round,
+                               local_epochs=args.local_epochs, loss=ops.MSELoss(), privacy=privacy, update_clip=args.update_clip,
+                               update_noise=args.update_noise, server_lr=args.server_lr, optimizer_impl=args.optimizer_impl,
+                               seed=args.seed)
+    for cid in range(args.num_clients):
+        lr, hr = create_client_data(cid, args.samples)
+        trainer.set_client_data(cid, (lr.to(device), hr.to(device)))          # on the device: a round copies nothing from the host
+    for _ in range(args.num_rounds):
+        m = trainer.train_round()
+        print(f"Round {m['round']}: {m['clients']} clients, {m['samples']} samples, loss {m['train_loss']:.4f}")
+    Path("checkpoints").mkdir(exist_ok=True)
+    torch.save(engine.state_dict(), "checkpoints/federated_model.pt")
+    print("\nFederated training complete!")
+
+
+if __name__ == "__main__":
+    main()

@@ -932,6 +932,46 @@ int nvq_cell_descriptor(const float* x, int B, int C, int H, int W, int gh, int 
 int nvq_metric_window_update(const float* value, float* ring, int* state, int window, float baseline, float threshold,
                              double* mean_out, unsigned char* flag_out, void* stream);
 
+/* ------------------------------------------------------------------ federated rounds and differential privacy
+ * (csrc/federated.hip).  Flat fp32 buffers, sums in double, no atomics; every grid depends on the sizes
+ * only and a thread owns whole quads in the 16-byte form (everything 16-byte aligned, stride % 4 == 0) and in the scalar form
+ * alike, so a result is the same bits on every call and at every pointer alignment.
+ *
+ * Noise: z_i for element i of a buffer is Philox4x32-10 (Random123 constants) with key = {seed low, seed high} and counter =
+ * {q low, q high, offset low, offset high}, q = i >> 2; the words r0..r3 give u_j = ((r_j >> 8) + 0.5) 2^-24 and elements
+ * 4q .. 4q + 3 take sqrt(-2 ln u0) cospi(2 u1), sqrt(-2 ln u0) sinpi(2 u1) and the same from (u2, u3), with the accurate
+ * logf / sincospif.  seed and offset are non-negative.  The stream depends on (seed, offset, i) and on nothing else.
+ *
+ * nvq_fed_delta_norms: clients is a [K][stride] matrix, stride >= n, 1 <= K <= 64; sq[k] = sum_i (x_k[i] - base[i])^2 with the
+ * differences and the sums in double (base == NULL: the rows themselves).  One pass reads base once per quad and the K rows,
+ * writes per-block partials to the workspace (nvq_fed_workspace_bytes, 8-byte aligned; NVQ_EWORKSPACE when short) and a
+ * finishing launch adds them in a fixed order.
+ *
+ * nvq_fed_aggregate: weights = K device doubles (sample counts, unnormalised), W = their sum in k order; c_k = weights[k] / W *
+ * s_k with s_k = min(1, clip_norm / (sqrt(sq[k]) + 1e-6)) when sq != NULL, else 1.  Per element, in double with fma, k ascending:
+ * a = sum_k c_k (x_k[i] - base[i]) (base == NULL: 0), v = (float) fma(server_lr, a, base[i]) rounded once, out[i] =
+ * fmaf(noise_std, z_i, v); noise_std == 0 skips the noise path: out[i] = v.  FedAvg is base = NULL, sq = NULL, server_lr = 1,
+ * noise_std = 0.  out may alias base: every element is read before the same thread writes it.  out must not alias clients.
+ * All-zero weights give NaN: the caller checks its sample counts. */
+size_t nvq_fed_workspace_bytes(int K, long n);
+int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* base, long n, double* sq, float* workspace,
+                        size_t workspace_bytes, void* stream);
+int nvq_fed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, const double* sq,
+                      float clip_norm, float server_lr, float noise_std, long seed, long offset, long n, float* out,
+                      void* stream);
+/* Per-slot clipping and noise on a gradient bucket g (16-byte aligned, anything else is NVQ_EINVAL): slot s is numel[s] floats
+ * at seg_off[s], a multiple of 4, padded with zeros to the next multiple of 4.  seg_off / seg_numel: S device longs each.
+ * chunks: n_chunks device int triples {slot, first quad of the bucket, quads}, sorted by slot, covering every slot's quads once;
+ * one block per chunk.  A chunk outside its slot, or of a slot at a misaligned offset, is skipped.
+ * nvq_dp_segment_norms: sq[s] = sum of g^2 over slot s, chunk partials in the workspace (n_chunks doubles) added in table order.
+ * nvq_dp_clip_noise: coef_s = min(max_norm / (sqrt(sq[s]) + 1e-6), 1) rounded to float; g[i] = fmaf(noise_scale, z_i, g[i] * coef_s)
+ * for the numel elements of each slot, q the quad index within the bucket; the padding floats are written as 0 and their draws
+ * dropped.  noise_scale == 0 skips the noise path, and a slot with coef_s == 1 is then not written at all. */
+int nvq_dp_segment_norms(const float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks, int n_chunks,
+                         double* sq, float* workspace, size_t workspace_bytes, void* stream);
+int nvq_dp_clip_noise(float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks, int n_chunks,
+                      const double* sq, float max_norm, float noise_scale, long seed, long offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
