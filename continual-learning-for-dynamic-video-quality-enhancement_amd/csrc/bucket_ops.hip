@@ -4,50 +4,12 @@
 //
 // Every thread owns whole quads (4 consecutive floats) in both the vector and the scalar form of a kernel, so the two
 // forms add the same products in the same order: the sums do not depend on the alignment of the pointers, only on n.
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
 
 // acc slots (float64, device): g.r, r.r, g.g, projection coefficient c, number of projections so far
 enum { ACC_GR = 0, ACC_RR = 1, ACC_GG = 2, ACC_C = 3, ACC_COUNT = 4 };
-
-__device__ __forceinline__ double group_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Block-wide sums of three doubles over 256 threads; valid in every thread. scratch: >= 12 doubles of LDS.
-__device__ __forceinline__ void block_sum3_256(double& a, double& b, double& c, double* scratch) {
-    a = group_sum_f64(a);
-    b = group_sum_f64(b);
-    c = group_sum_f64(c);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        scratch[wave * 3 + 0] = a;
-        scratch[wave * 3 + 1] = b;
-        scratch[wave * 3 + 2] = c;
-    }
-    __syncthreads();
-    a = scratch[0] + scratch[3] + scratch[6] + scratch[9];
-    b = scratch[1] + scratch[4] + scratch[7] + scratch[10];
-    c = scratch[2] + scratch[5] + scratch[8] + scratch[11];
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 ldq(const float* p) {
-    if (VEC) return ld4(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void stq(float* p, float4 v) {
-    if (VEC) {
-        st4(p, v);
-    } else {
-        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-    }
-}
 
 #define NVQ_MOMENT(gv, rv)                                 \
     do {                                                   \
@@ -74,7 +36,7 @@ __global__ __launch_bounds__(256) void bucket_moments_kernel(const float* __rest
     }
     const long t = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
     if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) NVQ_MOMENT(g[t], HAS_R ? r[t] : 0.f);
-    block_sum3_256(gr, rr, gg, scratch);
+    block_wave_sum_256(scratch, gr, rr, gg);
     if (threadIdx.x == 0) {
         part[blockIdx.x * 3 + 0] = gr;
         part[blockIdx.x * 3 + 1] = rr;
@@ -93,7 +55,7 @@ __global__ __launch_bounds__(256) void bucket_moments_final_kernel(const double*
         rr += part[b * 3 + 1];
         gg += part[b * 3 + 2];
     }
-    block_sum3_256(gr, rr, gg, scratch);
+    block_wave_sum_256(scratch, gr, rr, gg);
     if (threadIdx.x != 0) return;
     if (accumulate) {
         if (has_r) {
@@ -160,14 +122,6 @@ __global__ __launch_bounds__(256) void bucket_clip_kernel(float* __restrict__ g,
     if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) g[t] *= cf;
 }
 
-// one quad per thread and trip, at most 1024 blocks: a function of n only (the sums are bit-reproducible)
-static int bucket_blocks(long n) {
-    int nb = ceil_div(n, 256L * 4);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return nb;
-}
-
 }  // namespace nvq
 
 using namespace nvq;
@@ -177,9 +131,8 @@ extern "C" {
 int nvq_bucket_moments(const float* g, const float* r, long n, double* acc, int accumulate, int coefficient,
                        float* workspace, size_t workspace_bytes, void* stream) {
     NVQ_REQUIRE(g != nullptr && acc != nullptr && n >= 0, "bucket_moments: g / acc / n");
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(acc) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-                "bucket_moments: acc and workspace must be 8-byte aligned");
-    const int nb = bucket_blocks(n);
+    NVQ_REQUIRE(aligned8(acc) && aligned8(workspace), "bucket_moments: acc and workspace must be 8-byte aligned");
+    const int nb = flat_blocks(n);
     if (workspace == nullptr || (size_t)nb * 3 * sizeof(double) > workspace_bytes) {
         set_error("bucket_moments: workspace");
         return NVQ_EWORKSPACE;
@@ -188,13 +141,8 @@ int nvq_bucket_moments(const float* g, const float* r, long n, double* acc, int 
     double* part = reinterpret_cast<double*>(workspace);
     const bool vec = aligned16(g) && (r == nullptr || aligned16(r));
     const dim3 grid(nb), block(256);
-    if (r != nullptr) {
-        if (vec) hipLaunchKernelGGL((bucket_moments_kernel<true, true>), grid, block, 0, s, g, r, n, part);
-        else hipLaunchKernelGGL((bucket_moments_kernel<false, true>), grid, block, 0, s, g, r, n, part);
-    } else {
-        if (vec) hipLaunchKernelGGL((bucket_moments_kernel<true, false>), grid, block, 0, s, g, r, n, part);
-        else hipLaunchKernelGGL((bucket_moments_kernel<false, false>), grid, block, 0, s, g, r, n, part);
-    }
+    with_bools([&](auto V, auto R) { hipLaunchKernelGGL((bucket_moments_kernel<V(), R()>), grid, block, 0, s, g, r, n, part); },
+               vec, r != nullptr);
     int rc = check_launch("bucket_moments");
     if (rc) return rc;
     hipLaunchKernelGGL(bucket_moments_final_kernel, dim3(1), dim3(256), 0, s, part, nb, r != nullptr ? 1 : 0, accumulate,
@@ -204,7 +152,7 @@ int nvq_bucket_moments(const float* g, const float* r, long n, double* acc, int 
 
 int nvq_bucket_project(float* g, const float* r, long n, const double* acc, void* stream) {
     NVQ_REQUIRE(g != nullptr && r != nullptr && acc != nullptr && n >= 0, "bucket_project: g / r / acc / n");
-    const dim3 grid(bucket_blocks(n)), block(256);
+    const dim3 grid(flat_blocks(n)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (aligned16(g) && aligned16(r)) hipLaunchKernelGGL(bucket_project_kernel<true>, grid, block, 0, s, g, r, n, acc);
     else hipLaunchKernelGGL(bucket_project_kernel<false>, grid, block, 0, s, g, r, n, acc);
@@ -213,7 +161,7 @@ int nvq_bucket_project(float* g, const float* r, long n, const double* acc, void
 
 int nvq_bucket_clip(float* g, long n, const double* acc, float max_norm, float* norm_out, void* stream) {
     NVQ_REQUIRE(g != nullptr && acc != nullptr && n >= 0, "bucket_clip: g / acc / n");
-    const dim3 grid(bucket_blocks(n)), block(256);
+    const dim3 grid(flat_blocks(n)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (aligned16(g)) hipLaunchKernelGGL(bucket_clip_kernel<true>, grid, block, 0, s, g, n, acc, max_norm, norm_out);
     else hipLaunchKernelGGL(bucket_clip_kernel<false>, grid, block, 0, s, g, n, acc, max_norm, norm_out);

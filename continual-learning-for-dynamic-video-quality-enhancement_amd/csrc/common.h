@@ -27,6 +27,8 @@ inline int check_launch(const char* what) {
     } while (0)
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -88,7 +90,7 @@ __device__ __forceinline__ int xcd_tile(int bid, int n) {
     return x * q + (x < r ? x : r) + (bid >> 3);
 }
 
-// Second stage of every two-stage reduction in the library:
+// Second stage of the two-stage reductions with K outputs (conv_igemm.hip; flat.h declares the ones of the flat-buffer losses):
 // out[k] = alpha * sum_b part[b*K + k] (+ out[k]); summed in double, fixed order => deterministic.
 int launch_reduce_partials(const float* part, int nblk, int K, float alpha, float* out,
                            int accumulate, hipStream_t s);

@@ -8,6 +8,7 @@
 // 16-channel K chunk and the matching weight slab are staged in LDS, every wave owns two tile
 // rows (4 pixel blocks of 16) and all NB*16 output channels of the workgroup.
 #include "conv_common.h"
+#include "flat.h"
 
 namespace nvq {
 
@@ -502,7 +503,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
     if (k >= K) return;
     double s = 0.0;
     for (int b = lane; b < nblk; b += 64) s += (double)part[(long)b * K + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (lane == 0) {
         const float v = alpha * (float)s;
         out[k] = accumulate ? out[k] + v : v;

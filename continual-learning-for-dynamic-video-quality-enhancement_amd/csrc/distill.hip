@@ -11,31 +11,11 @@
 // a first sweep over the channels and writes ds in a second one: nothing is saved besides the two inputs.
 //
 // HBM-bound VALU kernels, no LDS beyond the block reduction, no float atomics: two identical calls give the same bits.
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
 
 namespace {
-
-// Block-wide sum of a double over 256 threads in a fixed tree order; result valid in thread 0. scratch: 256 doubles of LDS.
-__device__ __forceinline__ double block_sum_256_f64(double v, double* scratch) {
-    __syncthreads();
-    scratch[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) scratch[threadIdx.x] += scratch[threadIdx.x + o];
-        __syncthreads();
-    }
-    return scratch[0];
-}
-
-// blocks per group of the elementwise passes (the rule of the pixel losses): 16 elements per thread, capped
-int group_blocks(long per, int groups) {
-    int nb = ceil_div(per, 256L * 16);
-    const int cap = groups == 1 ? 2048 : 1024;
-    if (nb > cap) nb = cap;
-    return nb < 1 ? 1 : nb;
-}
 
 // ------------------------------------------------------------------------------------------------------------ distill
 
@@ -87,8 +67,8 @@ __global__ __launch_bounds__(256) void distill_final_kernel(const float* __restr
         d += (double)p[2 * k];
         m += (double)p[2 * k + 1];
     }
-    d = block_sum_256_f64(d, scratch);
-    m = block_sum_256_f64(m, scratch);
+    d = block_tree_sum_256(d, scratch);
+    m = block_tree_sum_256(m, scratch);
     if (threadIdx.x == 0) {
         d *= inv_per;
         m *= inv_per;
@@ -188,17 +168,6 @@ __global__ __launch_bounds__(256) void cosine_partial_kernel(const float* __rest
     if (threadIdx.x == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 
-// grid (G): out[g] = alpha * sum_k part[g * nblk + k], in double in a fixed order
-__global__ __launch_bounds__(256) void cosine_final_kernel(const float* __restrict__ part, int nblk, double alpha,
-                                                           float* __restrict__ out) {
-    __shared__ double scratch[256];
-    const float* p = part + (long)blockIdx.x * nblk;
-    double v = 0.0;
-    for (int k = threadIdx.x; k < nblk; k += 256) v += (double)p[k];
-    v = block_sum_256_f64(v, scratch);
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(alpha * v);
-}
-
 // ds_c = -(go / N) (t_c - [sqrt(a) > eps] (ab / a) s_c) / (ns nt): with r = ab / a the bracket is one fma per element, and for
 // parallel s and t (C = 1 always) it cancels to a few ulp of t_c
 template <int V>
@@ -245,17 +214,6 @@ using namespace nvq;
 
 extern "C" {
 
-#define NVQ_DISTILL_DISPATCH(KERNEL, ...)                                                                         \
-    do {                                                                                                          \
-        if (vec) {                                                                                                \
-            if (y) hipLaunchKernelGGL((KERNEL<true, true>), grid, dim3(256), 0, st, __VA_ARGS__);                 \
-            else hipLaunchKernelGGL((KERNEL<true, false>), grid, dim3(256), 0, st, __VA_ARGS__);                  \
-        } else {                                                                                                  \
-            if (y) hipLaunchKernelGGL((KERNEL<false, true>), grid, dim3(256), 0, st, __VA_ARGS__);                \
-            else hipLaunchKernelGGL((KERNEL<false, false>), grid, dim3(256), 0, st, __VA_ARGS__);                 \
-        }                                                                                                         \
-    } while (0)
-
 int nvq_distill_forward(const float* s, const float* t, const float* y, int groups, long per, float wt, float wy, float* out,
                         float* workspace, size_t workspace_bytes, void* stream) {
     NVQ_REQUIRE(groups > 0 && groups <= 65535 && per > 0 && s && t && out && aligned16(s) && aligned16(t) && aligned16(y),
@@ -265,7 +223,9 @@ int nvq_distill_forward(const float* s, const float* t, const float* y, int grou
     hipStream_t st = (hipStream_t)stream;
     const bool vec = (per & 3) == 0;
     const dim3 grid(nbs, groups);
-    NVQ_DISTILL_DISPATCH(distill_partial_kernel, s, t, y, per, workspace);
+    with_bools([&](auto V, auto Y) {
+        hipLaunchKernelGGL((distill_partial_kernel<V(), Y()>), grid, dim3(256), 0, st, s, t, y, per, workspace);
+    }, vec, y != nullptr);
     int rc = check_launch("distill_partial");
     if (rc) return rc;
     hipLaunchKernelGGL(distill_final_kernel, dim3(groups), dim3(256), 0, st, workspace, nbs, 1.0 / (double)per, wt, wy, out);
@@ -280,7 +240,10 @@ int nvq_distill_backward(const float* s, const float* t, const float* y, int gro
     hipStream_t st = (hipStream_t)stream;
     const bool vec = (per & 3) == 0;
     const dim3 grid(group_blocks(per, groups), groups);
-    NVQ_DISTILL_DISPATCH(distill_backward_kernel, s, t, y, per, wt, wy, grad_out_dev, (float)(2.0 / (double)per), ds);
+    with_bools([&](auto V, auto Y) {
+        hipLaunchKernelGGL((distill_backward_kernel<V(), Y()>), grid, dim3(256), 0, st, s, t, y, per, wt, wy, grad_out_dev,
+                           (float)(2.0 / (double)per), ds);
+    }, vec, y != nullptr);
     return check_launch("distill_backward");
 }
 
@@ -300,8 +263,8 @@ int nvq_cosine_distill_forward(const float* s, const float* t, int B, int C, int
     int rc = check_launch("cosine_distill_partial");
     if (rc) return rc;
     const int groups = per_sample ? B : 1;
-    hipLaunchKernelGGL(cosine_final_kernel, dim3(groups), dim3(256), 0, st, workspace, per_sample ? nbx : B * nbx,
-                       1.0 / ((double)(per_sample ? 1 : B) * (double)hw), out);
+    launch_group_final(workspace, per_sample ? nbx : B * nbx, groups, 1.0 / ((double)(per_sample ? 1 : B) * (double)hw), 0.0, out,
+                       st);
     return check_launch("cosine_distill_final");
 }
 

@@ -2,7 +2,7 @@
 // on v_mfma_f64_16x16x4_f64, np.histogram-exact counts and the population stability index, per-cell mean / standard deviation
 // clip descriptors, and the sliding metric window of the performance monitor.  No float atomics anywhere: every sum is a
 // function of the shapes only, so a score is bit-reproducible.
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
 
@@ -13,14 +13,10 @@ constexpr int GK = 32;            // features staged per chunk
 constexpr int GLD = GK + 4;       // LDS row stride in floats: 36 r + k (r < 16, k < 4) covers 64 distinct banks
 constexpr int KLD = GT + 1;       // row stride in doubles of the finished tile
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum over 256 threads in a fixed order; valid in thread 0.  scratch: >= 4 doubles of LDS.
+// Sum over 256 threads in a fixed order; valid in thread 0.  scratch: >= 4 doubles of LDS.  The wave sums meet pairwise,
+// (w0 + w1) + (w2 + w3), not left to right as in flat.h's block_wave_sum_256: the order is part of the scores' bits.
 __device__ __forceinline__ double block_sum_f64_256(double v, double* scratch) {
-    v = wave_sum_f64(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -256,7 +252,7 @@ __global__ __launch_bounds__(256) void cell_descriptor_kernel(const float* __res
                 s += pass == 0 ? t : t * t;
             }
         }
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (pass == 0) mean = s / cnt;
         else dev = s / cnt;
     }
@@ -298,8 +294,6 @@ __global__ __launch_bounds__(256) void metric_window_kernel(const float* __restr
         flag[0] = (filled >= window && (b - mean) / b > (double)threshold) ? 1 : 0;
     }
 }
-
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace nvq
 

@@ -1,6 +1,6 @@
 // Elastic Weight Consolidation on flat parameter buckets: one launch instead of the
 // reference's ~5 tiny ops per parameter tensor (ewc.py:225-232, 139-141).
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
 
@@ -16,15 +16,6 @@ __global__ __launch_bounds__(256) void ewc_penalty_kernel(const float* __restric
     }
     s = block_sum_256(s, scratch);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-__global__ void ewc_penalty_final_kernel(const float* __restrict__ part, int nblk, float half_lambda,
-                                         float* __restrict__ out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s += (double)part[b];
-        *out = (float)((double)half_lambda * s);
-    }
 }
 
 __global__ __launch_bounds__(256) void ewc_grad_kernel(const float* __restrict__ theta, const float* __restrict__ star,
@@ -70,13 +61,6 @@ __global__ __launch_bounds__(256) void si_consolidate_kernel(const float* __rest
     }
 }
 
-static int flat_blocks(long n) {
-    int nb = ceil_div(n, 256L * 4);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return nb;
-}
-
 }  // namespace nvq
 
 using namespace nvq;
@@ -91,7 +75,7 @@ int nvq_ewc_penalty(const float* theta, const float* theta_star, const float* fi
     hipLaunchKernelGGL(ewc_penalty_kernel, dim3(nb), dim3(256), 0, s, theta, theta_star, fisher, n, workspace);
     int rc = check_launch("ewc_penalty");
     if (rc) return rc;
-    hipLaunchKernelGGL(ewc_penalty_final_kernel, dim3(1), dim3(64), 0, s, workspace, nb, 0.5f * lambda, out);
+    launch_serial_final(workspace, nb, (double)(0.5f * lambda), out, s);
     return check_launch("ewc_penalty_final");
 }
 

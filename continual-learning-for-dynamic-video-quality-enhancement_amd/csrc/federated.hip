@@ -8,37 +8,9 @@
 // No atomics; every grid depends on the sizes only; every thread owns whole quads (4 consecutive floats) in the vector and
 // in the scalar form alike and adds in one order, so a result depends neither on pointer alignment nor on the call.  The
 // noise is Philox4x32-10 keyed by (seed), counted by (quad index, offset): a function of (seed, offset, element) alone.
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
-
-__device__ __forceinline__ double fed_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 fed_ldq(const float* p) {
-    if (VEC) return ld4(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void fed_stq(float* p, float4 v) {
-    if (VEC) {
-        st4(p, v);
-    } else {
-        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-    }
-}
-
-// one quad per thread and trip, at most 1024 blocks: a function of n only
-static int fed_blocks(long n) {
-    int nb = ceil_div(n, 256L * 4);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return nb;
-}
 
 // ------------------------------------------------------------------ Philox4x32-10 and the normals of one quad
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
@@ -98,11 +70,11 @@ __global__ __launch_bounds__(256) void fed_delta_norms_kernel(const float* __res
     for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
     const long nq = n >> 2;
     for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        const float4 b = HAS_BASE ? fed_ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 b = HAS_BASE ? ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             if (k < K) {
-                const float4 x = fed_ldq<VEC>(clients + k * stride + 4 * q);
+                const float4 x = ldq<VEC>(clients + k * stride + 4 * q);
                 NVQ_SQDIFF(acc[k], x.x, b.x);
                 NVQ_SQDIFF(acc[k], x.y, b.y);
                 NVQ_SQDIFF(acc[k], x.z, b.z);
@@ -121,7 +93,7 @@ __global__ __launch_bounds__(256) void fed_delta_norms_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
         if (k < K) {
-            const double v = fed_wave_sum(acc[k]);
+            const double v = wave_sum(acc[k]);
             if ((threadIdx.x & 63) == 0) scratch[wave * KMAX + k] = v;
         }
     }
@@ -139,10 +111,8 @@ __global__ __launch_bounds__(256) void fed_delta_norms_final_kernel(const double
     const int k = blockIdx.x;
     double v = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 256) v += part[(long)b * K + k];
-    v = fed_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) sq[k] = scratch[0] + scratch[1] + scratch[2] + scratch[3];
+    block_wave_sum_256(scratch, v);
+    if (threadIdx.x == 0) sq[k] = v;
 }
 
 // ------------------------------------------------------------------ aggregate
@@ -169,10 +139,10 @@ __global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restr
     const double lr = (double)server_lr;
     const long nq = n >> 2;
     for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        const float4 b = HAS_BASE ? fed_ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 b = HAS_BASE ? ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
         double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
         for (int k = 0; k < K; ++k) {
-            const float4 x = fed_ldq<VEC>(clients + k * stride + 4 * q);
+            const float4 x = ldq<VEC>(clients + k * stride + 4 * q);
             const double c = coef[k];
             ax = fma(c, (double)x.x - (double)b.x, ax);
             ay = fma(c, (double)x.y - (double)b.y, ay);
@@ -187,7 +157,7 @@ __global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restr
             v.z = fmaf(noise_std, z.z, v.z);
             v.w = fmaf(noise_std, z.w, v.w);
         }
-        fed_stq<VEC>(out + 4 * q, v);
+        stq<VEC>(out + 4 * q, v);
     }
     const long t = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
     if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
@@ -237,10 +207,8 @@ __global__ __launch_bounds__(256) void dp_segment_norms_kernel(const float* __re
             v = fma(w, w, v);
         }
     }
-    v = fed_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = scratch[0] + scratch[1] + scratch[2] + scratch[3];
+    block_wave_sum_256(scratch, v);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 // thread s: sq[s] = the sum of slot s's chunks in table order (its first chunk by bisection: the table is sorted by slot)
@@ -300,9 +268,7 @@ static int dp_check(const char* what, const float* g, const long* seg_off, const
                 "%s: null pointer", what);
     NVQ_REQUIRE(S >= 1 && n_chunks >= 1, "%s: S = %d, n_chunks = %d", what, S, n_chunks);
     NVQ_REQUIRE(aligned16(g), "%s: the bucket must be 16-byte aligned (slots are whole quads)", what);
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(seg_off) & 7) == 0 && (reinterpret_cast<uintptr_t>(seg_numel) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(sq) & 7) == 0 && (reinterpret_cast<uintptr_t>(chunks) & 3) == 0,
-                "%s: table alignment", what);
+    NVQ_REQUIRE(aligned8(seg_off) && aligned8(seg_numel) && aligned8(sq) && aligned4(chunks), "%s: table alignment", what);
     return NVQ_OK;
 }
 
@@ -314,28 +280,16 @@ extern "C" {
 
 size_t nvq_fed_workspace_bytes(int K, long n) {
     if (K < 1 || n < 0) return 0;
-    return (size_t)fed_blocks(n) * (size_t)K * sizeof(double);
+    return (size_t)flat_blocks(n) * (size_t)K * sizeof(double);
 }
-
-#define NVQ_FED_NORMS(KMAX)                                                                                               \
-    do {                                                                                                                  \
-        if (base != nullptr) {                                                                                            \
-            if (vec) hipLaunchKernelGGL((fed_delta_norms_kernel<true, true, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);   \
-            else hipLaunchKernelGGL((fed_delta_norms_kernel<false, true, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);      \
-        } else {                                                                                                          \
-            if (vec) hipLaunchKernelGGL((fed_delta_norms_kernel<true, false, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);  \
-            else hipLaunchKernelGGL((fed_delta_norms_kernel<false, false, KMAX>), grid, block, 0, s, clients, stride, K, base, n, part);     \
-        }                                                                                                                 \
-    } while (0)
 
 int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* base, long n, double* sq, float* workspace,
                         size_t workspace_bytes, void* stream) {
     NVQ_REQUIRE(clients != nullptr && sq != nullptr && n >= 0, "fed_delta_norms: clients / sq / n");
     NVQ_REQUIRE(K >= 1 && K <= 64, "fed_delta_norms: K = %d outside 1 .. 64", K);
     NVQ_REQUIRE(stride >= n, "fed_delta_norms: stride %ld < n %ld", stride, n);
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(sq) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-                "fed_delta_norms: sq and workspace must be 8-byte aligned");
-    const int nb = fed_blocks(n);
+    NVQ_REQUIRE(aligned8(sq) && aligned8(workspace), "fed_delta_norms: sq and workspace must be 8-byte aligned");
+    const int nb = flat_blocks(n);
     if (workspace == nullptr || (size_t)nb * K * sizeof(double) > workspace_bytes) {
         set_error("fed_delta_norms: workspace");
         return NVQ_EWORKSPACE;
@@ -344,18 +298,17 @@ int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* b
     double* part = reinterpret_cast<double*>(workspace);
     const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base));
     const dim3 grid(nb), block(256);
-    if (K <= 8) NVQ_FED_NORMS(8);
-    else if (K <= 16) NVQ_FED_NORMS(16);
-    else NVQ_FED_NORMS(64);
+    with_bools([&](auto V, auto B) {
+        const auto kernel = K <= 8    ? fed_delta_norms_kernel<V(), B(), 8>
+                            : K <= 16 ? fed_delta_norms_kernel<V(), B(), 16>
+                                      : fed_delta_norms_kernel<V(), B(), 64>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, clients, stride, K, base, n, part);
+    }, vec, base != nullptr);
     int rc = check_launch("fed_delta_norms");
     if (rc) return rc;
     hipLaunchKernelGGL(fed_delta_norms_final_kernel, dim3(K), dim3(256), 0, s, part, nb, K, sq);
     return check_launch("fed_delta_norms_final");
 }
-
-#define NVQ_FED_AGG(VEC, HAS_BASE, NOISE)                                                                                 \
-    hipLaunchKernelGGL((fed_aggregate_kernel<VEC, HAS_BASE, NOISE>), grid, block, 0, s, clients, stride, K, base, weights, sq, \
-                       clip_norm, server_lr, noise_std, seed, offset, n, out)
 
 int nvq_fed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, const double* sq,
                       float clip_norm, float server_lr, float noise_std, long seed, long offset, long n, float* out,
@@ -365,19 +318,14 @@ int nvq_fed_aggregate(const float* clients, long stride, int K, const float* bas
     NVQ_REQUIRE(stride >= n, "fed_aggregate: stride %ld < n %ld", stride, n);
     NVQ_REQUIRE(seed >= 0 && offset >= 0, "fed_aggregate: seed and offset are non-negative");
     NVQ_REQUIRE(noise_std >= 0.f && (sq == nullptr || clip_norm >= 0.f), "fed_aggregate: noise_std / clip_norm");
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(weights) & 7) == 0 && (reinterpret_cast<uintptr_t>(sq) & 7) == 0,
-                "fed_aggregate: weights and sq must be 8-byte aligned");
+    NVQ_REQUIRE(aligned8(weights) && aligned8(sq), "fed_aggregate: weights and sq must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base)) && aligned16(out);
-    const bool noise = noise_std != 0.f;
-    const dim3 grid(fed_blocks(n)), block(256);
-    if (base != nullptr) {
-        if (vec) { if (noise) NVQ_FED_AGG(true, true, true); else NVQ_FED_AGG(true, true, false); }
-        else { if (noise) NVQ_FED_AGG(false, true, true); else NVQ_FED_AGG(false, true, false); }
-    } else {
-        if (vec) { if (noise) NVQ_FED_AGG(true, false, true); else NVQ_FED_AGG(true, false, false); }
-        else { if (noise) NVQ_FED_AGG(false, false, true); else NVQ_FED_AGG(false, false, false); }
-    }
+    const dim3 grid(flat_blocks(n)), block(256);
+    with_bools([&](auto V, auto B, auto N) {
+        hipLaunchKernelGGL((fed_aggregate_kernel<V(), B(), N()>), grid, block, 0, s, clients, stride, K, base, weights, sq,
+                           clip_norm, server_lr, noise_std, seed, offset, n, out);
+    }, vec, base != nullptr, noise_std != 0.f);
     return check_launch("fed_aggregate");
 }
 
@@ -385,7 +333,7 @@ int nvq_dp_segment_norms(const float* g, const long* seg_off, const long* seg_nu
                          double* sq, float* workspace, size_t workspace_bytes, void* stream) {
     int rc = dp_check("dp_segment_norms", g, seg_off, seg_numel, S, chunks, n_chunks, sq);
     if (rc) return rc;
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "dp_segment_norms: workspace must be 8-byte aligned");
+    NVQ_REQUIRE(aligned8(workspace), "dp_segment_norms: workspace must be 8-byte aligned");
     if (workspace == nullptr || (size_t)n_chunks * sizeof(double) > workspace_bytes) {
         set_error("dp_segment_norms: workspace");
         return NVQ_EWORKSPACE;
@@ -407,12 +355,10 @@ int nvq_dp_clip_noise(float* g, const long* seg_off, const long* seg_numel, int 
     NVQ_REQUIRE(max_norm >= 0.f && noise_scale >= 0.f, "dp_clip_noise: max_norm / noise_scale");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(n_chunks), block(256);
-    if (noise_scale != 0.f)
-        hipLaunchKernelGGL(dp_clip_noise_kernel<true>, grid, block, 0, s, g, seg_off, seg_numel, S, chunks, sq, max_norm,
+    with_bools([&](auto N) {
+        hipLaunchKernelGGL(dp_clip_noise_kernel<N()>, grid, block, 0, s, g, seg_off, seg_numel, S, chunks, sq, max_norm,
                            noise_scale, seed, offset);
-    else
-        hipLaunchKernelGGL(dp_clip_noise_kernel<false>, grid, block, 0, s, g, seg_off, seg_numel, S, chunks, sq, max_norm,
-                           noise_scale, seed, offset);
+    }, noise_scale != 0.f);
     return check_launch("dp_clip_noise");
 }
 

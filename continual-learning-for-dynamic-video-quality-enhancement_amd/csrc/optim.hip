@@ -5,7 +5,7 @@
 // float4 and the scalar form, the n % 4 last floats go to threads 0..2 of block 0.  Every fma is spelled out and contraction is
 // off in the element function, so the compiler cannot contract the two forms differently: an element's result depends on its
 // inputs only, never on the alignment of the pointers or on its position.  No atomics, no LDS.
-#include "common.h"
+#include "flat.h"
 
 #include <math.h>
 
@@ -48,21 +48,6 @@ __device__ __forceinline__ AdamOut adam_element(float theta, float g, float m, f
     return o;
 }
 
-template <bool VEC>
-__device__ __forceinline__ float4 ldq4(const float* p) {
-    if (VEC) return ld4(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void stq4(float* p, float4 x) {
-    if (VEC) {
-        st4(p, x);
-    } else {
-        p[0] = x.x; p[1] = x.y; p[2] = x.z; p[3] = x.w;
-    }
-}
-
 #define NVQ_ADAM_LANE(c)                                                                  \
     do {                                                                                  \
         const AdamOut o = adam_element<HAS_EMA>(t.c, g.c, m.c, v.c, e.c, a, clip, cf);     \
@@ -84,19 +69,19 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ thet
     }
     const long nq = n >> 2;
     for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        float4 t = ldq4<VEC>(theta + 4 * q);
-        const float4 g = ldq4<VEC>(grad + 4 * q);
-        float4 m = ldq4<VEC>(exp_avg + 4 * q);
-        float4 v = ldq4<VEC>(exp_avg_sq + 4 * q);
-        float4 e = HAS_EMA ? ldq4<VEC>(ema + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 t = ldq<VEC>(theta + 4 * q);
+        const float4 g = ldq<VEC>(grad + 4 * q);
+        float4 m = ldq<VEC>(exp_avg + 4 * q);
+        float4 v = ldq<VEC>(exp_avg_sq + 4 * q);
+        float4 e = HAS_EMA ? ldq<VEC>(ema + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
         NVQ_ADAM_LANE(x);
         NVQ_ADAM_LANE(y);
         NVQ_ADAM_LANE(z);
         NVQ_ADAM_LANE(w);
-        stq4<VEC>(theta + 4 * q, t);
-        stq4<VEC>(exp_avg + 4 * q, m);
-        stq4<VEC>(exp_avg_sq + 4 * q, v);
-        if (HAS_EMA) stq4<VEC>(ema + 4 * q, e);
+        stq<VEC>(theta + 4 * q, t);
+        stq<VEC>(exp_avg + 4 * q, m);
+        stq<VEC>(exp_avg_sq + 4 * q, v);
+        if (HAS_EMA) stq<VEC>(ema + 4 * q, e);
     }
     const long i = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
     if (blockIdx.x == 0 && threadIdx.x < 3 && i < n) {
@@ -107,16 +92,6 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ thet
         if (HAS_EMA) ema[i] = o.ema;
     }
 }
-
-// one quad per thread and trip, at most 1024 blocks: a function of n only
-static int adam_blocks(long n) {
-    int nb = ceil_div(n, 256L * 4);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return nb;
-}
-
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 }  // namespace nvq
 
@@ -133,7 +108,7 @@ int nvq_adam_step(float* theta, const float* grad, float* exp_avg, float* exp_av
                 "adam_step: theta / grad / exp_avg / exp_avg_sq must not be NULL");
     NVQ_REQUIRE(aligned4(theta) && aligned4(grad) && aligned4(exp_avg) && aligned4(exp_avg_sq) && aligned4(ema),
                 "adam_step: pointers must be 4-byte aligned");
-    NVQ_REQUIRE((reinterpret_cast<uintptr_t>(acc) & 7) == 0, "adam_step: acc must be 8-byte aligned");
+    NVQ_REQUIRE(aligned8(acc), "adam_step: acc must be 8-byte aligned");
     NVQ_REQUIRE(bias1 > 0.f && bias2_sqrt > 0.f, "adam_step: bias1 = %g, bias2_sqrt = %g (step count < 1?)", (double)bias1,
                 (double)bias2_sqrt);
     NVQ_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam_step: betas = (%g, %g)", (double)beta1,
@@ -152,15 +127,11 @@ int nvq_adam_step(float* theta, const float* grad, float* exp_avg, float* exp_av
     a.decoupled = decoupled != 0;
     const bool vec = aligned16(theta) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) &&
                      (ema == nullptr || aligned16(ema));
-    const dim3 grid(adam_blocks(n)), block(256);
+    const dim3 grid(flat_blocks(n)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (ema != nullptr) {
-        if (vec) hipLaunchKernelGGL((adam_step_kernel<true, true>), grid, block, 0, s, theta, grad, exp_avg, exp_avg_sq, ema, n, a, acc);
-        else hipLaunchKernelGGL((adam_step_kernel<false, true>), grid, block, 0, s, theta, grad, exp_avg, exp_avg_sq, ema, n, a, acc);
-    } else {
-        if (vec) hipLaunchKernelGGL((adam_step_kernel<true, false>), grid, block, 0, s, theta, grad, exp_avg, exp_avg_sq, ema, n, a, acc);
-        else hipLaunchKernelGGL((adam_step_kernel<false, false>), grid, block, 0, s, theta, grad, exp_avg, exp_avg_sq, ema, n, a, acc);
-    }
+    with_bools([&](auto V, auto E) {
+        hipLaunchKernelGGL((adam_step_kernel<V(), E()>), grid, block, 0, s, theta, grad, exp_avg, exp_avg_sq, ema, n, a, acc);
+    }, vec, ema != nullptr);
     return check_launch("adam_step");
 }
 

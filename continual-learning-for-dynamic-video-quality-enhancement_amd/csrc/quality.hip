@@ -3,7 +3,7 @@
 // Everything is fp32 on the VALU with two-stage reductions (fp32 per block, double in fixed order across blocks): no float
 // atomics anywhere, so two runs give the same bits.
 //
-// quality_sums / pixel_loss: the mse_partial / mse_final pattern of loss.hip with blockIdx.y = sample (a workgroup never
+// quality_sums / pixel_loss: the two-stage pattern of loss.hip with blockIdx.y = sample (a workgroup never
 // straddles two samples).  HBM-bound: two reads per element (+ one write for the pixel-loss backward).
 //
 // SSIM: one workgroup per (image plane, tile).  `moments_tile` stages the x and y tiles with their halo in LDS, runs the
@@ -14,7 +14,7 @@
 //
 // Multi-scale SSIM: the same two kernels per scale of a 2 x 2 mean pyramid with a contrast-structure
 // functor, one launch that pools x and y together, and a finalize that forms the clamped weighted product and its derivatives.
-#include "common.h"
+#include "flat.h"
 
 namespace nvq {
 
@@ -34,18 +34,6 @@ Taps gaussian_taps() {
     }
     for (int i = 0; i < kTaps; ++i) t.g[i] /= s;
     return t;
-}
-
-// Block-wide sum of a double over 256 threads in a fixed tree order; result valid in thread 0. scratch: 256 doubles of LDS.
-__device__ __forceinline__ double block_sum_256_f64(double v, double* scratch) {
-    __syncthreads();
-    scratch[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) scratch[threadIdx.x] += scratch[threadIdx.x + o];
-        __syncthreads();
-    }
-    return scratch[0];
 }
 
 // ------------------------------------------------------------------------------------------------ sums and pixel losses
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(256) void quality_sums_final_kernel(const float* __
     for (int q = 0; q < kSums; ++q) {
         double s = 0.0;
         for (int k = threadIdx.x; k < nbs; k += 256) s += (double)p[(long)k * kSums + q];
-        s = block_sum_256_f64(s, scratch);
+        s = block_tree_sum_256(s, scratch);
         if (threadIdx.x == 0) out[blockIdx.x * 8 + 1 + q] = s;
     }
     if (threadIdx.x == 0) out[blockIdx.x * 8] = (double)per;
@@ -138,17 +126,6 @@ __global__ __launch_bounds__(256) void pixel_loss_partial_kernel(const float* __
     if (threadIdx.x == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
-// grid (G): out[g] = bias + alpha * sum_k part[g * nblk + k], in double in a fixed order
-__global__ __launch_bounds__(256) void group_final_kernel(const float* __restrict__ part, int nblk, double alpha, double bias,
-                                                          float* __restrict__ out) {
-    __shared__ double scratch[256];
-    const float* p = part + (long)blockIdx.x * nblk;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nblk; k += 256) s += (double)p[k];
-    s = block_sum_256_f64(s, scratch);
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(bias + alpha * s);
-}
-
 // dx = go[g] * f'(x - y) / per
 template <int KIND, bool VEC>
 __global__ __launch_bounds__(256) void pixel_loss_backward_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -170,13 +147,6 @@ __global__ __launch_bounds__(256) void pixel_loss_backward_kernel(const float* _
         for (long i = blockIdx.x * 256L + threadIdx.x; i < per; i += (long)gridDim.x * 256)
             ds[i] = sc * pixel_slope<KIND>(xs[i] - ys[i], eps2);
     }
-}
-
-int group_blocks(long per, int groups) {
-    int nb = ceil_div(per, 256L * 16);
-    const int cap = groups == 1 ? 2048 : 1024;
-    if (nb > cap) nb = cap;
-    return nb < 1 ? 1 : nb;
 }
 
 // ------------------------------------------------------------------------------------------------------ windowed SSIM
@@ -519,7 +489,7 @@ __global__ __launch_bounds__(1024) void msssim_finalize_kernel(const float* __re
                                                                const float* __restrict__ w, int per_sample, int as_loss,
                                                                float* __restrict__ out, float* __restrict__ mt,
                                                                float* __restrict__ dt) {
-    __shared__ double wave_sum[16];
+    __shared__ double wave_acc[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long planes = (long)B * C;
     const double wj = lane < M ? (double)w[lane] : 0.0;
@@ -534,7 +504,7 @@ __global__ __launch_bounds__(1024) void msssim_finalize_kernel(const float* __re
                 const float* q = part + g.off[j] + plane * n;
                 double s = 0.0;
                 for (int k = lane; k < n; k += 64) s += (double)q[k];
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                s = wave_sum(s);
                 if (lane == j) m = s * g.inv_count[j];
             }
             const double pw = lane < M ? (m > 0.0 ? pow(m, wj) : 0.0) : 1.0;
@@ -558,11 +528,11 @@ __global__ __launch_bounds__(1024) void msssim_finalize_kernel(const float* __re
         }
     }
     if (per_sample) return;
-    if (lane == 0) wave_sum[wave] = acc;
+    if (lane == 0) wave_acc[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = 0.0;
-        for (int k = 0; k < 16; ++k) s += wave_sum[k];
+        for (int k = 0; k < 16; ++k) s += wave_acc[k];
         s /= (double)B;
         out[0] = (float)(as_loss ? 1.0 - s : s);
     }
@@ -684,7 +654,7 @@ extern "C" {
 
 int nvq_quality_sums(const float* x, const float* y, int B, long per, double* out, float* workspace, size_t workspace_bytes,
                      void* stream) {
-    NVQ_REQUIRE(B > 0 && B <= 65535 && per > 0 && aligned16(x) && aligned16(y) && ((uintptr_t)out & 7) == 0,
+    NVQ_REQUIRE(B > 0 && B <= 65535 && per > 0 && aligned16(x) && aligned16(y) && aligned8(out),
                 "quality_sums: 0 < B <= 65535, per > 0, 16-byte aligned tensors");
     const int nbs = group_blocks(per, B);
     if ((size_t)B * nbs * kSums * sizeof(float) > workspace_bytes) { set_error("quality_sums: workspace"); return NVQ_EWORKSPACE; }
@@ -699,19 +669,13 @@ int nvq_quality_sums(const float* x, const float* y, int B, long per, double* ou
     return check_launch("quality_sums_final");
 }
 
-#define NVQ_PIXEL_DISPATCH(KERNEL, ...)                                                                        \
-    do {                                                                                                       \
-        if (kind == NVQ_LOSS_L1) {                                                                             \
-            if (vec) hipLaunchKernelGGL((KERNEL<NVQ_LOSS_L1, true>), grid, dim3(256), 0, s, __VA_ARGS__);      \
-            else hipLaunchKernelGGL((KERNEL<NVQ_LOSS_L1, false>), grid, dim3(256), 0, s, __VA_ARGS__);         \
-        } else if (kind == NVQ_LOSS_CHARBONNIER) {                                                             \
-            if (vec) hipLaunchKernelGGL((KERNEL<NVQ_LOSS_CHARBONNIER, true>), grid, dim3(256), 0, s, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<NVQ_LOSS_CHARBONNIER, false>), grid, dim3(256), 0, s, __VA_ARGS__);    \
-        } else {                                                                                               \
-            if (vec) hipLaunchKernelGGL((KERNEL<NVQ_LOSS_MSE, true>), grid, dim3(256), 0, s, __VA_ARGS__);     \
-            else hipLaunchKernelGGL((KERNEL<NVQ_LOSS_MSE, false>), grid, dim3(256), 0, s, __VA_ARGS__);        \
-        }                                                                                                      \
-    } while (0)
+#define NVQ_PIXEL_DISPATCH(KERNEL, ...)                                                                                  \
+    with_bools([&](auto V) {                                                                                             \
+        if (kind == NVQ_LOSS_L1) hipLaunchKernelGGL((KERNEL<NVQ_LOSS_L1, V()>), grid, dim3(256), 0, s, __VA_ARGS__);     \
+        else if (kind == NVQ_LOSS_CHARBONNIER)                                                                           \
+            hipLaunchKernelGGL((KERNEL<NVQ_LOSS_CHARBONNIER, V()>), grid, dim3(256), 0, s, __VA_ARGS__);                 \
+        else hipLaunchKernelGGL((KERNEL<NVQ_LOSS_MSE, V()>), grid, dim3(256), 0, s, __VA_ARGS__);                        \
+    }, vec)
 
 int nvq_pixel_loss_forward(const float* x, const float* y, int groups, long per, int kind, float eps, float* out,
                            float* workspace, size_t workspace_bytes, void* stream) {
@@ -726,7 +690,7 @@ int nvq_pixel_loss_forward(const float* x, const float* y, int groups, long per,
     NVQ_PIXEL_DISPATCH(pixel_loss_partial_kernel, x, y, per, eps * eps, workspace);
     int rc = check_launch("pixel_loss_partial");
     if (rc) return rc;
-    hipLaunchKernelGGL(group_final_kernel, dim3(groups), dim3(256), 0, s, workspace, nbs, 1.0 / (double)per, 0.0, out);
+    launch_group_final(workspace, nbs, groups, 1.0 / (double)per, 0.0, out, s);
     return check_launch("pixel_loss_final");
 }
 
@@ -767,8 +731,7 @@ int nvq_ssim_forward(const float* x, const float* y, int B, int C, int H, int W,
     if (rc) return rc;
     const int groups = per_sample ? B : 1;
     const double count = (double)(tiles / groups) / ((double)tx * ty) * (double)(H - kHalo) * (double)(W - kHalo);
-    hipLaunchKernelGGL(group_final_kernel, dim3(groups), dim3(256), 0, s, workspace, (int)(tiles / groups),
-                       (as_loss ? -1.0 : 1.0) / count, as_loss ? 1.0 : 0.0, out);
+    launch_group_final(workspace, (int)(tiles / groups), groups, (as_loss ? -1.0 : 1.0) / count, as_loss ? 1.0 : 0.0, out, s);
     return check_launch("ssim_final");
 }
 

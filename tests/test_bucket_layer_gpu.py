@@ -7,7 +7,7 @@ consumer launches once over the whole bucket per network plus once per loose par
 Accumulated state (two backwards): autograd replaced ``.grad`` by sums, nothing aliases; one launch per parameter with a gradient.
 The expected sequences are computed here from ``_bucket_layout()`` and the parameter list.
 
-Equivalence.  csrc/bucket_ops.hip: ``bucket_moments_kernel`` sums per block of ``bucket_blocks(n)`` blocks and the final kernel
+Equivalence.  csrc/bucket_ops.hip: ``bucket_moments_kernel`` sums per block of ``flat_blocks(n)`` blocks and the final kernel
 adds the block partials, so g.r / r.r / g.g over ONE bucket and over 47 tensors chained with ``accumulate`` are double sums of the
 same exact products in a different order: they MAY differ in their last bits, for all three consumers that read them (project:
 c = g.r / r.r; clip and nvq_adam_step: coef = max_norm / (sqrt(g.g) + 1e-6)).  ``bucket_project_kernel``, ``bucket_clip_kernel``
