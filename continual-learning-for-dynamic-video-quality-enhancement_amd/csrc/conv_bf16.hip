@@ -926,11 +926,19 @@ __global__ __launch_bounds__(512, 4) void rdb_tail8_kernel(const nvq_conv_desc d
 // the per-tile iteration is latency-bound, so doing more per iteration is what pays.
 // COC: output channels per workgroup (32, or 64 for the 1x1 kernel with bf16 dy: its accumulators are one fragment per
 // (ci, co) block, so a wave takes all four 16-co blocks and the x tile is fetched once instead of once per 32 co).
-template <int KS, bool XB, bool YB, int CIC, int COC = 32>
-__global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc d, int tilesX, int tilesY,
-                                                             int ntiles, int nci32, int nco) {
+// NW: waves per workgroup.  8 (3x3, 64 ci x 64 co): the 3x3 form of the 64-co workgroup.  Four 16-co blocks x 9 taps would be
+// 144 accumulator registers per lane, so the workgroup's waves split in two halves as conv_bf16_kernel<.., CS = 2> does: waves
+// 0-3 own co blocks 0-1, waves 4-7 co blocks 2-3 of the SAME staged tiles (72 accumulator registers, as with 32 co), and the
+// 512 threads share the staging (6 x pieces and 4 dy pieces each).  The x halo tile is then fetched once per 64 co instead of
+// once per 32.  95 KB of LDS: one workgroup per CU, the same two waves per SIMD as two 256-thread workgroups.
+template <int KS, bool XB, bool YB, int CIC, int COC = 32, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc d, int tilesX, int tilesY,
+                                                                int ntiles, int nci32, int nco) {
     static_assert(CIC == 32 || (CIC == 64 && XB), "64-channel chunks need bf16 x");
-    static_assert(COC == 32 || (COC == 64 && CIC == 64 && YB && KS == 1), "64-co chunks: 1x1, bf16 x and dy");
+    static_assert(COC == 32 || (COC == 64 && CIC == 64 && YB && (KS == 1 || NW == 8)),
+                  "64-co chunks: bf16 x and dy; 3x3 with eight waves");
+    static_assert(NW == 4 || (NW == 8 && KS == 3 && COC == 64), "eight waves: the 3x3 64-co form");
+    constexpr int NTHR = 64 * NW;
     constexpr int HALO = KS / 2;
     constexpr int TAPS = KS * KS;
     constexpr int HW_ = TW + 2 * HALO;
@@ -942,21 +950,22 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
     constexpr int YPP = (YB ? 4 : 8) * (COC / 32);
     constexpr int XCH = CIC / XPP, YCH = COC / YPP;   // channels per piece
     constexpr int XITEMS = NPIX * XPP;
-    constexpr int XPER = (XITEMS + 255) / 256;
-    constexpr int YPER = TH * TW * YPP / 256;
-    constexpr int NCO = (CIC == 64 ? 2 : 1) * (COC / 32);   // 16-co blocks per wave
+    constexpr int XPER = (XITEMS + NTHR - 1) / NTHR;
+    constexpr int YPER = TH * TW * YPP / NTHR;
+    constexpr int NCO = (CIC == 64 ? 2 : 1) * (COC / 32) / (NW / 4);   // 16-co blocks per wave
     __shared__ __attribute__((aligned(16))) __bf16 lds[NPIX * XSX + TH * TW * YSX];
     __bf16* xs = lds;
     __bf16* dys = lds + NPIX * XSX;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int wave = NW == 8 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int r = lane & 15;
     const int g = lane >> 4;
     const int q = r >> 2, p = r & 3;                 // tr-read role of this lane inside its 16-lane group
-    const int cib = CIC == 64 ? wave : wave >> 1;    // 16-ci block of this wave inside the chunk
-    const int cob0 = CIC == 64 ? 0 : (wave & 1);
+    // 16-ci block of this wave inside the chunk, and its first 16-co block (eight waves: the wave's co half)
+    const int cib = NW == 8 ? wave & 3 : (CIC == 64 ? wave : wave >> 1);
+    const int cob0 = NW == 8 ? (wave >> 2) * NCO : (CIC == 64 ? 0 : (wave & 1));
     const int cic = blockIdx.y, coc = blockIdx.z;
     const int H = d.h, W = d.w;
     const float* x32 = d.x + d.x_coff;
@@ -995,7 +1004,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         xmask = 0; ymask = 0;
 #pragma unroll
         for (int k = 0; k < XPER; ++k) {
-            const int item = tid + k * 256;
+            const int item = tid + k * NTHR;
             const int hp = item / XPP;
             const int hy = hp / HW_, hx = hp - hy * HW_;
             const int gy = ty * TH + hy - HALO, gx = tx * TW + hx - HALO;
@@ -1007,7 +1016,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         }
 #pragma unroll
         for (int k = 0; k < YPER; ++k) {
-            const int item = tid + k * 256;
+            const int item = tid + k * NTHR;
             const int pp = item / YPP;
             const int py = pp / TW, px = pp - py * TW;
             const int gy = ty * TH + py, gx = tx * TW + px;
@@ -1024,7 +1033,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int k = 0; k < XPER; ++k) {
-            const int item = tid + k * 256;
+            const int item = tid + k * NTHR;
             if (item < XITEMS) {
                 const u32x4 v = (xmask >> k) & 1 ? xr[k] : z;
                 __bf16* dst = xs + (item / XPP) * XSX + XCH * (item & (XPP - 1));
@@ -1034,7 +1043,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         }
 #pragma unroll
         for (int k = 0; k < YPER; ++k) {
-            const int item = tid + k * 256;
+            const int item = tid + k * NTHR;
             const u32x4 v = (ymask >> k) & 1 ? yr[k] : z;
             __bf16* dst = dys + (item / YPP) * YSX + YCH * (item & (YPP - 1));
             if constexpr (YB) {
@@ -1050,7 +1059,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
     };
     // a wave whose 16 input channels lie beyond the tensor's (the second half of a 64-channel chunk when cin % 64 == 32) has
     // nothing to accumulate: it keeps staging with the others but leaves the matrix cores to the workgroup sharing the CU
-    const bool idle = cic * CIC + cib * 16 >= d.cin_w;
+    // (eight waves: likewise a wave whose two 16-co blocks both lie beyond cout: cout = 81 leaves 17 live channels, the blocks of
+    // waves 0-3, to the second 64-co workgroup.  A wave with one live block of its two runs both: the dead block's dy is staged
+    // as zeros, and a scalar branch per MFMA to skip it - built - breaks up the MFMA run of every wave.)
+    const bool co_dead = NW == 8 && coc * COC + cob0 * 16 >= d.cout;
+    const bool idle = cic * CIC + cib * 16 >= d.cin_w || co_dead;
     typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
     auto tr_read = [&](const __bf16* base, int stride, int pix, int chblock) -> s16x4 {
         // lane (q, p) supplies row `pix + q`'s address, columns 4p..4p+3 of the 16-channel block
@@ -1065,6 +1078,40 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         __syncthreads();
         if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
         if (idle) continue;                                   // (wave-uniform; the wave still staged and met the barriers)
+        if constexpr (NW == 8) {
+            // The eight-wave form walks the tile's HH_ halo rows of x instead of its TH rows of dy: the x fragment of halo row
+            // hy and column offset ddx serves the taps (ddy, ddx) of the dy rows hy - ddy, so it is read once instead of up to
+            // three times (60 x + 32 dy fragment reads per wave and tile instead of 144 + 32: with one workgroup per CU the LDS
+            // reads were as long as the MFMAs).  Every accumulator still sums its rows in ascending order: the same results.
+            bf16x8 bfrag[TH][NCO];                            // (fully unrolled: three rows are live at a time)
+#pragma unroll
+            for (int hy = 0; hy < HH_; ++hy) {
+                if (hy < TH) {
+#pragma unroll
+                    for (int a = 0; a < NCO; ++a) {
+                        const s16x4 b0 = tr_read(dys, YSX, hy * TW + 4 * g, cob0 + a);
+                        const s16x4 b1 = tr_read(dys, YSX, hy * TW + 16 + 4 * g, cob0 + a);
+                        bfrag[hy][a] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+                    }
+                }
+#pragma unroll
+                for (int ddx = 0; ddx < KS; ++ddx) {
+                    const s16x4 a0 = tr_read(xs, XSX, hy * HW_ + ddx + 4 * g, cib);
+                    const s16x4 a1 = tr_read(xs, XSX, hy * HW_ + ddx + 16 + 4 * g, cib);
+                    const bf16x8 afrag = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+                    for (int ddy = 0; ddy < KS; ++ddy) {
+                        const int py = hy - ddy;
+                        if (py < 0 || py >= TH) continue;
+#pragma unroll
+                        for (int a = 0; a < NCO; ++a)
+                            acc[a][ddy * KS + ddx] =
+                                __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, bfrag[py][a], acc[a][ddy * KS + ddx], 0, 0, 0);
+                    }
+                }
+            }
+            continue;
+        }
 #pragma unroll 2
         for (int py = 0; py < TH; ++py) {
             bf16x8 bfrag[NCO];
@@ -1107,7 +1154,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
 
     // bias partials: thread t's sums cover channels yq..yq+YCH-1 of the co chunk, pieces repeat every YPP threads
     if (cic == 0 && d.dbias != nullptr) {                    // uniform per workgroup
-        float* scratch = reinterpret_cast<float*>(lds);      // 256 x 8 floats
+        float* scratch = reinterpret_cast<float*>(lds);      // NTHR x 8 floats
         __syncthreads();
         st4(scratch + 8 * tid, bsumA);
         st4(scratch + 8 * tid + 4, bsumB);
@@ -1115,7 +1162,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const nvq_wgrad_desc
         if (tid < COC) {
             const int piece = tid / YCH, e = tid % YCH;      // channel `tid` of the chunk
             float s = 0.f;
-            for (int k = 0; k < 256 / YPP; ++k) s += scratch[8 * (YPP * k + piece) + e];
+            for (int k = 0; k < NTHR / YPP; ++k) s += scratch[8 * (YPP * k + piece) + e];
             float* bp = d.workspace + (size_t)WGRAD_MAX_SLABS * 9 * WG_C * WG_C;
             const int coc32 = coc * (COC / 32) + tid / WG_C;
             if (coc32 < nco) bp[((size_t)blockIdx.x * nco + coc32) * WG_C + tid % WG_C] = s;
@@ -1270,9 +1317,30 @@ int rdb_tail_bf16(const nvq_conv_desc& d3, const nvq_conv_desc& dl, int vec3, in
 
 int conv_wgrad_bf16(const nvq_wgrad_desc& d, int nsplit, int nci, int nco, int tilesX, int tilesY, int ntiles,
                     hipStream_t s) {
-    if ((d.variant & 15) != 1 && wgrad_m32_takes(d)) return conv_wgrad_m32(d, s);
-    NVQ_REQUIRE((d.variant & 15) != 2, "conv_wgrad: variant 2 (all-input-channel kernel) does not take %d -> %d channels, ksize %d",
+    const int variant = d.variant & 15;
+    if (variant != 1 && variant != 3 && wgrad_m32_takes(d)) return conv_wgrad_m32(d, s);
+    NVQ_REQUIRE(variant != 2, "conv_wgrad: variant 2 (all-input-channel kernel) does not take %d -> %d channels, ksize %d",
                 d.cin, d.cout, d.ksize);
+    // 3x3, bf16 x and dy, more than 32 output channels: eight waves take 64 ci x 64 co (the x halo tile fetched once per 64 co
+    // instead of once per 32; variant 3 keeps the 32-co workgroups).  One workgroup per CU (95 KB of LDS), so half of
+    // WGRAD_MAX_WG fills the device.  A chunk with fewer than 64 input channels just has idle waves; with no more than 32 (one
+    // 32-ci chunk: the first layers, 3 / 16 / 32 -> 64) half of the ci waves are idle and the 32 x 32 workgroups stay, which
+    // stage a 32-channel x tile (0.82 - 0.94x with this form there; 1.40x at 40 and 48 input channels: DESIGN.md section 5).
+    if (d.ksize == 3 && d.x_bf16 && d.dy_bf16 && d.cout > 32 && d.cin_w > 32 && variant != 3) {
+        const int ncig = (nci + 1) / 2, nco64 = (nco + 1) / 2;
+        nsplit = WGRAD_MAX_WG / 2 / (ncig * nco64);
+        // the partial slabs (one per split x 32-ci chunk x 32-co chunk, taps * 32 * 32 floats each) must fit the workspace
+        const int cap = WGRAD_MAX_SLABS / (nci * nco);
+        if (nsplit > cap) nsplit = cap;
+        if (nsplit < 1) nsplit = 1;
+        if (nsplit > ntiles) nsplit = ntiles;
+        if (nsplit >= 8) nsplit &= ~7;      // multiple of the XCD count: see xcd_tile()
+        NVQ_REQUIRE((size_t)nsplit * nci * nco * 9 <= (size_t)WGRAD_MAX_SLABS * 9,
+                    "conv_wgrad(bf16, 3x3, 64 co): %d splits x %d x %d chunks exceed the workspace", nsplit, nci, nco);
+        hipLaunchKernelGGL((wgrad_bf16_kernel<3, true, true, 64, 64, 8>), dim3(nsplit, ncig, nco64), dim3(512), 0, s, d, tilesX,
+                           tilesY, ntiles, nci, nco);
+        return nsplit;
+    }
     // nsplit / nci come from the caller in 32-ci units; with bf16 x and >= 64 input channels use 64-ci workgroups
     const bool wide = d.x_bf16 && d.dy_bf16 && d.cin_w >= 64;   // (the bf16-x / fp32-dy wide variant spills)
     const int ncig = wide ? (nci + 1) / 2 : nci;

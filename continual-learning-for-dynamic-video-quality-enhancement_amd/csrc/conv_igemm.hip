@@ -782,9 +782,10 @@ static int wgrad_partial(const nvq_wgrad_desc* dp, nvq_wgrad_reduce_job* job, vo
     NVQ_REQUIRE(d.cin_w > 0 && d.cin_w <= d.cin && d.cout > 0, "conv_wgrad: channels");
     NVQ_REQUIRE(!(d.x_bf16 | d.dy_bf16) || d.math == NVQ_MATH_BF16, "conv_wgrad: bf16 tensors need NVQ_MATH_BF16");
     NVQ_REQUIRE(!d.x_bf16 || (d.cin % 8 == 0 && d.x_ld % 8 == 0 && d.x_coff % 8 == 0), "conv_wgrad: bf16 x alignment");
-    NVQ_REQUIRE(!d.dy_bf16 || (d.cout % 8 == 0 && d.dy_ld % 8 == 0 && d.dy_coff % 8 == 0), "conv_wgrad: bf16 dy alignment");
-    NVQ_REQUIRE(d.math != NVQ_MATH_BF16 || d.dy_coff + ((d.cout + 3) & ~3) <= d.dy_ld,
-                "conv_wgrad(bf16): the dy slice must be readable up to a multiple of 4 channels");
+    // (cout itself may be any number: the kernels stage dy in 16-byte pieces and never write the sums of channels >= cout)
+    NVQ_REQUIRE(!d.dy_bf16 || (d.dy_ld % 8 == 0 && d.dy_coff % 8 == 0), "conv_wgrad: bf16 dy alignment");
+    NVQ_REQUIRE(d.math != NVQ_MATH_BF16 || d.dy_coff + ((d.cout + (d.dy_bf16 ? 7 : 3)) & (d.dy_bf16 ? ~7 : ~3)) <= d.dy_ld,
+                "conv_wgrad(bf16): the dy slice must be readable up to a multiple of 4 (fp32) / 8 (bf16) channels");
     NVQ_REQUIRE(d.workspace_bytes >= nvq_wgrad_workspace_bytes(), "conv_wgrad: workspace too small");
     NVQ_REQUIRE(!d.x_plane || (d.math == NVQ_MATH_BF16 && d.x_bf16 && d.x_coff == 0 && d.cin % 32 == 0 &&
                                (d.x_ld == 32 || d.x_ld == 64 || d.x_ld == 128) && d.x_ld <= d.cin &&

@@ -162,7 +162,9 @@ typedef struct nvq_wgrad_desc {
      * (pixel split, ci chunk, co chunk) kernels; 2 = always the all-input-channel kernels (an error for a shape they do not
      * take).  The all-input-channel kernels (bf16 x and dy; 3x3: cout = 32, slice-planar x, cin in {96, .., 192}; 1x1: cin in
      * {64, .., 256}, cout <= 64) read x without halo and dy once per launch, as persistent workgroups; automatic from four
-     * 4x32-pixel tiles per workgroup on (smaller launches: the split kernels).  Lets a caller A/B the two forms. */
+     * 4x32-pixel tiles per workgroup on (smaller launches: the split kernels).  Lets a caller A/B the two forms.
+     * 3 = as 1, and the split kernel keeps 32 output channels per workgroup where it would take 64 (3x3, bf16 x and dy,
+     * cout > 32: eight waves stage the x tile once per 64 output channels). */
     int variant;
 } nvq_wgrad_desc;
 size_t nvq_wgrad_workspace_bytes(void);   /* upper bound valid for every shape */
