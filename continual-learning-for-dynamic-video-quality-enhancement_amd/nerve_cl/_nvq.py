@@ -249,6 +249,10 @@ SIGNATURES = {
     "nvq_fed_aggregate": (ci, [vp, cl, ci, vp, vp, vp, cf, cf, cf, cl, cl, cl, vp, vp]),
     "nvq_dp_segment_norms": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, sz, vp]),
     "nvq_dp_clip_noise": (ci, [vp, vp, vp, ci, vp, ci, vp, cf, cf, cl, cl, vp]),
+    "nvq_fed_gram_workspace_bytes": (sz, [ci, cl]),
+    "nvq_fed_update_gram": (ci, [vp, cl, ci, vp, cl, vp, vp, sz, vp]),
+    "nvq_cluster_gram_kmeans": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+    "nvq_fed_aggregate_clusters": (ci, [vp, cl, ci, vp, ci, vp, cl, vp, vp, cf, cf, cf, cl, cl, cl, vp, cl, vp]),
 }
 
 
@@ -1551,3 +1555,60 @@ def dp_clip_noise(g: torch.Tensor, table: DpTable, max_norm: float, noise_scale:
     check(lib().nvq_dp_clip_noise(_dp_bucket(g, table), ptr(table.seg_off), ptr(table.seg_numel), table.S, ptr(table.chunks),
                                   table.n_chunks, ptr(table.sq), float(max_norm), float(noise_scale), int(seed), int(offset),
                                   stream()), "nvq_dp_clip_noise")
+
+
+# ----------------------------------------------------------------------------- clustered federated learning
+CLUSTER_MAX = 8
+
+
+def fed_gram_workspace_bytes(K: int, n: int) -> int:
+    return int(lib().nvq_fed_gram_workspace_bytes(int(K), int(n)))
+
+
+def _rows_stride(m: torch.Tensor, n: int, what: str) -> int:
+    """row stride of a [R][stride] fp32 matrix with rows of at least n floats (a one-row matrix: any stride >= n serves)"""
+    assert m.dtype == torch.float32 and m.dim() == 2 and m.stride(1) == 1 and m.shape[1] >= n, f"{what}: a [rows][stride] fp32 matrix"
+    require_device(m, what)
+    stride = m.stride(0) if m.shape[0] > 1 else max(m.stride(0), m.shape[1])
+    assert stride >= n, f"{what}: row stride {stride} < n {n}"
+    return stride
+
+
+def fed_update_gram(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], gram: torch.Tensor, ws: torch.Tensor) -> None:
+    """gram[i, j] = sum_t (clients[i, t] - base[t]) (clients[j, t] - base[t]) over the first n columns (nvq_fed_update_gram)"""
+    K, stride = _fed_rows(clients, n)
+    assert gram.dtype == torch.float64 and gram.numel() >= K * K and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    check(lib().nvq_fed_update_gram(clients.data_ptr(), stride, K, ptr(base), n, ptr(gram), ptr(ws), ws.numel() * ws.element_size(),
+                                    stream()), "nvq_fed_update_gram")
+
+
+def cluster_gram_kmeans(gram: torch.Tensor, K: int, C: int, init: Optional[torch.Tensor], max_iter: int, labels: torch.Tensor,
+                        counts: torch.Tensor, inertia: torch.Tensor, n_iter: torch.Tensor) -> None:
+    """Lloyd's algorithm from the K x K float64 Gram matrix alone (nvq_cluster_gram_kmeans); every output stays on the device"""
+    assert gram.dtype == torch.float64 and gram.numel() >= K * K and (init is None or (init.dtype == torch.int32 and init.numel() >= C))
+    assert labels.dtype == torch.int32 and labels.numel() >= K and counts.dtype == torch.int32 and counts.numel() >= C
+    assert inertia.dtype == torch.float64 and inertia.numel() >= 1 and n_iter.dtype == torch.int32 and n_iter.numel() >= 1
+    check(lib().nvq_cluster_gram_kmeans(ptr(gram), int(K), int(C), ptr(init), int(max_iter), ptr(labels), ptr(counts), ptr(inertia),
+                                        ptr(n_iter), stream()), "nvq_cluster_gram_kmeans")
+
+
+def fed_aggregate_clusters(clients: torch.Tensor, n: int, labels: torch.Tensor, C: int, bases: Optional[torch.Tensor],
+                           weights: torch.Tensor, sq: Optional[torch.Tensor], out: torch.Tensor, *, clip_norm: float = 0.0,
+                           server_lr: float = 1.0, noise_std: float = 0.0, seed: int = 0, offset: int = 0) -> None:
+    """out[c] = base_c + server_lr * sum_{k: labels[k] == c} c_k (clients[k] - base_c) + noise_std * z (nvq_fed_aggregate_clusters).
+    ``bases``: None (zeros), a vector (one shared base) or a [C][stride] matrix (one base per cluster; ``out`` may be it)."""
+    K, stride = _fed_rows(clients, n)
+    assert labels.dtype == torch.int32 and labels.numel() >= K and 1 <= C <= CLUSTER_MAX
+    assert weights.dtype == torch.float64 and weights.numel() >= K and (sq is None or (sq.dtype == torch.float64 and sq.numel() >= K))
+    assert out.shape[0] == C, "out: one row per cluster"
+    out_stride = _rows_stride(out, n, "out")
+    base_stride = 0
+    if bases is not None and bases.dim() == 2:
+        assert bases.shape[0] == C, "bases: one row per cluster"
+        base_stride = _rows_stride(bases, n, "bases")
+    elif bases is not None:
+        assert bases.dtype == torch.float32 and bases.numel() >= n
+    check(lib().nvq_fed_aggregate_clusters(clients.data_ptr(), stride, K, ptr(labels), int(C),
+                                           None if bases is None else bases.data_ptr(), base_stride, ptr(weights), ptr(sq),
+                                           float(clip_norm), float(server_lr), float(noise_std), int(seed), int(offset), n,
+                                           out.data_ptr(), out_stride, stream()), "nvq_fed_aggregate_clusters")

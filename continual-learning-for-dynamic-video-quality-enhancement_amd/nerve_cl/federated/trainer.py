@@ -5,7 +5,10 @@ learning rate and Gaussian noise, as one pass of csrc/federated.hip over a matri
 The reference's ``FederatedTrainer.train_round`` (reference nerve_cl/federated/server.py:141-193) selects clients and counts
 samples but neither trains nor aggregates; here a round trains every selected client on the model itself (its flat parameter
 buffer is reset to the global weights in place, so parameters are never re-homed and captured graphs stay valid) and averages
-on the device.  ``flwr`` is only the transport between processes and is not needed for any of this.
+on the device.  ``flwr`` is only the transport between processes and is not needed for any of this; it is still not implemented.
+
+With ``num_clusters > 1`` the trainer is clustered federated learning: one round clusters the clients by
+their updates (csrc/cluster.hip) and from then on every cluster has its own model, stepped by its own clients.
 """
 from __future__ import annotations
 
@@ -173,6 +176,16 @@ class FederatedTrainer:
     (``nerve_cl.optim.BucketAdamW``).  ``seed`` fixes the client selection and every noise stream; without it the selection is
     ``random.sample`` of the global generator, as in the reference.
 
+    ``num_clusters > 1`` (at most 8, ``num_clients`` at most 64, no ``update_clip``): rounds ``1 .. cluster_after`` are plain FedAvg;
+    round ``cluster_after + 1`` trains every client with data from the global model, clusters the rows by their updates
+    (``cluster_updates`` on the largest flat buffer; the labels are read to the host once and become ``client_cluster``) and forms
+    ``cluster_models``, one ``[C, n]`` device matrix per HIP-backed network, with one ``nvq_fed_aggregate_clusters`` each.  Later
+    rounds restore each selected client from its cluster's row, step all cluster models in place with one
+    ``nvq_fed_aggregate_clusters`` per network (a cluster with no selected client keeps its model; with ``update_noise`` every
+    cluster's row receives its draw) and leave the sample-weighted mean of the cluster models in the model itself.
+    There is no re-clustering: a client whose data arrives after the split round belongs to no cluster, and a round that selects it
+    raises ``ValueError``.  A selected client without samples is left out of its cluster's step.  ``load_cluster(c)`` copies a cluster's model into the network, ``load_mean()`` the weighted mean again; the round dict gains ``"clusters"``, the sizes.
+
     On the GPU the weights of every HIP-backed network inside ``model`` are one flat buffer: the clients' results are the rows of a
     persistent ``[clients_per_round, n]`` matrix and a round ends with one ``nvq_fed_delta_norms`` (only with ``update_clip``) and
     one ``nvq_fed_aggregate`` writing into ``flat_theta()``.  Everything else in the state dict (BatchNorm statistics, loose
@@ -183,7 +196,15 @@ class FederatedTrainer:
     def __init__(self, model: nn.Module, num_clients: int = 10, clients_per_round: int = 5, local_epochs: int = 5, *,
                  lr: float = 1e-4, batch_size: int = 16, loss=None, privacy: Optional[PrivacyConfig] = None,
                  update_clip: Optional[float] = None, update_noise: float = 0.0, server_lr: float = 1.0,
-                 optimizer_impl: str = "torch", seed: Optional[int] = None):
+                 optimizer_impl: str = "torch", seed: Optional[int] = None, num_clusters: int = 1, cluster_after: int = 0):
+        if not 1 <= num_clusters <= _nvq.CLUSTER_MAX:
+            raise ValueError(f"num_clusters: 1 .. {_nvq.CLUSTER_MAX}")
+        if cluster_after < 0:
+            raise ValueError(f"invalid cluster_after: {cluster_after}")
+        if num_clusters > 1 and num_clients > _nvq.FED_MAX_CLIENTS:
+            raise ValueError(f"num_clients: at most {_nvq.FED_MAX_CLIENTS} with clusters (the split round takes every client)")
+        if num_clusters > 1 and update_clip is not None:
+            raise NotImplementedError("update_clip with num_clusters > 1: per-cluster bases have no single update norm")
         if optimizer_impl not in ("torch", "bucket"):
             raise ValueError(f"optimizer_impl {optimizer_impl!r}: 'torch' or 'bucket'")
         if clients_per_round < 1 or clients_per_round > _nvq.FED_MAX_CLIENTS:
@@ -208,6 +229,10 @@ class FederatedTrainer:
         self.global_round = 0
         self.last_selected: List[int] = []
         self._plan = None
+        self.num_clusters, self.cluster_after = num_clusters, cluster_after
+        self.client_cluster: Dict[int, int] = {}              # client id -> cluster, filled by the split round
+        self.cluster_models: Optional[List[torch.Tensor]] = None   # per HIP-backed network a [C, n] matrix, after the split round
+        self.cluster_result = None                            # the split round's ClusterResult, on the clients' device
 
     def set_client_data(self, client_id: int, data: Tuple) -> None:
         """``data``: ``(inputs, targets)`` tensors with one sample per row"""
@@ -223,7 +248,7 @@ class FederatedTrainer:
         sd = model.state_dict()                       # detached tensors that share the parameters' and buffers' memory
         rest_f = [t for k, t in sd.items() if k not in flat_names and _is_float(t)]
         rest_i = [t for k, t in sd.items() if k not in flat_names and not _is_float(t)]
-        K = self.clients_per_round
+        K = self.clients_per_round if self.num_clusters == 1 else max(self.clients_per_round, self.num_clients)
         plan = {"dev": dev, "nets": nets, "pack": _Pack(rest_f), "ints": rest_i,
                 "rows": [torch.zeros(K, net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
                 "snaps": [torch.zeros(net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
@@ -306,10 +331,119 @@ class FederatedTrainer:
         for t, rows in zip(plan["ints"], plan["int_rows"]):
             t.copy_(_int_mean(rows[:K], w.to(rows.device)))
 
+    # ------------------------------------------------------------------ clustered rounds
+    def _cluster_weights(self) -> List[float]:
+        """the samples of the clients assigned to each cluster"""
+        w = [0.0] * self.num_clusters
+        for cid, c in self.client_cluster.items():
+            if cid in self.client_data:
+                w[c] += float(len(self.client_data[cid][0]))
+        return w
+
+    @torch.no_grad()
+    def _aggregate_clusters(self, plan, selected: List[int], counts: List[int], K: int, split: bool) -> None:
+        """the split round (``split``): cluster the K rows and form the cluster models from the global model; later rounds: step the
+        cluster models in place.  Then the model itself receives the sample-weighted mean of the cluster models."""
+        from nerve_cl.federated.clustering import aggregate_flat_clustered, cluster_updates
+        C, dev, w = self.num_clusters, plan["dev"], plan["weights"][:K]
+        nets, pack = plan["nets"], plan["pack"]
+        if split:
+            if K < C:
+                raise ValueError(f"the split round needs at least num_clusters = {C} clients with data, got {K}")
+            sizes = [net.flat_theta().numel() for net in nets]
+            big = max(range(len(nets)), key=lambda j: sizes[j]) if nets else -1
+            if big >= 0 and sizes[big] >= pack.total:
+                res = cluster_updates(plan["rows"][big][:K], C, base=plan["snaps"][big])
+            else:
+                res = cluster_updates(plan["rest_rows"][:K], C, base=plan["rest_snap"])
+            self.cluster_result = res
+            host = [int(v) for v in res.labels.tolist()]                # the one read-back of clustered training
+            self.client_cluster = dict(zip(selected, host))
+            self.cluster_models = [torch.zeros(C, n, dtype=torch.float32, device=dev) for n in sizes]
+            plan["rest_clusters"] = torch.zeros(C, plan["rest_rows"].shape[1], dtype=torch.float32, device=dev)
+            plan["int_clusters"] = [torch.zeros((C,) + tuple(t.shape), dtype=t.dtype, device=t.device) for t in plan["ints"]]
+            for ic, snap in zip(plan["int_clusters"], plan["int_snap"]):
+                ic.copy_(snap.expand_as(ic))
+            plan["labels"] = torch.zeros(plan["weights"].numel(), dtype=torch.int32, device=dev)
+            plan["cluster_w"] = torch.zeros(C, dtype=torch.float64, device=dev)
+        else:
+            host = [self.client_cluster[cid] for cid in selected]
+        # A client without samples has weight 0 and label -1 here: it belongs to no cluster in this pass, so a cluster whose
+        # selected members all lack samples is an empty cluster and keeps its row instead of dividing by W_c = 0.  The labels
+        # are written from the host like the sample counts: no copy, nothing read back.
+        labels = plan["labels"][:K]
+        for k, c in enumerate(host):
+            labels[k].fill_(c if counts[k] > 0 else -1)
+        base_off = (self.global_round * (len(nets) + 1)) * C
+        for j, (rows, snap, cm) in enumerate(zip(plan["rows"], plan["snaps"], self.cluster_models)):
+            aggregate_flat_clustered(rows[:K], w, labels, C, bases=snap if split else cm, server_lr=self.server_lr,
+                                     noise_std=self.update_noise, seed=self._noise_seed, offset=base_off + j * C, out=cm)
+        if pack.total:
+            rc = plan["rest_clusters"]
+            if nets:                                   # statistics and loose parameters: a plain step, as in _aggregate
+                aggregate_flat_clustered(plan["rest_rows"][:K], w, labels, C, bases=plan["rest_snap"] if split else rc, out=rc)
+            else:
+                aggregate_flat_clustered(plan["rest_rows"][:K], w, labels, C, bases=plan["rest_snap"] if split else rc,
+                                         server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed,
+                                         offset=base_off, out=rc)
+        for rows, ic in zip(plan["int_rows"], plan["int_clusters"]):
+            for c in range(C):                         # members with samples (known on the host): their weighted mean, by a mask
+                if sum(counts[k] for k in range(K) if host[k] == c) > 0:
+                    ic[c].copy_(_int_mean(rows[:K], (w * (labels == c)).to(rows.device)))
+        self.load_mean()                               # the model: the mean of the cluster models, weighted by their clients' samples
+
+    @torch.no_grad()
+    def load_cluster(self, c: int) -> None:
+        """copy cluster c's model into the network (for evaluation; the next round restores what it needs itself)"""
+        if self.cluster_models is None:
+            raise RuntimeError("load_cluster: the split round has not run yet")
+        if not 0 <= c < self.num_clusters:
+            raise ValueError(f"cluster {c} outside 0 .. {self.num_clusters - 1}")
+        plan = self._plan
+        for net, cm in zip(plan["nets"], self.cluster_models):
+            net.flat_theta().copy_(cm[c])
+        plan["pack"].unpack(plan["rest_clusters"][c])
+        for t, ic in zip(plan["ints"], plan["int_clusters"]):
+            t.copy_(ic[c])
+
+    @torch.no_grad()
+    def load_mean(self) -> None:
+        """put the sample-weighted mean of the cluster models back into the network (what a round leaves there)"""
+        if self.cluster_models is None:
+            raise RuntimeError("load_mean: the split round has not run yet")
+        plan, dev = self._plan, self._plan["dev"]
+        cw_host, cw = self._cluster_weights(), plan["cluster_w"]
+        for c, v in enumerate(cw_host):
+            cw[c].fill_(v)
+        for net, cm in zip(plan["nets"], self.cluster_models):
+            with _nvq.device_guard(dev):
+                _nvq.fed_aggregate(cm, cm.shape[1], None, cw, None, net.flat_theta())
+        if plan["pack"].total:
+            aggregate_flat(plan["rest_clusters"], cw if cw.is_cuda else cw_host, out=plan["rest_snap"])
+            plan["pack"].unpack(plan["rest_snap"])
+        for t, ic in zip(plan["ints"], plan["int_clusters"]):
+            t.copy_(_int_mean(ic, cw.to(ic.device)))
+
+    def cluster_sizes(self) -> List[int]:
+        """the number of clients assigned to each cluster (zeros before the split round)"""
+        sizes = [0] * self.num_clusters
+        for c in self.client_cluster.values():
+            sizes[c] += 1
+        return sizes
+
     def train_round_device(self) -> Dict[str, object]:
-        """One round; ``train_loss`` stays a 0-dim tensor on the device, so with client data on the device nothing is read back."""
+        """One round; ``train_loss`` stays a 0-dim tensor on the device, so with client data on the device nothing is read back
+        (the split round of a clustered trainer reads the labels once)."""
         available = list(self.client_data.keys())
-        selected = self._rng.sample(available, min(self.clients_per_round, len(available)))
+        clustered = self.num_clusters > 1 and self.global_round >= self.cluster_after
+        split = clustered and self.cluster_models is None
+        if split:                                      # every client with data, starting from the global model
+            selected = sorted(available)
+        else:
+            selected = self._rng.sample(available, min(self.clients_per_round, len(available)))
+        late = [c for c in selected if c not in self.client_cluster] if clustered and not split else []
+        if late:
+            raise ValueError(f"clients {late} received data after the split round and belong to no cluster: there is no re-clustering")
         counts = [len(self.client_data[c][0]) for c in selected]
         if selected and not sum(counts) > 0:
             raise ValueError("train_round: every selected client has no samples (all-zero aggregation weights)")
@@ -317,6 +451,8 @@ class FederatedTrainer:
             self._plan = self._build_plan()
         plan = self._plan
         K = len(selected)
+        if K > plan["weights"].numel():
+            raise ValueError(f"{K} clients with data, but num_clients = {self.num_clients}: the split round takes every client")
         seeds = [self._rng.getrandbits(62) for _ in selected] if self.seed is not None else [random.getrandbits(62) for _ in selected]
         loss_sum = torch.zeros((), dtype=torch.float32, device=plan["dev"])
         with torch.no_grad():
@@ -327,7 +463,10 @@ class FederatedTrainer:
                 s.copy_(t)
         for k, (cid, cnt) in enumerate(zip(selected, counts)):
             with torch.no_grad():
-                self._restore(plan)
+                if clustered and not split:
+                    self.load_cluster(self.client_cluster[cid])
+                else:
+                    self._restore(plan)
             loss_sum += self._train_client(plan, self.client_data[cid], seeds[k])
             with torch.no_grad():
                 for net, rows in zip(plan["nets"], plan["rows"]):
@@ -336,12 +475,17 @@ class FederatedTrainer:
                 for t, rows in zip(plan["ints"], plan["int_rows"]):
                     rows[k].copy_(t)
                 plan["weights"][k].fill_(float(cnt))
-        if K:
+        if K and clustered:
+            self._aggregate_clusters(plan, selected, counts, K, split)
+        elif K:
             self._aggregate(plan, K)
         self.global_round += 1
         self.last_selected = selected
         steps = max(sum(counts) * self.local_epochs, 1)
-        return {"round": self.global_round, "clients": K, "samples": sum(counts), "train_loss": loss_sum / steps}
+        out = {"round": self.global_round, "clients": K, "samples": sum(counts), "train_loss": loss_sum / steps}
+        if self.num_clusters > 1:
+            out["clusters"] = self.cluster_sizes()
+        return out
 
     def train_round(self) -> Dict[str, float]:
         """Execute one federated round: ``{"round", "clients", "samples"}`` as in the reference, plus ``train_loss``, the mean

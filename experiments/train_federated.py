@@ -7,7 +7,9 @@ shapes its tasks.  A round trains the selected clients one after the other on th
 to the global weights in place, and ends with one aggregation pass of csrc/federated.hip over the matrix of client weights
 (nerve_cl.federated.FederatedTrainer).  ``--dp-enabled`` wraps the local optimizer in the per-tensor
 clip-and-noise DPOptimizer (two launches on the gradient bucket); ``--update-clip`` / ``--update-noise`` / ``--server-lr`` act on
-the clients' whole updates in the aggregation pass.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
+the clients' whole updates in the aggregation pass.  ``--clusters C`` (with ``--cluster-after R`` plain rounds first) is clustered
+federated learning: one round clusters the clients by their updates (csrc/cluster.hip), every cluster then
+has its own model; the sizes are printed after the split and every cluster's evaluation loss at the end.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
 """
 import argparse
 from pathlib import Path
@@ -43,6 +45,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--update-noise", type=float, default=0.0, metavar="S",
                     help="standard deviation of the Gaussian noise added to the aggregated weights")
     ap.add_argument("--server-lr", type=float, default=1.0, help="the aggregated update is scaled by this before it is applied")
+    ap.add_argument("--clusters", type=int, default=1, metavar="C",
+                    help="cluster the clients by their updates into C groups with one model each (default 1: plain FedAvg)")
+    ap.add_argument("--cluster-after", type=int, default=0, metavar="R", help="plain FedAvg rounds before the round that clusters")
     ap.add_argument("--samples", type=int, default=100, help="clips per client (the reference's 100)")
     ap.add_argument("--features", type=int, default=64)
     ap.add_argument("--blocks", type=int, default=8)
@@ -73,13 +78,34 @@ def main() -> None:
     trainer = FederatedTrainer(_ClipAdapter(engine), num_clients=args.num_clients, clients_per_round=args.clients_per_round,
                                local_epochs=args.local_epochs, loss=ops.MSELoss(), privacy=privacy, update_clip=args.update_clip,
                                update_noise=args.update_noise, server_lr=args.server_lr, optimizer_impl=args.optimizer_impl,
-                               seed=args.seed)
+                               seed=args.seed, num_clusters=args.clusters, cluster_after=args.cluster_after)
     for cid in range(args.num_clients):
         lr, hr = create_client_data(cid, args.samples)
         trainer.set_client_data(cid, (lr.to(device), hr.to(device)))          # on the device: a round copies nothing from the host
     for _ in range(args.num_rounds):
         m = trainer.train_round()
         print(f"Round {m['round']}: {m['clients']} clients, {m['samples']} samples, loss {m['train_loss']:.4f}")
+        if args.clusters > 1 and m["round"] == args.cluster_after + 1:
+            print(f"  clusters after the split: sizes {m['clusters']}, clients {trainer.client_cluster}")
+    if trainer.cluster_models is not None:
+        model, loss = trainer.model, ops.MSELoss()
+        for c in range(args.clusters):
+            members = [cid for cid, k in trainer.client_cluster.items() if k == c]
+            if not members:
+                print(f"Cluster {c}: empty")
+                continue
+            trainer.load_cluster(c)
+            model.eval()
+            total, seen = 0.0, 0
+            with torch.no_grad():
+                for cid in members:
+                    xs, ys = trainer.client_data[cid]
+                    for i in range(0, len(xs), trainer.batch_size):
+                        x, y = xs[i:i + trainer.batch_size], ys[i:i + trainer.batch_size]
+                        total += float(loss(model(x), y)) * len(x)
+                        seen += len(x)
+            print(f"Cluster {c}: {len(members)} clients, eval loss {total / max(seen, 1):.4f}")
+        trainer.load_mean()
     Path("checkpoints").mkdir(exist_ok=True)
     torch.save(engine.state_dict(), "checkpoints/federated_model.pt")
     print("\nFederated training complete!")

@@ -974,6 +974,38 @@ int nvq_dp_segment_norms(const float* g, const long* seg_off, const long* seg_nu
 int nvq_dp_clip_noise(float* g, const long* seg_off, const long* seg_numel, int S, const int* chunks, int n_chunks,
                       const double* sq, float max_norm, float noise_scale, long seed, long offset, void* stream);
 
+/* ------------------------------------------------------------------ clustered federated learning
+ * (csrc/cluster.hip).  The same client matrix and the same rule as above: no atomics, size-only grids,
+ * sums in double in a fixed order, the same bits on every call and at every pointer alignment.
+ *
+ * nvq_fed_update_gram: gram[i * K + j] = sum_t (x_i[t] - base[t]) (x_j[t] - base[t]) as K * K device doubles, 1 <= K <= 64, base
+ * == NULL: zeros.  The differences are widened to double before the product; the partial Gram of a block is formed on
+ * v_mfma_f64_16x16x4_f64 for the 16 x 16 tiles (i <= j) only, written to the workspace (nvq_fed_gram_workspace_bytes, 8-byte
+ * aligned; NVQ_EWORKSPACE when short) and a finishing launch adds the blocks in order and mirrors: gram is symmetric bit for bit.
+ *
+ * nvq_cluster_gram_kmeans: Lloyd's algorithm on the rows behind a Gram matrix, from the Gram alone, one workgroup, 1 <= C <= 8,
+ * C <= K.  d(k, c) = G_kk - (2 / |S_c|) sum_{j in S_c} G_kj + (1 / |S_c|^2) sum_{i, j in S_c} G_ij, +inf for an empty cluster (it
+ * stays empty).  init: C device ints, distinct row indices (one outside [0, K) gives an empty cluster), or NULL: farthest-first,
+ * the first seed the row with the largest G_kk, each next one the row that maximises its minimum distance to the seeds so far,
+ * ties to the lowest index.  Rows go to the nearest seed, then up to max_iter sweeps reassign every row to its nearest centroid
+ * (ties to the lowest cluster) until no label changes; n_iter = the sweeps made.  labels: K ints, counts: C ints, inertia: one
+ * double, the sum of d(k, labels[k]) for the final labels, n_iter: one int, all on the device.
+ *
+ * nvq_fed_aggregate_clusters: labels = K device ints; for c < C, with S_c = {k : labels[k] == c}, W_c = sum of weights over S_c in
+ * ascending k and c_k = weights[k] / W_c * s_k (s_k from sq and clip_norm as in nvq_fed_aggregate): out[c * out_stride + i] =
+ * the value nvq_fed_aggregate gives for the rows of S_c in ascending k with base = bases + c * base_stride and the noise stream
+ * (seed, offset + c).  base_stride == 0: one shared base; bases == NULL: zeros.  sq != NULL needs base_stride == 0.  An empty
+ * cluster's row is its base (plus noise); a label outside [0, C) leaves the client out.  out may be bases when out_stride ==
+ * base_stride (or C == 1); out must not alias clients.  Members whose weights are all zero give NaN in that row. */
+size_t nvq_fed_gram_workspace_bytes(int K, long n);
+int nvq_fed_update_gram(const float* clients, long stride, int K, const float* base, long n, double* gram, float* workspace,
+                        size_t workspace_bytes, void* stream);
+int nvq_cluster_gram_kmeans(const double* gram, int K, int C, const int* init, int max_iter, int* labels, int* counts,
+                            double* inertia, int* n_iter, void* stream);
+int nvq_fed_aggregate_clusters(const float* clients, long stride, int K, const int* labels, int C, const float* bases,
+                               long base_stride, const double* weights, const double* sq, float clip_norm, float server_lr,
+                               float noise_std, long seed, long offset, long n, float* out, long out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
