@@ -8,7 +8,9 @@ from nerve_cl.models import (FrameRecoveryNet, SuperResolutionNet, LightweightSu
 from nerve_cl.continual import EpisodicMemory, EWC, MAML
 from nerve_cl.drift import DriftDetector, DriftResult, ModelDriftMonitor
 from nerve_cl.federated import FederatedTrainer
+from nerve_cl.abr import StreamingEnv, VecStreamingEnv, PPOAgent, ABRConfig
 
 __all__ = ["FrameRecoveryNet", "SuperResolutionNet", "LightweightSuperResolution", "EnhancementEngine",
            "AdaptiveEnhancementEngine", "EnhancementConfig", "EpisodicMemory", "EWC", "MAML",
-           "DriftDetector", "DriftResult", "ModelDriftMonitor", "FederatedTrainer"]
+           "DriftDetector", "DriftResult", "ModelDriftMonitor", "FederatedTrainer",
+           "StreamingEnv", "VecStreamingEnv", "PPOAgent", "ABRConfig"]

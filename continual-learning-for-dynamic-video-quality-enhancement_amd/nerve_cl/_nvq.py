@@ -253,6 +253,15 @@ SIGNATURES = {
     "nvq_fed_update_gram": (ci, [vp, cl, ci, vp, cl, vp, vp, sz, vp]),
     "nvq_cluster_gram_kmeans": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
     "nvq_fed_aggregate_clusters": (ci, [vp, cl, ci, vp, ci, vp, cl, vp, vp, cf, cf, cf, cl, cl, cl, vp, cl, vp]),
+    # ABR agent: vectorised environment, fused act, GAE, PPO loss (csrc/abr.hip)
+    "nvq_abr_env_reset": (ci, [vp, vp, vp, vp, ci, ci, cl, ci, vp]),
+    "nvq_abr_env_step": (ci, [vp, vp, vp, _IP, ci, ci, ci, vp, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "nvq_abr_act_supported": (ci, [ci, _IP]),
+    "nvq_abr_act": (ci, [vp, ci, ci, vp, _IP, vp, cl, ci, vp, vp, vp, vp, vp]),
+    "nvq_abr_gae": (ci, [vp, vp, vp, vp, cf, cf, ci, ci, vp, vp, vp]),
+    "nvq_abr_adv_stats": (ci, [vp, cl, vp, vp]),
+    "nvq_ppo_loss_workspace_bytes": (sz, [cl]),
+    "nvq_ppo_loss": (ci, [vp, vp, vp, vp, vp, vp, cl, _IP, ci, cf, cf, cf, vp, vp, vp, sz, vp]),
 }
 
 
@@ -1612,3 +1621,117 @@ def fed_aggregate_clusters(clients: torch.Tensor, n: int, labels: torch.Tensor, 
                                            None if bases is None else bases.data_ptr(), base_stride, ptr(weights), ptr(sq),
                                            float(clip_norm), float(server_lr), float(noise_std), int(seed), int(offset), n,
                                            out.data_ptr(), out_stride, stream()), "nvq_fed_aggregate_clusters")
+
+
+# ----------------------------------------------------------------------------- ABR agent (csrc/abr.hip)
+ABR_MAX_LAYERS, ABR_MAX_HEADS = 3, 4
+
+
+def abr_env_reset(state: torch.Tensor, counters: torch.Tensor, obs: torch.Tensor, params: torch.Tensor, nq: int, max_steps: int,
+                  seed: int) -> None:
+    N = state.shape[0]
+    assert state.dtype == torch.float64 and tuple(state.shape) == (N, 8) and counters.dtype == torch.int64 and counters.numel() == N
+    assert obs.dtype == torch.float32 and tuple(obs.shape) == (N, 7) and params.dtype == torch.float64 and params.numel() == 2
+    check(lib().nvq_abr_env_reset(ptr(state), ptr(counters), ptr(obs), ptr(params), int(nq), int(max_steps), int(seed), N, stream()),
+          "nvq_abr_env_reset")
+
+
+def abr_env_step(state: torch.Tensor, counters: torch.Tensor, actions: torch.Tensor, bitrates: Sequence[int], enh_levels: int,
+                 max_steps: int, params: torch.Tensor, seed: int, obs: torch.Tensor, reward: torch.Tensor, terminated: torch.Tensor,
+                 truncated: torch.Tensor, info: Optional[torch.Tensor] = None, reward_f32: Optional[torch.Tensor] = None,
+                 done_f32: Optional[torch.Tensor] = None, finished: Optional[torch.Tensor] = None) -> None:
+    """One step of every environment with the same-step reset (nvq_abr_env_step); every tensor is written in place"""
+    N = state.shape[0]
+    assert state.dtype == torch.float64 and tuple(state.shape) == (N, 8) and counters.dtype == torch.int64 and counters.numel() == N
+    assert actions.dtype == torch.int32 and tuple(actions.shape) == (N, 2), "actions: (N, 2) int32"
+    assert obs.dtype == torch.float32 and tuple(obs.shape) == (N, 7) and params.dtype == torch.float64 and params.numel() == 2
+    assert reward.dtype == torch.float64 and reward.numel() == N
+    for f in (terminated, truncated):
+        assert f.dtype in (torch.uint8, torch.bool) and f.numel() == N
+    assert info is None or (info.dtype == torch.float64 and tuple(info.shape) == (5, N))
+    for f in (reward_f32, done_f32):
+        assert f is None or (f.dtype == torch.float32 and f.numel() == N)
+    assert finished is None or (finished.dtype == torch.float64 and tuple(finished.shape) == (N, 2))
+    check(lib().nvq_abr_env_step(ptr(state), ptr(counters), ptr(actions), int_array(list(bitrates)), len(bitrates), int(enh_levels),
+                                 int(max_steps), ptr(params), int(seed), N, ptr(obs), ptr(reward), ptr(terminated), ptr(truncated),
+                                 ptr(info), ptr(reward_f32), ptr(done_f32), ptr(finished), stream()), "nvq_abr_env_step")
+
+
+def abr_dims(hidden: Sequence[int], heads: Sequence[int]):
+    """the dims_host table of nvq_abr_act, or None when the counts alone rule the network out"""
+    if not 1 <= len(hidden) <= ABR_MAX_LAYERS or not 1 <= len(heads) <= ABR_MAX_HEADS:
+        return None
+    return int_array([len(hidden)] + list(hidden) + [0] * (ABR_MAX_LAYERS - len(hidden))
+                     + [len(heads)] + list(heads) + [0] * (ABR_MAX_HEADS - len(heads)))
+
+
+def abr_act_supported(obs_dim: int, hidden: Sequence[int], heads: Sequence[int]) -> bool:
+    dims = abr_dims(hidden, heads)
+    return dims is not None and bool(lib().nvq_abr_act_supported(int(obs_dim), dims))
+
+
+def abr_act(obs: torch.Tensor, layers: "Sequence[tuple[torch.Tensor, torch.Tensor]]",
+            heads: "Sequence[tuple[torch.Tensor, torch.Tensor]]", value_head: "tuple[torch.Tensor, torch.Tensor]",
+            counters: Optional[torch.Tensor], seed: int, deterministic: bool, actions: torch.Tensor, log_prob: torch.Tensor,
+            value: torch.Tensor, head_out: Optional[torch.Tensor] = None) -> None:
+    """layers / heads / value_head: (weight, bias) pairs as nn.Linear holds them (nvq_abr_act reads them in place)"""
+    B, obs_dim = obs.shape
+    width = obs_dim                           # the kernel strides every weight by the width before it: the shapes must chain
+    for group, chained in ((layers, True), (list(heads) + [value_head], False)):
+        for w, b in group:
+            assert w.dtype == torch.float32 and b.dtype == torch.float32, "nvq_abr_act: fp32 weights and biases"
+            assert w.device == obs.device and b.device == obs.device, "nvq_abr_act: weights on the observations' device"
+            assert w.dim() == 2 and w.shape[1] == width and tuple(b.shape) == (w.shape[0],), \
+                f"nvq_abr_act: a weight of shape {tuple(w.shape)} after a width of {width}"
+            if chained:
+                width = w.shape[0]
+    assert value_head[0].shape[0] == 1, "nvq_abr_act: the value head has one output"
+    dims = abr_dims([w.shape[0] for w, _ in layers], [w.shape[0] for w, _ in heads])
+    if dims is None:
+        raise RuntimeError("nvq_abr_act: unsupported network (1 to 3 hidden layers, 1 to 4 heads)")
+    table = (vp * 16)()
+    for i, (w, b) in enumerate(layers):
+        table[2 * i], table[2 * i + 1] = ptr(w), ptr(b)
+    for i, (w, b) in enumerate(heads):
+        table[6 + 2 * i], table[7 + 2 * i] = ptr(w), ptr(b)
+    table[14], table[15] = ptr(value_head[0]), ptr(value_head[1])
+    P = sum(w.shape[0] for w, _ in heads) + 1
+    assert obs.dtype == torch.float32 and actions.dtype == torch.int32 and tuple(actions.shape) == (B, len(heads))
+    assert log_prob.dtype == torch.float32 and log_prob.numel() == B and value.dtype == torch.float32 and value.numel() == B
+    assert counters is None or (counters.dtype == torch.int64 and counters.numel() == B)
+    assert head_out is None or (head_out.dtype == torch.float32 and tuple(head_out.shape) == (B, P))
+    check(lib().nvq_abr_act(ptr(obs), B, obs_dim, C.cast(table, vp), dims, ptr(counters), int(seed), int(deterministic), ptr(actions),
+                            ptr(log_prob), ptr(value), ptr(head_out), stream()), "nvq_abr_act")
+
+
+def abr_gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: torch.Tensor, gamma: float, lam: float,
+            returns: torch.Tensor, advantages: torch.Tensor) -> None:
+    T, N = rewards.shape
+    for t in (rewards, values, dones, returns, advantages):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (T, N)
+    assert last_values.dtype == torch.float32 and last_values.numel() == N
+    check(lib().nvq_abr_gae(ptr(rewards), ptr(values), ptr(dones), ptr(last_values), float(gamma), float(lam), T, N, ptr(returns),
+                            ptr(advantages), stream()), "nvq_abr_gae")
+
+
+def abr_adv_stats(adv: torch.Tensor, stats: torch.Tensor) -> None:
+    assert adv.dtype == torch.float32 and stats.dtype == torch.float64 and stats.numel() == 2
+    check(lib().nvq_abr_adv_stats(ptr(adv), adv.numel(), ptr(stats), stream()), "nvq_abr_adv_stats")
+
+
+def ppo_loss(head_outputs: torch.Tensor, actions: torch.Tensor, old_log_probs: torch.Tensor, advantages: torch.Tensor,
+             adv_stats: torch.Tensor, returns: torch.Tensor, heads: Sequence[int], clip_ratio: float, value_coef: float,
+             entropy_coef: float, grad: torch.Tensor, out: torch.Tensor) -> None:
+    """out (6 doubles) = loss and statistics, grad = d loss / d head_outputs (nvq_ppo_loss); two launches"""
+    M, P = head_outputs.shape
+    assert P == sum(heads) + 1, "head_outputs: the heads' logits, then the value"
+    assert head_outputs.dtype == torch.float32 and grad.dtype == torch.float32 and grad.shape == head_outputs.shape
+    assert actions.dtype == torch.int32 and tuple(actions.shape) == (M, len(heads))
+    for t in (old_log_probs, advantages, returns):
+        assert t.dtype == torch.float32 and t.numel() == M
+    assert adv_stats.dtype == torch.float64 and adv_stats.numel() == 2 and out.dtype == torch.float64 and out.numel() == 6
+    nbytes = int(lib().nvq_ppo_loss_workspace_bytes(M))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=head_outputs.device)
+    check(lib().nvq_ppo_loss(ptr(head_outputs), ptr(actions), ptr(old_log_probs), ptr(advantages), ptr(adv_stats), ptr(returns), M,
+                             int_array(list(heads)), len(heads), float(clip_ratio), float(value_coef), float(entropy_coef), ptr(grad),
+                             ptr(out), ptr(ws), nbytes, stream()), "nvq_ppo_loss")

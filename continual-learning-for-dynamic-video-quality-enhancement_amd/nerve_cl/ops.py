@@ -16,6 +16,9 @@ needs), not one value per element.
 student output) and ``cosine_feature_loss`` / ``CosineFeatureLoss`` (feature distillation on ``return_intermediate`` tensors)
 are csrc/distill.hip; their gradient is with respect to the student only.
 
+``ppo_loss`` (csrc/abr.hip) is the clipped-surrogate PPO loss of the ABR agent over the actor-critic's head
+outputs: one pass that also writes the gradient, one autograd node; CPU tensors take a float64 torch composition.
+
 ``clip_grad_norm_`` is not a loss: global 2-norm gradient clipping on the flat gradient buckets without a host read
 (csrc/bucket_ops.hip).
 """
@@ -525,3 +528,115 @@ def clip_grad_norm_(module_or_parameters, max_norm: float, refresh: bool = False
             if dst is not None:
                 dst.copy_(g.view(dst.shape))
     return norm
+
+
+# ------------------------------------------------------------------------------------------------ PPO loss (section 26)
+PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction")
+
+
+def ppo_loss_composition(x: torch.Tensor, heads: Sequence[int], actions: torch.Tensor, old_log_probs: torch.Tensor,
+                         advantages: torch.Tensor, returns: torch.Tensor, clip_ratio: float, value_coef: float, entropy_coef: float,
+                         adv_stats: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.float64):
+    """The rule of ``ppo_loss`` as a differentiable torch composition in ``dtype`` on x's device -> (loss, stats (6,)).  ``x``: the
+    (M, P) head outputs, or the forward's tuple (logits_0, .., value (M, 1)); with the tuple every head's gradient reaches its
+    Linear as a contiguous tensor, as in a loop written on the forward's outputs directly."""
+    if isinstance(x, torch.Tensor):
+        x = x.to(dtype)
+        offs = [sum(heads[:j]) for j in range(len(heads) + 1)]
+        parts = [x[:, offs[j]:offs[j + 1]] for j in range(len(heads))] + [x[:, offs[-1]:offs[-1] + 1]]
+    else:
+        parts = [p.to(dtype) for p in x]
+    adv, old, ret = advantages.reshape(-1).to(dtype), old_log_probs.reshape(-1).to(dtype), returns.reshape(-1).to(dtype)
+    mean, std = (adv.mean(), adv.std()) if adv_stats is None else (adv_stats[0].to(dtype), adv_stats[1].to(dtype))
+    adv = (adv - mean) / (std + 1e-8)
+    a = actions.long()
+    new, ent = 0, 0
+    for j, logits in enumerate(parts[:-1]):
+        # the operations of torch.distributions.Categorical(logits=), so that fp32 results are those of a loop written with it
+        lp = logits - logits.logsumexp(dim=-1, keepdim=True)
+        new = new + lp.gather(1, a[:, j:j + 1])[:, 0]
+        ent = ent + (-(lp * torch.softmax(lp, dim=-1)).sum(-1)).mean()
+    value = parts[-1].squeeze(-1)
+    log_ratio = new - old
+    ratio = log_ratio.exp()
+    pol = -torch.min(ratio * adv, torch.clamp(ratio, 1 - clip_ratio, 1 + clip_ratio) * adv).mean()
+    val = ((value - ret) ** 2).mean()
+    loss = pol + value_coef * val - entropy_coef * ent
+    with torch.no_grad():
+        stats = torch.stack([loss, pol, val, ent, ((ratio - 1) - log_ratio).mean(),
+                             ((ratio - 1).abs() > clip_ratio).to(dtype).mean()]).detach()
+    return loss, stats
+
+
+class _PPOLossFn(torch.autograd.Function):
+    """nvq_ppo_loss: the forward writes the loss, the statistics and the gradient; the backward scales the stored gradient.  The head
+    outputs arrive as one (M, P) tensor or as the forward's tuple; the tuple's gradients go back as contiguous tensors, so the
+    Linear layers behind them run their GEMMs on dense operands."""
+
+    @staticmethod
+    def forward(ctx, actions, old_log_probs, advantages, returns, adv_stats, heads, clip_ratio, value_coef, entropy_coef, *parts):
+        xa = (parts[0] if len(parts) == 1 else torch.cat([p.detach() for p in parts], dim=-1)).detach().float().contiguous()
+        M = xa.shape[0]
+        f = lambda t: t.detach().reshape(-1).float().contiguous()      # noqa: E731
+        adv = f(advantages)
+        grad = torch.empty_like(xa)
+        out = torch.empty(6, dtype=torch.float64, device=xa.device)
+        with _nvq.device_guard(xa.device):
+            if adv_stats is None:
+                adv_stats = torch.empty(2, dtype=torch.float64, device=xa.device)
+                _nvq.abr_adv_stats(adv, adv_stats)
+            _nvq.ppo_loss(xa, actions.detach().reshape(M, -1).int().contiguous(), f(old_log_probs), adv,
+                          adv_stats.detach().double().contiguous(), f(returns), heads, clip_ratio, value_coef, entropy_coef, grad, out)
+        ctx.save_for_backward(grad)
+        ctx.meta = [(p.shape[-1], p.dtype) for p in parts]
+        loss, stats = out[0], out
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, go, _gs):
+        (grad,) = ctx.saved_tensors
+        g = grad * go.detach().to(grad.dtype)
+        if len(ctx.meta) == 1:
+            outs = [g.to(ctx.meta[0][1])]
+        else:
+            outs = [piece.contiguous().to(dt) for piece, (_, dt) in zip(torch.split(g, [w for w, _ in ctx.meta], dim=-1), ctx.meta)]
+        return (None,) * 9 + tuple(outs)
+
+
+def ppo_loss(head_outputs, actions: torch.Tensor, old_log_probs: torch.Tensor, advantages: torch.Tensor, returns: torch.Tensor,
+             clip_ratio: float, value_coef: float, entropy_coef: float, adv_stats: Optional[torch.Tensor] = None,
+             heads: Optional[Sequence[int]] = None, return_stats: bool = False):
+    """The PPO loss over M samples: policy + value_coef * value - entropy_coef * entropy with
+    policy = -mean(min(r A, clamp(r, 1 - clip, 1 + clip) A)), r = exp(new log-prob - old), A = (adv - mean) / (std + 1e-8),
+    value = mean((v - returns)^2), entropy = the sum over the heads of the mean entropy.
+
+    ``head_outputs``: what the actor-critic's forward returns, a sequence (logits_0 (M, n_0), .., value (M, 1)), or one (M, P)
+    tensor of the same columns with ``heads=(n_0, ..)``.  ``actions`` (M, heads) integers; ``advantages`` raw: ``adv_stats`` = a
+    2-element float64 tensor {mean, unbiased std} (``None``: formed here, on the device by one reduction launch).
+    On HIP tensors this is one autograd node (nvq_ppo_loss: the loss, the statistics and the gradient from one pass, per sample
+    in double, bit-reproducible); its backward scales the stored gradient by ``grad_output``.  CPU tensors take the float64 torch
+    composition.  The loss is a float64 scalar; ``return_stats``: also a (6,) float64 tensor in the order of ``PPO_STATS``."""
+    if isinstance(head_outputs, torch.Tensor):
+        if heads is None:
+            raise ValueError("ppo_loss: a single head_outputs tensor needs heads=(n_0, ...)")
+        parts = (head_outputs,)
+    else:
+        parts = tuple(head_outputs)
+        if heads is None:
+            heads = [int(t.shape[-1]) for t in parts[:-1]]
+    heads = tuple(int(n) for n in heads)
+    M, P = parts[0].shape[0], sum(int(t.shape[-1]) for t in parts)
+    if any(t.dim() != 2 or t.shape[0] != M for t in parts) or P != sum(heads) + 1 or M < 1 or \
+            (len(parts) > 1 and [int(t.shape[-1]) for t in parts] != list(heads) + [1]):
+        raise RuntimeError(f"ppo_loss: head outputs {[tuple(t.shape) for t in parts]} are not (M, n_j) for heads {heads} and (M, 1)")
+    if actions.numel() != M * len(heads) or old_log_probs.numel() != M or advantages.numel() != M or returns.numel() != M:
+        raise RuntimeError("ppo_loss: actions / old_log_probs / advantages / returns do not hold M samples")
+    if not parts[0].is_cuda:
+        loss, stats = ppo_loss_composition(parts[0] if len(parts) == 1 else parts, heads, actions.reshape(M, -1), old_log_probs,
+                                           advantages, returns, clip_ratio, value_coef, entropy_coef, adv_stats)
+    else:
+        loss, stats = _PPOLossFn.apply(actions, old_log_probs, advantages, returns, adv_stats, heads, float(clip_ratio),
+                                       float(value_coef), float(entropy_coef), *parts)
+    return (loss, stats) if return_stats else loss

@@ -1006,6 +1006,64 @@ int nvq_fed_aggregate_clusters(const float* clients, long stride, int K, const i
                                long base_stride, const double* weights, const double* sq, float clip_norm, float server_lr,
                                float noise_std, long seed, long offset, long n, float* out, long out_stride, void* stream);
 
+/* ------------------------------------------------------------------ ABR agent: vectorised streaming environment, fused act,
+ * GAE and the PPO loss (csrc/abr.hip).  No atomics; sums in double in a fixed order; plain vector stores.
+ *
+ * Draws: Philox4x32-10 as in "Noise" above with key = {seed low, seed high} and counter = {e low, e high, t low,
+ * (t high & 0xFFFFFF) | stream << 24} for environment e and its draw counter t = counters[e] (t < 2^56); the words r0..r3 give
+ * u_j = ((r_j >> 8) + 0.5) 2^-24 in double.  Stream 0 is the environment: bandwidth factor 0.8 + 0.4 u0, content complexity of
+ * the returned observation 0.3 + 0.5 u1 and, when the step ends the episode (and in nvq_abr_env_reset), the new bandwidth
+ * 2 + 13 u2 and the reset observation's complexity 0.3 + 0.5 u3.  Stream 1 is the policy: head j samples with u_j.  Both
+ * environment calls add one to every counters[e].
+ *
+ * state: N rows of 8 doubles {buffer level, bandwidth, battery, last quality, last VMAF, step count, total rebuffer, episode
+ * return}; counters: N longs; params: 2 device doubles {segment duration, buffer size}; obs: N rows of 7 floats.  One thread per
+ * environment, float64 in the order of operations of the single-environment step, without contraction.  An action outside its
+ * range is clamped into it.  An environment whose step ends its episode (step count >= max_steps: terminated; battery <= 0:
+ * truncated) is reset in the same call: reward, flags and info are those of the finished step, obs is the reset observation.
+ * info (optional): 5 rows of N doubles {vmaf, rebuffer, bandwidth, buffer, episode return}.  reward_f32 / done_f32 (optional): the
+ * reward and (terminated | truncated) as floats, e.g. a row of a rollout.  finished (optional): N pairs {sum of finished episode
+ * returns, finished episodes}, added to by the environment's own thread.  1 <= nq <= 16 ladder entries (kbps), enh_levels >= 2.
+ *
+ * nvq_abr_act: the actor-critic forward and sampling in one launch.  params_host: 16 device pointers {W1, b1, W2, b2, W3, b3,
+ * Wh0, bh0, .., Wh3, bh3, Wv, bv}, nn.Linear layouts ([out][in] weights, 16-byte aligned), unused entries NULL; dims_host: 9 ints
+ * {hidden layers, w1, w2, w3, heads, n0, n1, n2, n3}.  Supported (nvq_abr_act_supported; anything else is NVQ_EINVAL): obs_dim <=
+ * 32, 1 to 3 hidden layers of a width that is a multiple of 32 in [32, 512], 1 to 4 heads, at most 32 head outputs with the
+ * value; any B >= 1.  The linears run on v_mfma_f32_16x16x4_f32; each head's log-softmax is x - (m + logf(sum expf(x - m))).
+ * Sampling: the CDF of expf(log-softmax) is added in index order in fp32, the action is the first k with u < cdf_k, else the last;
+ * the draw of row i is (e = i, t = counters[i]) on stream 1.  deterministic != 0 or counters == NULL: the first index of the
+ * maximum.  actions: B rows of `heads` ints; log_prob: the sum over the heads of the log-probability of the action taken;
+ * head_out (optional): B rows of the P = n0 + .. + 1 raw head outputs, the value last.
+ *
+ * nvq_abr_gae: rewards / values / dones / returns / advantages are [T][N] floats, one thread per environment from t = T - 1 down:
+ * delta = r + gamma v_next (1 - done) - v, gae = delta + gamma lam (1 - done) gae, returns = gae + v, v_next of the last step =
+ * last_values.  nvq_abr_adv_stats: stats = {mean, unbiased standard deviation} of M floats as 2 device doubles, one workgroup.
+ *
+ * nvq_ppo_loss: head_outputs / grad are M rows of P floats (the heads' logits, then the value), actions M rows of n_heads ints.
+ * Per sample, in double: A = (adv - stats[0]) / (stats[1] + 1e-8), ratio = exp(new log-prob - old), policy term
+ * -min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A), value term (v - return)^2, the heads' entropies.  out = 6 device doubles
+ * {loss, policy loss, value loss, entropy, approximate KL = mean((ratio - 1) - log ratio), clip fraction = mean(|ratio - 1| >
+ * clip)} with loss = policy + value_coef * value - entropy_coef * entropy, means over M; grad = d loss / d head_outputs rounded
+ * once to fp32.  Block partials go to the workspace (nvq_ppo_loss_workspace_bytes, 8-byte aligned; NVQ_EWORKSPACE when short)
+ * and a finishing launch adds them in block order.  P <= 64. */
+int nvq_abr_env_reset(double* state, long* counters, float* obs, const double* params, int nq, int max_steps, long seed, int N,
+                      void* stream);
+int nvq_abr_env_step(double* state, long* counters, const int* actions, const int* bitrates_host, int nq, int enh_levels,
+                     int max_steps, const double* params, long seed, int N, float* obs, double* reward,
+                     unsigned char* terminated, unsigned char* truncated, double* info, float* reward_f32, float* done_f32,
+                     double* finished, void* stream);
+int nvq_abr_act_supported(int obs_dim, const int* dims_host);
+int nvq_abr_act(const float* obs, int B, int obs_dim, const void* params_host, const int* dims_host, const long* counters,
+                long seed, int deterministic, int* actions, float* log_prob, float* value, float* head_out, void* stream);
+int nvq_abr_gae(const float* rewards, const float* values, const float* dones, const float* last_values, float gamma, float lam,
+                int T, int N, float* returns, float* advantages, void* stream);
+int nvq_abr_adv_stats(const float* adv, long M, double* stats, void* stream);
+size_t nvq_ppo_loss_workspace_bytes(long M);
+int nvq_ppo_loss(const float* head_outputs, const int* actions, const float* old_log_probs, const float* advantages,
+                 const double* adv_stats, const float* returns, long M, const int* heads_host, int n_heads, float clip_ratio,
+                 float value_coef, float entropy_coef, float* grad, double* out, double* workspace, size_t workspace_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
