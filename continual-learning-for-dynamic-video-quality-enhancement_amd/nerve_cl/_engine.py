@@ -311,6 +311,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
                    P["temporal_aggregator.attention.2.bias"], Sl(a2), 3, relu=True, math=math)
     K.conv_forward(Sl(a2), packs.get("temporal_aggregator.attention.4.weight", False, F),
                    P["temporal_aggregator.attention.4.bias"], Sl(logits, T), 3, cout_store=g.Tp, math=math)
+    _capture("logits", lambda: logits)
     nblk = K.tsum_blocks(H, W)
     # bf16 activation mode: the aggregated features (the CBAM's input; one write, four reads per step) and the two gradients around
     # the CBAM backward are stored as bf16 like the tensors on either side of them; the pooled sums (GAP, channel mean / max,
@@ -568,6 +569,7 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     # ---- upsampler tail
     du = _new(dev, B, H, W, g.Up)
     K.shuffle_clamp_backward(dout, sv.passmask, g.s, du)
+    _capture("du", lambda: du)
     _wgrad(Sl(sv.fused), F, Sl(du, g.U), G, "upsampler.conv.weight", "upsampler.conv.bias", wq, 3, math=math)
     # Frozen layers: the stages below run while something upstream of them, or one of their own parameters, needs a gradient
     # (plan.run); past the last such stage the pass ends.
@@ -614,6 +616,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
     dg = _new(dev, B, H, W, F, dtype=act_dtype)
     K.conv_forward(Sl(du), packs.get("upsampler.conv.weight", True, g.Up, F), None, Sl(dg), 3,
                    out2=Sl(dfeat_c16) if feat16 else Sl(dfeat_c), mask=Sl(sv.gr), mask_c0=0, mask_c1=F, math=math)
+    _capture("dg", lambda: dg.float())
     # ---- gff
     xN = sv.xloc(nb)
     _wgrad(xN, F, Sl(dg), G, "gff.0.weight", "gff.0.bias", wq, 3, math=math)
@@ -649,6 +652,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         dcat = dcats[k & 1]
         pre = f"residual_blocks.{k}."
         gout = dcat.x()
+        _capture(f"drdb{k}", lambda: gout.t[..., :F].float())
         _wgrad(cat.inp(g.CAT), g.CAT, gout, G, pre + "lff.weight", pre + "lff.bias", wq, 1, alpha=0.2, math=math)
         j = ran.index(k)
         wpb = mirror[j * (LAYERS + 1):(j + 1) * (LAYERS + 1)]     # packs of Wb_4 .. Wb_0, Wb_x
@@ -701,6 +705,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
     if (dw1 is None) != (dw2 is None):                     # one of the two frozen: the full form, the other into a sink
         dw1, dw2 = (dw1 if dw1 is not None else torch.empty_like(P[fc0])), (dw2 if dw2 is not None else torch.empty_like(P[fc2]))
     K.cbam_bwd_channel(dca_partial, sv.nblk, F, g.R, B, H * W, w1, w2, sv.gap, sv.hid, sv.ca, dw1, dw2, dgap_pix)
+    _capture("dgap_pix", lambda: dgap_pix)
     if "cbam" not in dxs:
         return None
 
@@ -714,6 +719,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         da2 = _new(dev, B, H, W, F, dtype=act_dtype)
         K.conv_forward(Sl(dlogits), packs.get(pre + "4.weight", True, g.Tp, F), None, Sl(da2), 3,
                        mask=Sl(sv.a2), mask_c0=0, mask_c1=F, math=math)
+        _capture("da2", lambda: da2.float())
         _wgrad(Sl(sv.a1), F, Sl(da2), G, pre + "2.weight", pre + "2.bias", wq, 3, math=math)
     if "att.2" in dxs:
         da1 = _new(dev, B, H, W, F, dtype=act_dtype)
@@ -722,6 +728,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         else:
             K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3,
                            mask=Sl(sv.a1), mask_c0=0, mask_c1=F, math=math)
+        _capture("da1", lambda: da1.float())
         _wgrad(Sl(sv.aligned), T * F, Sl(da1), G, pre + "0.weight", pre + "0.bias", wq, 3, math=math)
     if "att.0" not in dxs:
         # nothing before the attention convs needs a gradient: no motion or extractor backward
@@ -775,6 +782,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
                 # 81 real channels) - a row of 84 channels would leave lines half written (fill reads)
                 full = dx_t.shape[-1] if dx_t.dtype == torch.bfloat16 else K.pad4(chans[li])
                 K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, cout_store=full, math=math)
+            _capture(f"dflow_x{li}", lambda: dx_t.float())
             dy_t, dy_c = dx_t, chans[li]
         dcorr = dy_t
         _capture("f1", acts[1])
@@ -860,6 +868,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
                                P[pre + "bn.bias"], sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
             _wgrad(Sl(sv.dws[k]), F, Sl(dp), G, pre + "pointwise.weight", None, wq, 1, math=math)
             K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
+        _capture(f"dd{k}", lambda: dd.float())
         xin, xin_bn = sv.dw_in[k]
         dww = G.get(pre + "depthwise.weight")
         if fused_bwd and k > 0 and xin.dtype == torch.bfloat16 and os.environ.get("NVQ_FUSED_DW_BWD", "1") != "0":
@@ -880,6 +889,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
                                   bn_sums=bn_sums, bn_dgamma=bn_targets[0], bn_dbeta=bn_targets[1])
             else:
                 K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws)
+            _capture(f"dx{k}", lambda: dx.float())
             dcur = dx
             continue
         if dww is not None:
@@ -893,6 +903,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         else:
             dx = _new(dev, NI, H, W, F, dtype=act_dtype if k > 0 else torch.float32)
             K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
+        _capture(f"dx{k}", lambda: dx.float())
         dcur = dx
     if "head" in run:
         hw, hb = G.get("feature_extractor.head.0.weight"), G.get("feature_extractor.head.0.bias")
