@@ -469,14 +469,11 @@ int nvq_tsum_forward(const float* aligned, int aligned_ld, const float* logits, 
     NVQ_REQUIRE(T >= 1 && T <= NVQ_MAX_T && logits_ld >= T && attn_ld >= T, "tsum_forward: T %d", T);
     NVQ_REQUIRE(aligned_ld % 4 == 0 && weighted_ld % 4 == 0 && aligned_ld >= T * C, "tsum_forward: ld");
     const dim3 grid(tsum_blocks_host(H, W), N);
-#define NVQ_TS(M_, U_, A_, W_) hipLaunchKernelGGL((tsum_fwd_kernel<M_, U_, A_, W_>), grid, dim3(256), 0, (hipStream_t)stream, aligned, \
-                                                  aligned_ld, logits, logits_ld, T, C, (long)H * W, attn, attn_ld, weighted, weighted_ld, \
-                                                  gap_partial)
-#define NVQ_TS2(M_, U_) do { if (aligned_bf16) { if (weighted_bf16) NVQ_TS(M_, U_, true, true); else NVQ_TS(M_, U_, true, false); } \
-                             else { if (weighted_bf16) NVQ_TS(M_, U_, false, true); else NVQ_TS(M_, U_, false, false); } } while (0)
-    if (T <= 4) NVQ_TS2(4, 4); else NVQ_TS2(NVQ_MAX_T, 2);
-#undef NVQ_TS2
-#undef NVQ_TS
+    with_bools([&](auto SMALL, auto AB, auto WB) {             // T <= 4: <4, 4>, else <NVQ_MAX_T, 2>
+        constexpr int M = SMALL() ? 4 : NVQ_MAX_T, U = SMALL() ? 4 : 2;
+        hipLaunchKernelGGL((tsum_fwd_kernel<M, U, AB(), WB()>), grid, dim3(256), 0, (hipStream_t)stream, aligned, aligned_ld, logits,
+                           logits_ld, T, C, (long)H * W, attn, attn_ld, weighted, weighted_ld, gap_partial);
+    }, T <= 4, aligned_bf16, weighted_bf16);
     return check_launch("tsum_forward");
 }
 
@@ -488,12 +485,11 @@ int nvq_tsum_backward(const float* dweighted, int dweighted_ld, const float* dga
     NVQ_REQUIRE(T >= 1 && T <= NVQ_MAX_T && dlogits_ld >= T && attn_ld >= T, "tsum_backward: T %d", T);
     NVQ_REQUIRE(aligned_ld % 4 == 0 && dweighted_ld % 4 == 0 && daligned_ld % 4 == 0, "tsum_backward: ld");
     const long total = (long)N * H * W * (C / 4);
-#define NVQ_TB(A_, W_) hipLaunchKernelGGL((tsum_bwd_kernel<A_, W_>), dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream,  \
-                                          dweighted, dweighted_ld, dgap_pix, aligned, aligned_ld, attn, attn_ld, T, C, (long)H * W, \
-                                          daligned, daligned_ld, dlogits, dlogits_ld, total, aligned_bf16, daligned_bf16)
-    if (aligned_bf16 && daligned_bf16) { if (dweighted_bf16) NVQ_TB(true, true); else NVQ_TB(true, false); }
-    else { if (dweighted_bf16) NVQ_TB(false, true); else NVQ_TB(false, false); }
-#undef NVQ_TB
+    with_bools([&](auto AB, auto WB) {
+        hipLaunchKernelGGL((tsum_bwd_kernel<AB(), WB()>), dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dweighted,
+                           dweighted_ld, dgap_pix, aligned, aligned_ld, attn, attn_ld, T, C, (long)H * W, daligned, daligned_ld, dlogits,
+                           dlogits_ld, total, aligned_bf16, daligned_bf16);
+    }, aligned_bf16 && daligned_bf16, dweighted_bf16);
     return check_launch("tsum_backward");
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/nvq.h"
 
 namespace nvq {
@@ -30,6 +31,55 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Runtime bools to template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), so the caller
+// writes kernel<V(), R()> once and every combination is instantiated.  A hand-written ladder with one wrong arm runs
+// 16-byte loads on an unaligned pointer.
+template <bool... Bs, class F>
+inline void with_bools(F&& f) {
+    f(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, class F, class... Rest>
+inline void with_bools(F&& f, bool b, Rest... rest) {
+    if (b) with_bools<Bs..., true>(f, rest...);
+    else with_bools<Bs..., false>(f, rest...);
+}
+
+// The same for small integer sets, mixed with bools: with_consts("conv", f, one_of<1, 3>(ksize), bf16) calls
+// f(std::integral_constant<int, ksize>{}, std::bool_constant<bf16>{}) and returns NVQ_OK.  A value outside its set is
+// NVQ_EINVAL under the name `what` and f is not called: no last arm catches it.  A kernel that exists for a part of a
+// product only is dispatched on one "form" integer that the lambda takes apart again, so no further kernel is instantiated.
+template <int... Vs>
+struct one_of {
+    int v;
+    explicit one_of(int v_) : v(v_) {}
+};
+template <class... Ks, class F, class... Rest>
+inline int with_consts(const char*, F&&, bool, Rest...);
+template <class... Ks, class F, class... Rest>
+inline int with_consts(const char*, F&&, one_of<>, Rest...);
+template <class... Ks, class F, int V, int... Vs, class... Rest>
+inline int with_consts(const char*, F&&, one_of<V, Vs...>, Rest...);
+
+template <class... Ks, class F>
+inline int with_consts(const char*, F&& f) {
+    f(Ks{}...);
+    return NVQ_OK;
+}
+template <class... Ks, class F, class... Rest>
+inline int with_consts(const char* what, F&& f, bool b, Rest... rest) {
+    return b ? with_consts<Ks..., std::true_type>(what, f, rest...) : with_consts<Ks..., std::false_type>(what, f, rest...);
+}
+template <class... Ks, class F, class... Rest>
+inline int with_consts(const char* what, F&&, one_of<> a, Rest...) {
+    set_error("%s: no kernel form for the value %d", what, a.v);
+    return NVQ_EINVAL;
+}
+template <class... Ks, class F, int V, int... Vs, class... Rest>
+inline int with_consts(const char* what, F&& f, one_of<V, Vs...> a, Rest... rest) {
+    return a.v == V ? with_consts<Ks..., std::integral_constant<int, V>>(what, f, rest...)
+                    : with_consts<Ks...>(what, f, one_of<Vs...>(a.v), rest...);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -1248,24 +1248,11 @@ int conv_forward_bf16(const nvq_conv_desc& d, int vec_ok, hipStream_t s) {
         return check_launch("conv_forward_bf16");
     }
     const dim3 grid((unsigned)((long)tilesX * tilesY * d.n), ncz);
-#define NVQ_LAUNCH_CONVB(NB, KS)                                                                                        \
-    do {                                                                                                                 \
-        if (d.in_bf16)                                                                                                   \
-            hipLaunchKernelGGL((conv_bf16_kernel<NB, KS, true>), grid, dim3(256), 0, s, d, tilesX, tilesY, nkc, vec_ok, g_debug_mode & 3, TailArgs{});   \
-        else                                                                                                             \
-            hipLaunchKernelGGL((conv_bf16_kernel<NB, KS, false>), grid, dim3(256), 0, s, d, tilesX, tilesY, nkc, vec_ok, g_debug_mode & 3, TailArgs{});  \
-    } while (0)
-    if (d.ksize == 3) {
-        if (NT == 16) NVQ_LAUNCH_CONVB(1, 3);
-        else if (NT == 32) NVQ_LAUNCH_CONVB(2, 3);
-        else NVQ_LAUNCH_CONVB(4, 3);
-    } else {
-        if (NT == 16) NVQ_LAUNCH_CONVB(1, 1);
-        else if (NT == 32) NVQ_LAUNCH_CONVB(2, 1);
-        else NVQ_LAUNCH_CONVB(4, 1);
-    }
-#undef NVQ_LAUNCH_CONVB
-    return check_launch("conv_forward_bf16");
+    int rc = with_consts("conv_forward_bf16", [&](auto NB, auto KS, auto IB) {
+        hipLaunchKernelGGL((conv_bf16_kernel<NB(), KS(), IB()>), grid, dim3(256), 0, s, d, tilesX, tilesY, nkc, vec_ok,
+                           g_debug_mode & 3, TailArgs{});
+    }, one_of<1, 2, 4>(NT / 16), one_of<3, 1>(d.ksize), d.in_bf16);
+    return rc ? rc : check_launch("conv_forward_bf16");
 }
 
 // conv 3x3 (cin -> Cimg * s * s, bf16 input) + PixelShuffle(s) + bicubic skip + clamp in one launch
@@ -1369,23 +1356,15 @@ int conv_wgrad_bf16(const nvq_wgrad_desc& d, int nsplit, int nci, int nco, int t
         return nsplit;
     }
     const dim3 grid(nsplit, ncig, nco);
-#define NVQ_LAUNCH_WG(KS, XB, YB, CIC) \
-    hipLaunchKernelGGL((wgrad_bf16_kernel<KS, XB, YB, CIC>), grid, dim3(256), 0, s, d, tilesX, tilesY, ntiles, nci, nco)
-    if (d.ksize == 3) {
-        if (wide) NVQ_LAUNCH_WG(3, true, true, 64);
-        else if (d.x_bf16 && d.dy_bf16) NVQ_LAUNCH_WG(3, true, true, 32);
-        else if (d.x_bf16) NVQ_LAUNCH_WG(3, true, false, 32);
-        else if (d.dy_bf16) NVQ_LAUNCH_WG(3, false, true, 32);
-        else NVQ_LAUNCH_WG(3, false, false, 32);
-    } else {
-        if (wide) NVQ_LAUNCH_WG(1, true, true, 64);
-        else if (d.x_bf16 && d.dy_bf16) NVQ_LAUNCH_WG(1, true, true, 32);
-        else if (d.x_bf16) NVQ_LAUNCH_WG(1, true, false, 32);
-        else if (d.dy_bf16) NVQ_LAUNCH_WG(1, false, true, 32);
-        else NVQ_LAUNCH_WG(1, false, false, 32);
-    }
-#undef NVQ_LAUNCH_WG
-    return nsplit;      // > 0: the number of pixel splits actually used (the reduce kernel needs it)
+    // form 4: bf16 x and dy in 64-ci workgroups; 0 .. 3: 32-ci workgroups, 2 = bf16 x, 1 = bf16 dy
+    const int form = wide ? 4 : (d.x_bf16 ? 2 : 0) + (d.dy_bf16 ? 1 : 0);
+    int rc = with_consts("conv_wgrad(bf16)", [&](auto KS, auto FORM) {
+        constexpr int F = FORM();
+        hipLaunchKernelGGL((wgrad_bf16_kernel<KS(), F == 4 || (F & 2), F == 4 || (F & 1), F == 4 ? 64 : 32>), grid, dim3(256), 0, s,
+                           d, tilesX, tilesY, ntiles, nci, nco);
+    }, one_of<3, 1>(d.ksize), one_of<0, 1, 2, 3, 4>(form));
+    if (rc) return rc;
+    return nsplit;     // > 0: the number of pixel splits actually used (the reduce kernel needs it)
 }
 
 }  // namespace nvq

@@ -854,21 +854,18 @@ int corr_forward_mfma(const float* x1, int x1_ld, const float* x2, int x2_ld, in
     if (in_bf16) {                                            // bf16-stored features: the strip form (1.12 -> 1.03 ms at 16 x 540 x 960)
         const int njobs = N * tilesX * MS_SEG;
         int nwg = njobs < MS_MAXWG ? njobs : MS_MAXWG;
-#define NVQ_CS(CC, OB) \
-    hipLaunchKernelGGL((corr_fwd_strip_kernel<CC, OB>), dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(x1), x1_ld, \
-                       reinterpret_cast<const __bf16*>(x2), x2_ld, x2_images, H, W, tilesX, tilesY, njobs, out, out_ld)
-        if (C == 64) { if (out_bf16) NVQ_CS(64, true); else NVQ_CS(64, false); }
-        else { if (out_bf16) NVQ_CS(32, true); else NVQ_CS(32, false); }
-#undef NVQ_CS
-        return check_launch("correlation_forward(bf16, strip)");
+        int rc = with_consts("correlation_forward(bf16, strip)", [&](auto CC, auto OB) {
+            hipLaunchKernelGGL((corr_fwd_strip_kernel<CC(), OB()>), dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(x1),
+                               x1_ld, reinterpret_cast<const __bf16*>(x2), x2_ld, x2_images, H, W, tilesX, tilesY, njobs, out, out_ld);
+        }, one_of<64, 32>(C), out_bf16);
+        return rc ? rc : check_launch("correlation_forward(bf16, strip)");
     }
     const dim3 grid((unsigned)((long)tilesX * tilesY * N));
-#define NVQ_CF(CC, OB) \
-    hipLaunchKernelGGL((corr_fwd_mfma_kernel<CC, OB>), grid, dim3(M_T), 0, s, x1, x1_ld, x2, x2_ld, x2_images, H, W, tilesX, tilesY, out, out_ld, in_bf16)
-    if (C == 64) { if (out_bf16) NVQ_CF(64, true); else NVQ_CF(64, false); }
-    else { if (out_bf16) NVQ_CF(32, true); else NVQ_CF(32, false); }
-#undef NVQ_CF
-    return check_launch("correlation_forward(bf16)");
+    int rc = with_consts("correlation_forward(bf16)", [&](auto CC, auto OB) {
+        hipLaunchKernelGGL((corr_fwd_mfma_kernel<CC(), OB()>), grid, dim3(M_T), 0, s, x1, x1_ld, x2, x2_ld, x2_images, H, W, tilesX,
+                           tilesY, out, out_ld, in_bf16);
+    }, one_of<64, 32>(C), out_bf16);
+    return rc ? rc : check_launch("correlation_forward(bf16)");
 }
 
 int corr_backward_mfma(int which, const float* dcorr, int dcorr_ld, int dcorr_bf16, const float* other, int other_ld,
@@ -885,34 +882,31 @@ int corr_backward_mfma(int which, const float* dcorr, int dcorr_ld, int dcorr_bf
     if (which == 1 && dcorr_bf16 && other_bf16 && dcorr_ld % 8 == 0) {          // all-bf16 tensors: the strip form
         const int njobs = N * tilesX * MS_SEG;
         const int nwg = njobs < MS_MAXWG ? njobs : MS_MAXWG;
-#define NVQ_CB1(CC) hipLaunchKernelGGL(corr_bwd1_strip_kernel<CC>, dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(dcorr), \
-                                       dcorr_ld, reinterpret_cast<const __bf16*>(other), other_ld, other_images, H, W, tilesX, tilesY, \
-                                       njobs, dx, dx_ld, dx_coff, accumulate, reinterpret_cast<__bf16*>(dx16), dx16_ld, ad)
-        if (C == 64) NVQ_CB1(64); else NVQ_CB1(32);
-#undef NVQ_CB1
-        return check_launch("correlation_backward(bf16, strip)");
+        int rc = with_consts("correlation_backward(bf16, strip)", [&](auto CC) {
+            hipLaunchKernelGGL(corr_bwd1_strip_kernel<CC()>, dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(dcorr),
+                               dcorr_ld, reinterpret_cast<const __bf16*>(other), other_ld, other_images, H, W, tilesX, tilesY, njobs,
+                               dx, dx_ld, dx_coff, accumulate, reinterpret_cast<__bf16*>(dx16), dx16_ld, ad);
+        }, one_of<64, 32>(C));
+        return rc ? rc : check_launch("correlation_backward(bf16, strip)");
     }
     if (which == 2 && dcorr_bf16 && other_bf16 && dcorr_ld % 8 == 0) {          // all-bf16 tensors: the prefetching form
         const int ntiles = tilesX * tilesY * N;
         int nwg = ntiles < 256 ? ntiles : 256;                // one workgroup per CU (135 KB of LDS)
         if (nwg >= 8) nwg &= ~7;                              // multiple of the XCD count, see xcd_tile()
-#define NVQ_CB2P(CC) hipLaunchKernelGGL(corr_bwd2_pf_kernel<CC>, dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(dcorr), \
-                                        dcorr_ld, reinterpret_cast<const __bf16*>(other), other_ld, other_images, H, W, tilesX, tilesY, \
-                                        ntiles, dx, dx_ld, dx_coff, accumulate, groups, N, reinterpret_cast<__bf16*>(dx16), dx16_ld, ad)
-        if (C == 64) NVQ_CB2P(64); else NVQ_CB2P(32);
-#undef NVQ_CB2P
-        return check_launch("correlation_backward(bf16, prefetching)");
+        int rc = with_consts("correlation_backward(bf16, prefetching)", [&](auto CC) {
+            hipLaunchKernelGGL(corr_bwd2_pf_kernel<CC()>, dim3(nwg), dim3(M_T), 0, s, reinterpret_cast<const __bf16*>(dcorr), dcorr_ld,
+                               reinterpret_cast<const __bf16*>(other), other_ld, other_images, H, W, tilesX, tilesY, ntiles, dx, dx_ld,
+                               dx_coff, accumulate, groups, N, reinterpret_cast<__bf16*>(dx16), dx16_ld, ad);
+        }, one_of<64, 32>(C));
+        return rc ? rc : check_launch("correlation_backward(bf16, prefetching)");
     }
     const dim3 grid((unsigned)((long)tilesX * tilesY * N));
-#define NVQ_CB(CC, WH, DB) \
-    hipLaunchKernelGGL((corr_bwd_mfma_kernel<CC, WH, DB>), grid, dim3(M_T), 0, s, dcorr, dcorr_ld, other, other_ld, other_images, H, W, tilesX, tilesY, dx, dx_ld, dx_coff, accumulate, other_bf16, groups, N, reinterpret_cast<__bf16*>(dx16), dx16_ld, ad)
-#define NVQ_CB2(CC) \
-    do { if (which == 1) { if (dcorr_bf16) NVQ_CB(CC, 1, true); else NVQ_CB(CC, 1, false); } \
-         else { if (dcorr_bf16) NVQ_CB(CC, 2, true); else NVQ_CB(CC, 2, false); } } while (0)
-    if (C == 64) NVQ_CB2(64); else NVQ_CB2(32);
-#undef NVQ_CB2
-#undef NVQ_CB
-    return check_launch("correlation_backward(bf16)");
+    int rc = with_consts("correlation_backward(bf16)", [&](auto CC, auto WHICH, auto DB) {
+        hipLaunchKernelGGL((corr_bwd_mfma_kernel<CC(), WHICH(), DB()>), grid, dim3(M_T), 0, s, dcorr, dcorr_ld, other, other_ld,
+                           other_images, H, W, tilesX, tilesY, dx, dx_ld, dx_coff, accumulate, other_bf16, groups, N,
+                           reinterpret_cast<__bf16*>(dx16), dx16_ld, ad);
+    }, one_of<64, 32>(C), one_of<1, 2>(which), dcorr_bf16);
+    return rc ? rc : check_launch("correlation_backward(bf16)");
 }
 
 }  // namespace nvq

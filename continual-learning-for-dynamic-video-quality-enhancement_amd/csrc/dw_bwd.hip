@@ -345,17 +345,14 @@ static int dwconv_backward_impl(const float* x, int x_ld, const nvq_bn_input* bn
                 epi ? reinterpret_cast<const __bf16*>(epi->mask) : nullptr, epi ? epi->mask_ld : 0, workspace,
                 workspace + part_floats, H, W, tilesX, tilesY, group_images, tpg};
     hipStream_t s = (hipStream_t)stream;
-#define NVQ_DWBWD(B_, E_, S_, W_) hipLaunchKernelGGL((dw_bwd_kernel<B_, E_, S_, W_>), dim3(nwg, G), dim3(FT), 0, s, a)
-#define NVQ_DWBWD_ALL(W_)                                          \
-    if (bn_sums) NVQ_DWBWD(true, false, true, W_);                 \
-    else if (bn && epi) NVQ_DWBWD(true, true, false, W_);          \
-    else if (bn) NVQ_DWBWD(true, false, false, W_);                \
-    else if (epi) NVQ_DWBWD(false, true, false, W_);               \
-    else NVQ_DWBWD(false, false, false, W_);
-    if (wg) { NVQ_DWBWD_ALL(true) } else { NVQ_DWBWD_ALL(false) }
-#undef NVQ_DWBWD_ALL
-#undef NVQ_DWBWD
-    int rc = check_launch("dwconv_backward");
+    // 5 of the 8 (HAS_BN, EPI, SUMS): the sums come with the input transform and without an epilogue (required above)
+    const int form = bn_sums ? 4 : (bn ? 2 : 0) + (epi ? 1 : 0);
+    int rc = with_consts("dwconv_backward", [&](auto FORM, auto WG) {
+        constexpr int F = FORM();
+        hipLaunchKernelGGL((dw_bwd_kernel<(F >= 2), (F & 1) != 0, F == 4, WG()>), dim3(nwg, G), dim3(FT), 0, s, a);
+    }, one_of<0, 1, 2, 3, 4>(form), wg);
+    if (rc) return rc;
+    rc = check_launch("dwconv_backward");
     if (rc) return rc;
     if (wg) rc = launch_reduce_partials(workspace, G * nwg, FC * 9, 1.f, dweight, 0, s);
     if (rc || !bn_sums) return rc;

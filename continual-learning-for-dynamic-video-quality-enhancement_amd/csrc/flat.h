@@ -7,8 +7,6 @@
 #pragma once
 #include "common.h"
 
-#include <type_traits>
-
 namespace nvq {
 
 // one quad per thread and trip, at most 1024 blocks, at least 1: a function of n only
@@ -24,19 +22,6 @@ inline int group_blocks(long per, int groups) {
     const int cap = groups == 1 ? 2048 : 1024;
     if (nb > cap) nb = cap;
     return nb < 1 ? 1 : nb;
-}
-
-// Runtime bools to template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), so the caller
-// writes kernel<V(), R()> once and every combination is instantiated.  A hand-written ladder with one wrong arm runs
-// 16-byte loads on an unaligned pointer.
-template <bool... Bs, class F>
-inline void with_bools(F&& f) {
-    f(std::bool_constant<Bs>{}...);
-}
-template <bool... Bs, class F, class... Rest>
-inline void with_bools(F&& f, bool b, Rest... rest) {
-    if (b) with_bools<Bs..., true>(f, rest...);
-    else with_bools<Bs..., false>(f, rest...);
 }
 
 template <bool VEC>

@@ -971,17 +971,71 @@ static int bn2_ew_blocks(long npix, int ld) {
 
 size_t nvq_bn2_workspace_bytes(int C) { return (size_t)BN2_MAXBLK * 2 * (size_t)C * sizeof(float); }
 
+// ---- one launcher per BatchNorm pass.  The one-call entry points and the reduce / finish pairs of the synchronised BatchNorm
+// (nn.SyncBatchNorm) go through the same three and differ in their second stage only, so with local sums a pair is
+// bit-identical to the one-call form.  `who` names the entry point in the messages.
+
+// C channels in pixel rows of ld floats, read and written four channels at a time
+static bool bn2_rows_ok(int C, const float* p, int ld) { return ((C + 3) & ~3) <= ld && ld % 4 == 0 && aligned16(p); }
+
+// statistics, first stage: per-block sums of x and x^2 in workspace; *nb = the number of blocks
+static int bn2_launch_stats_partial(const char* who, const float* x, int x_ld, int C, long npix, float* workspace,
+                                    size_t workspace_bytes, int bf16, hipStream_t s, int* nb) {
+    NVQ_REQUIRE(C > 0 && C <= 1024 && bn2_rows_ok(C, x, x_ld) && npix > 0, "%s: C %d ld %d", who, C, x_ld);
+    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "%s: workspace", who);
+    *nb = bn2_nblk(npix);
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL((bn2_partial_kernel<0, BF()>), dim3(*nb), dim3(256), 0, s, x, x_ld, C, npix, nullptr, 0, nullptr, 0,
+                           nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, workspace);
+    }, bf16);
+    return check_launch("bn2_partial");
+}
+
+static int bn2_bwd_inputs_ok(const char* who, const float* dy, int dy_ld, const float* x, int x_ld, int C, const float* res,
+                             int res_ld, const float* dres, int dres_ld) {
+    NVQ_REQUIRE(C > 0 && C <= 1024 && bn2_rows_ok(C, x, x_ld) && bn2_rows_ok(C, dy, dy_ld), "%s: C %d", who, C);
+    NVQ_REQUIRE(!res || (dres && bn2_rows_ok(C, dres, dres_ld) && bn2_rows_ok(C, res, res_ld)),
+                "%s: a residual input needs its gradient buffer", who);
+    return NVQ_OK;
+}
+
+// backward, first stage: per-block sums of g and g xhat in workspace and, with a residual input, dres = g (the ReLU-masked
+// gradient, which the apply pass reads back); *nb = the number of blocks
+static int bn2_launch_bwd_partial(const char* who, const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix,
+                                  const float* mean, const float* invstd, const float* gamma, const float* beta, const float* res,
+                                  int res_ld, int relu, float* dres, int dres_ld, float* workspace, size_t workspace_bytes, int bf16,
+                                  hipStream_t s, int* nb) {
+    int rc = bn2_bwd_inputs_ok(who, dy, dy_ld, x, x_ld, C, res, res_ld, dres, dres_ld);
+    if (rc) return rc;
+    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "%s: workspace", who);
+    *nb = bn2_nblk(npix);
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL((bn2_partial_kernel<1, BF()>), dim3(*nb), dim3(256), 0, s, x, x_ld, C, npix, dy, dy_ld, res, res_ld,
+                           mean, invstd, gamma, beta, relu, dres, dres_ld, workspace);
+    }, bf16);
+    return check_launch("bn2_bwd_partial");
+}
+
+// backward, last stage: dx from the local fp32 sums (and `training`), or, with dsums, from the all-reduced fp64 sums and the
+// global pixel count (both on the device).  g: the buffer the first stage wrote, NULL without a residual input
+static int bn2_launch_bwd_apply(const char* who, const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix,
+                                const float* mean, const float* invstd, const float* gamma, const float* beta, const float* g,
+                                int g_ld, int relu, const float* sums, int training, const double* dsums, const double* count,
+                                float* dx, int dx_ld, int bf16, hipStream_t s) {
+    NVQ_REQUIRE(C > 0 && C <= 1024 && bn2_rows_ok(C, x, x_ld) && bn2_rows_ok(C, dy, dy_ld) && bn2_rows_ok(C, dx, dx_ld) &&
+                    dx_ld <= 1024, "%s: C %d dx ld %d", who, C, dx_ld);
+    with_bools([&](auto BF, auto DS) {
+        hipLaunchKernelGGL((bn2_bwd_apply_kernel<BF(), DS()>), dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, npix,
+                           dy, dy_ld, g, g_ld, mean, invstd, gamma, beta, sums, relu, training, dx, dx_ld, dsums, count);
+    }, bf16, dsums != nullptr);
+    return check_launch("bn2_bwd_apply");
+}
+
 int nvq_bn2_stats(const float* x, int x_ld, int C, long npix, float eps, float momentum, float* mean, float* invstd,
                   float* running_mean, float* running_var, float* workspace, size_t workspace_bytes, int bf16, void* stream) {
-    NVQ_REQUIRE(C > 0 && C <= 1024 && ((C + 3) & ~3) <= x_ld && x_ld % 4 == 0 && aligned16(x) && npix > 0, "bn2_stats: C %d ld %d", C, x_ld);
-    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "bn2_stats: workspace");
     hipStream_t s = (hipStream_t)stream;
-    const int nb = bn2_nblk(npix);
-#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<0, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, nullptr, 0, nullptr, 0, \
-                                       nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, workspace)
-    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
-#undef NVQ_B2P
-    int rc = check_launch("bn2_partial");
+    int nb;
+    int rc = bn2_launch_stats_partial("bn2_stats", x, x_ld, C, npix, workspace, workspace_bytes, bf16, s, &nb);
     if (rc) return rc;
     hipLaunchKernelGGL(bn2_stats_final_kernel, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, npix, eps, momentum, mean,
                        invstd, running_mean, running_var);
@@ -998,13 +1052,13 @@ int nvq_bn2_eval_stats(const float* running_mean, const float* running_var, int 
 int nvq_bn2_apply(const float* x, int x_ld, int C, long npix, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, const float* res, int res_ld, int relu, float* out, int out_ld, int bf16, void* stream) {
     NVQ_REQUIRE(C > 0 && ((C + 3) & ~3) <= x_ld && x_ld % 4 == 0 && C <= out_ld && out_ld % 4 == 0 && aligned16(out) && aligned16(x) &&
-                    (!res || (((C + 3) & ~3) <= res_ld && res_ld % 4 == 0 && aligned16(res))),
+                    (!res || bn2_rows_ok(C, res, res_ld)),
                 "bn2_apply: C %d ld %d/%d", C, x_ld, out_ld);
     NVQ_REQUIRE(out_ld <= 1024, "bn2_apply: ld %d", out_ld);
-#define NVQ_B2A(B_) hipLaunchKernelGGL(bn2_apply_kernel<B_>, dim3(bn2_ew_blocks(npix, out_ld)), dim3(256), 0, (hipStream_t)stream, x, \
-                                       x_ld, C, npix, mean, invstd, gamma, beta, res, res_ld, relu, out, out_ld)
-    if (bf16) NVQ_B2A(true); else NVQ_B2A(false);
-#undef NVQ_B2A
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL(bn2_apply_kernel<BF()>, dim3(bn2_ew_blocks(npix, out_ld)), dim3(256), 0, (hipStream_t)stream, x, x_ld, C,
+                           npix, mean, invstd, gamma, beta, res, res_ld, relu, out, out_ld);
+    }, bf16);
     return check_launch("bn2_apply");
 }
 
@@ -1014,29 +1068,25 @@ int nvq_bn2_backward_ex(const float* dy, int dy_ld, const float* x, int x_ld, in
                         float* workspace, size_t workspace_bytes, int bf16, int flags, void* stream) {
     NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "bn2_backward_ex: flags %d", flags);
     if (flags & NVQ_NO_WGRAD) dgamma = dbeta = nullptr;
-    const int C4 = (C + 3) & ~3;
-    NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && C4 <= dx_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && dx_ld % 4 == 0 &&
-                    aligned16(dx) && aligned16(x) && aligned16(dy), "bn2_backward: C %d", C);
-    NVQ_REQUIRE(!res || (dres && C4 <= dres_ld && dres_ld % 4 == 0 && C4 <= res_ld && res_ld % 4 == 0 && aligned16(res) && aligned16(dres)),
-                "bn2_backward: a residual input needs its gradient buffer");
+    // as before: C, x, dy, the residual pair and dx first, the workspace after them.  The passes check what they read and write
+    // themselves; dx (its ld <= 1024 included) is checked here as well, so that nothing runs before a refusal
+    int rc = bn2_bwd_inputs_ok("bn2_backward", dy, dy_ld, x, x_ld, C, res, res_ld, dres, dres_ld);
+    if (rc) return rc;
+    NVQ_REQUIRE(bn2_rows_ok(C, dx, dx_ld) && dx_ld <= 1024, "bn2_backward: dx ld %d", dx_ld);
     hipStream_t s = (hipStream_t)stream;
     if (!training && !dgamma && !dbeta) {
         // eval mode without affine gradients: dx (and dres) need no reduction - one element-wise pass, no workspace
-        NVQ_REQUIRE(dx_ld <= 1024, "bn2_backward: ld %d", dx_ld);
-#define NVQ_B2E(B_) hipLaunchKernelGGL(bn2_bwd_eval_kernel<B_>, dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, npix, dy, \
-                                       dy_ld, res, res_ld, mean, invstd, gamma, beta, relu, dx, dx_ld, dres, dres_ld)
-        if (bf16) NVQ_B2E(true); else NVQ_B2E(false);
-#undef NVQ_B2E
+        with_bools([&](auto BF) {
+            hipLaunchKernelGGL(bn2_bwd_eval_kernel<BF()>, dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, npix, dy,
+                               dy_ld, res, res_ld, mean, invstd, gamma, beta, relu, dx, dx_ld, dres, dres_ld);
+        }, bf16);
         return check_launch("bn2_bwd_eval");
     }
     NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C) + 2 * (size_t)C * sizeof(float), "bn2_backward: workspace");
-    const int nb = bn2_nblk(npix);
     float* sums = workspace + (size_t)BN2_MAXBLK * 2 * C;
-#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<1, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, dy, dy_ld, res, res_ld, \
-                                       mean, invstd, gamma, beta, relu, dres, dres_ld, workspace)
-    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
-#undef NVQ_B2P
-    int rc = check_launch("bn2_bwd_partial");
+    int nb;
+    rc = bn2_launch_bwd_partial("bn2_backward", dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, res, res_ld, relu, dres,
+                                    dres_ld, workspace, workspace_bytes, bf16, s, &nb);
     if (rc) return rc;
     if (dgamma && dbeta)
         hipLaunchKernelGGL(bn2_bwd_final_kernel<false>, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma, dbeta);
@@ -1044,12 +1094,8 @@ int nvq_bn2_backward_ex(const float* dy, int dy_ld, const float* x, int x_ld, in
         hipLaunchKernelGGL(bn2_bwd_final_kernel<true>, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma, dbeta);
     rc = check_launch("bn2_bwd_final");
     if (rc) return rc;
-    NVQ_REQUIRE(dx_ld <= 1024, "bn2_backward: ld %d", dx_ld);
-#define NVQ_B2B(B_) hipLaunchKernelGGL(bn2_bwd_apply_kernel<B_>, dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, npix, dy, \
-                                       dy_ld, dres, dres_ld, mean, invstd, gamma, beta, sums, relu, training, dx, dx_ld)
-    if (bf16) NVQ_B2B(true); else NVQ_B2B(false);
-#undef NVQ_B2B
-    return check_launch("bn2_bwd_apply");
+    return bn2_launch_bwd_apply("bn2_backward", dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, dres, dres_ld, relu, sums,
+                                training, nullptr, nullptr, dx, dx_ld, bf16, s);
 }
 
 int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
@@ -1061,20 +1107,12 @@ int nvq_bn2_backward(const float* dy, int dy_ld, const float* x, int x_ld, int C
                                dres, dres_ld, dgamma, dbeta, workspace, workspace_bytes, bf16, 0, stream);
 }
 
-// ---- synchronised BatchNorm (nn.SyncBatchNorm): reduce / finish phases of nvq_bn2_stats and nvq_bn2_backward.  With local
-// sums the pairs are bit-identical to the one-call forms.
 int nvq_bn2_stats_reduce(const float* x, int x_ld, int C, long npix, double* stats, float* workspace, size_t workspace_bytes,
                          int bf16, void* stream) {
-    NVQ_REQUIRE(C > 0 && C <= 1024 && ((C + 3) & ~3) <= x_ld && x_ld % 4 == 0 && aligned16(x) && npix > 0 && stats,
-                "bn2_stats_reduce: C %d ld %d", C, x_ld);
-    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "bn2_stats_reduce: workspace");
+    NVQ_REQUIRE(stats, "bn2_stats_reduce: stats");
     hipStream_t s = (hipStream_t)stream;
-    const int nb = bn2_nblk(npix);
-#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<0, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, nullptr, 0, nullptr, 0, \
-                                       nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, workspace)
-    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
-#undef NVQ_B2P
-    int rc = check_launch("bn2_partial");
+    int nb;
+    int rc = bn2_launch_stats_partial("bn2_stats_reduce", x, x_ld, C, npix, workspace, workspace_bytes, bf16, s, &nb);
     if (rc) return rc;
     hipLaunchKernelGGL(bn2_sums_kernel, dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, npix, stats);
     return check_launch("bn2_sums");
@@ -1089,24 +1127,16 @@ int nvq_bn2_stats_finish(const double* stats, int C, float eps, float momentum, 
 }
 
 // training-mode backward, reduce phase: sums[2C] = {sum g, sum g xhat} (fp64), dgamma / dbeta (local; either may be NULL) and,
-// with a residual input, dres = g (the ReLU-masked gradient, which the finish phase reads back)
+// with a residual input, dres = g
 int nvq_bn2_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
                             const float* invstd, const float* gamma, const float* beta, const float* res, int res_ld, int relu,
                             float* dres, int dres_ld, double* sums, float* dgamma, float* dbeta, float* workspace,
                             size_t workspace_bytes, int bf16, void* stream) {
-    const int C4 = (C + 3) & ~3;
-    NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && aligned16(x) && aligned16(dy) &&
-                    sums, "bn2_backward_reduce: C %d", C);
-    NVQ_REQUIRE(!res || (dres && C4 <= dres_ld && dres_ld % 4 == 0 && C4 <= res_ld && res_ld % 4 == 0 && aligned16(res) && aligned16(dres)),
-                "bn2_backward_reduce: a residual input needs its gradient buffer");
-    NVQ_REQUIRE(workspace_bytes >= nvq_bn2_workspace_bytes(C), "bn2_backward_reduce: workspace");
+    NVQ_REQUIRE(sums, "bn2_backward_reduce: sums");
     hipStream_t s = (hipStream_t)stream;
-    const int nb = bn2_nblk(npix);
-#define NVQ_B2P(B_) hipLaunchKernelGGL((bn2_partial_kernel<1, B_>), dim3(nb), dim3(256), 0, s, x, x_ld, C, npix, dy, dy_ld, res, res_ld, \
-                                       mean, invstd, gamma, beta, relu, dres, dres_ld, workspace)
-    if (bf16) NVQ_B2P(true); else NVQ_B2P(false);
-#undef NVQ_B2P
-    int rc = check_launch("bn2_bwd_partial");
+    int nb;
+    int rc = bn2_launch_bwd_partial("bn2_backward_reduce", dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, res, res_ld, relu,
+                                    dres, dres_ld, workspace, workspace_bytes, bf16, s, &nb);
     if (rc) return rc;
     hipLaunchKernelGGL((bn2_bwd_final_kernel<true, true>), dim3(ceil_div(C, 16)), dim3(256), 0, s, workspace, nb, C, sums, dgamma,
                        dbeta);
@@ -1118,17 +1148,10 @@ int nvq_bn2_backward_reduce(const float* dy, int dy_ld, const float* x, int x_ld
 int nvq_bn2_backward_finish(const float* dy, int dy_ld, const float* x, int x_ld, int C, long npix, const float* mean,
                             const float* invstd, const float* gamma, const float* beta, const float* dres, int dres_ld, int relu,
                             const double* sums, const double* count, float* dx, int dx_ld, int bf16, void* stream) {
-    const int C4 = (C + 3) & ~3;
-    NVQ_REQUIRE(C > 0 && C <= 1024 && C4 <= x_ld && C4 <= dy_ld && C4 <= dx_ld && x_ld % 4 == 0 && dy_ld % 4 == 0 && dx_ld % 4 == 0 &&
-                    dx_ld <= 1024 && aligned16(dx) && aligned16(x) && aligned16(dy) && sums && count,
-                "bn2_backward_finish: C %d", C);
-    NVQ_REQUIRE(!dres || (C4 <= dres_ld && dres_ld % 4 == 0 && aligned16(dres)), "bn2_backward_finish: dres");
-    hipStream_t s = (hipStream_t)stream;
-#define NVQ_B2B(B_) hipLaunchKernelGGL((bn2_bwd_apply_kernel<B_, true>), dim3(bn2_ew_blocks(npix, dx_ld)), dim3(256), 0, s, x, x_ld, C, \
-                                       npix, dy, dy_ld, dres, dres_ld, mean, invstd, gamma, beta, nullptr, relu, 1, dx, dx_ld, sums, count)
-    if (bf16) NVQ_B2B(true); else NVQ_B2B(false);
-#undef NVQ_B2B
-    return check_launch("bn2_bwd_apply");
+    NVQ_REQUIRE(sums && count, "bn2_backward_finish: sums / count");
+    NVQ_REQUIRE(!dres || bn2_rows_ok(C, dres, dres_ld), "bn2_backward_finish: dres");
+    return bn2_launch_bwd_apply("bn2_backward_finish", dy, dy_ld, x, x_ld, C, npix, mean, invstd, gamma, beta, dres, dres_ld, relu,
+                                nullptr, 1, sums, count, dx, dx_ld, bf16, (hipStream_t)stream);
 }
 
 int nvq_maxpool_forward(const float* x, int ld, int N, int H, int W, int k, int s, int pad, float* out, uint8_t* idx,
@@ -1137,12 +1160,10 @@ int nvq_maxpool_forward(const float* x, int ld, int N, int H, int W, int k, int 
     const int OH = (H + 2 * pad - k) / s + 1, OW = (W + 2 * pad - k) / s + 1;
     NVQ_REQUIRE(OH > 0 && OW > 0, "maxpool_forward: empty output");
     const long total = (long)N * OH * OW * (ld / 4);
-    if (bf16)
-        hipLaunchKernelGGL(maxpool_fwd_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x, ld, H, W, OH, OW, k,
-                           s, pad, total, out, idx);
-    else
-        hipLaunchKernelGGL(maxpool_fwd_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x, ld, H, W, OH, OW, k,
-                           s, pad, total, out, idx);
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL(maxpool_fwd_kernel<BF()>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x, ld, H, W, OH, OW,
+                           k, s, pad, total, out, idx);
+    }, bf16);
     return check_launch("maxpool_forward");
 }
 
@@ -1151,12 +1172,10 @@ int nvq_maxpool_backward(const float* dy, const uint8_t* idx, int ld, int N, int
     NVQ_REQUIRE(ld % 4 == 0 && k >= 1 && k <= 7 && s >= 1 && pad * 2 <= k, "maxpool_backward: args");
     const int OH = (H + 2 * pad - k) / s + 1, OW = (W + 2 * pad - k) / s + 1;
     const long total = (long)N * H * W * (ld / 4);
-    if (bf16)
-        hipLaunchKernelGGL(maxpool_bwd_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dy, idx, ld, H, W, OH,
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL(maxpool_bwd_kernel<BF()>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dy, idx, ld, H, W, OH,
                            OW, k, s, pad, total, dx);
-    else
-        hipLaunchKernelGGL(maxpool_bwd_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dy, idx, ld, H, W, OH,
-                           OW, k, s, pad, total, dx);
+    }, bf16);
     return check_launch("maxpool_backward");
 }
 
@@ -1164,12 +1183,10 @@ int nvq_subsample2(const float* in, int ld, int N, int H, int W, float* out, int
     NVQ_REQUIRE(ld % 4 == 0 && N > 0 && H > 0 && W > 0, "subsample2: args");
     const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
     const long total = backward ? (long)N * H * W * (ld / 4) : (long)N * OH * OW * (ld / 4);
-    if (bf16)
-        hipLaunchKernelGGL(subsample2_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, ld, H, W, OH, OW,
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL(subsample2_kernel<BF()>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, ld, H, W, OH, OW,
                            total, out, backward);
-    else
-        hipLaunchKernelGGL(subsample2_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, ld, H, W, OH, OW,
-                           total, out, backward);
+    }, bf16);
     return check_launch("subsample2");
 }
 
@@ -1191,12 +1208,10 @@ int nvq_bilinear_resize(const float* in, int ld, int N, int H, int W, int OH, in
 int nvq_depth_space2(const float* in, float* out, int N, int H, int W, int Co, int to_depth, int bf16, void* stream) {
     NVQ_REQUIRE(Co % 4 == 0 && N > 0 && H > 0 && W > 0, "depth_space2: Co %d", Co);
     const long total = (long)N * 2 * H * 2 * W * (Co / 4);
-    if (bf16)
-        hipLaunchKernelGGL(depth_space2_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, H, W, Co,
+    with_bools([&](auto BF) {
+        hipLaunchKernelGGL(depth_space2_kernel<BF()>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, H, W, Co,
                            total, to_depth);
-    else
-        hipLaunchKernelGGL(depth_space2_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, H, W, Co,
-                           total, to_depth);
+    }, bf16);
     return check_launch("depth_space2");
 }
 
@@ -1261,12 +1276,10 @@ int nvq_cast_slice(float* dst, int dst_ld, int dst_coff, int dst_bf16, const flo
     NVQ_REQUIRE(C > 0 && C % 4 == 0 && dst_ld % 4 == 0 && dst_coff % 4 == 0 && src_ld % 4 == 0 && src_coff % 4 == 0 &&
                     dst_coff + C <= dst_ld && src_coff + C <= src_ld, "cast_slice: C %d ld %d/%d", C, dst_ld, src_ld);
     const long total = npix * (C / 4);
-#define NVQ_CAST(DB, SB)                                                                                                  \
-    hipLaunchKernelGGL((cast_slice_kernel<DB, SB>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dst, dst_ld, \
-                       dst_coff, src, src_ld, src_coff, C, total, alpha, accumulate)
-    if (dst_bf16) { if (src_bf16) NVQ_CAST(true, true); else NVQ_CAST(true, false); }
-    else { if (src_bf16) NVQ_CAST(false, true); else NVQ_CAST(false, false); }
-#undef NVQ_CAST
+    with_bools([&](auto DB, auto SB) {
+        hipLaunchKernelGGL((cast_slice_kernel<DB(), SB()>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dst, dst_ld,
+                           dst_coff, src, src_ld, src_coff, C, total, alpha, accumulate);
+    }, dst_bf16, src_bf16);
     return check_launch("cast_slice");
 }
 

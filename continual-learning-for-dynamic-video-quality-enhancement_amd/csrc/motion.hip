@@ -999,11 +999,10 @@ int nvq_warp_forward(const float* feat, int feat_ld, const float* flow, int flow
     const long npix = (long)N * H * W;
     NVQ_REQUIRE(npix < ((long)1 << 31), "warp_forward: too many pixels");
     const int tilesX = (W + WT_W - 1) / WT_W, tilesY = (H + WT_H - 1) / WT_H;
-#define NVQ_WF(F_, O_) hipLaunchKernelGGL((warp_fwd_kernel<F_, O_>), dim3((unsigned)((long)tilesX * tilesY * N)), dim3(256), 0, \
-                                          (hipStream_t)stream, feat, feat_ld, flow, flow_ld, C, H, W, out, out_ld, out_coff, tilesX, tilesY)
-    if (feat_bf16) { if (out_bf16) NVQ_WF(true, true); else NVQ_WF(true, false); }
-    else { if (out_bf16) NVQ_WF(false, true); else NVQ_WF(false, false); }
-#undef NVQ_WF
+    with_bools([&](auto FB, auto OB) {
+        hipLaunchKernelGGL((warp_fwd_kernel<FB(), OB()>), dim3((unsigned)((long)tilesX * tilesY * N)), dim3(256), 0,
+                           (hipStream_t)stream, feat, feat_ld, flow, flow_ld, C, H, W, out, out_ld, out_coff, tilesX, tilesY);
+    }, feat_bf16, out_bf16);
     return check_launch("warp_forward");
 }
 
@@ -1030,28 +1029,23 @@ int nvq_warp_backward(const float* dout, int dout_ld, int dout_coff, const float
         NVQ_REQUIRE(npix < ((long)1 << 31), "warp_backward: too many pixels");
         const int tilesX = (W + WG_TW - 1) / WG_TW, tilesY = (H + WG_TH - 1) / WG_TH;
         static_assert(WG_TW == WT_W && WG_TH == WT_H, "the src and gather passes share the tile shape");
-#define NVQ_WS(F_, D_) hipLaunchKernelGGL((warp_bwd_src_kernel<F_, D_>), dim3((unsigned)((long)tilesX * tilesY * N)), dim3(256), 0, s, \
-                                          dout, dout_ld, dout_coff, feat, feat_ld, flow, flow_ld, C, H, W, dfeat, dfeat_ld, dflow,       \
-                                          dflow_ld, rec_w, rec_code, tilesX, tilesY, far_flag)
-        if (feat_bf16) { if (dout_bf16) NVQ_WS(true, true); else NVQ_WS(true, false); }
-        else { if (dout_bf16) NVQ_WS(false, true); else NVQ_WS(false, false); }
-#undef NVQ_WS
+        const dim3 tgrid((unsigned)((long)tilesX * tilesY * N));
+        with_bools([&](auto FB, auto DB) {
+            hipLaunchKernelGGL((warp_bwd_src_kernel<FB(), DB()>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, feat, feat_ld,
+                               flow, flow_ld, C, H, W, dfeat, dfeat_ld, dflow, dflow_ld, rec_w, rec_code, tilesX, tilesY, far_flag);
+        }, feat_bf16, dout_bf16);
         int rc = check_launch("warp_backward(src)");
         if (rc) return rc;
-#define NVQ_WG(D_, F_) hipLaunchKernelGGL((warp_bwd_gather_kernel<D_, F_>), dim3((unsigned)((long)tilesX * tilesY * N)), dim3(256), 0, s, \
-                                          dout, dout_ld, dout_coff, rec_w, rec_code, C, H, W, tilesX, tilesY, dfeat, dfeat_ld, overwrite)
-        if (dout_bf16) { if (dfeat_bf16) NVQ_WG(true, true); else NVQ_WG(true, false); }
-        else { if (dfeat_bf16) NVQ_WG(false, true); else NVQ_WG(false, false); }
-#undef NVQ_WG
+        with_bools([&](auto DB, auto GB) {
+            hipLaunchKernelGGL((warp_bwd_gather_kernel<DB(), GB()>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, rec_w, rec_code,
+                               C, H, W, tilesX, tilesY, dfeat, dfeat_ld, overwrite);
+        }, dout_bf16, dfeat_bf16);
         rc = check_launch("warp_backward(gather)");
         if (rc || !overwrite) return rc;
-if (dfeat_bf16) {
-                    hipLaunchKernelGGL(warp_bwd_far_kernel<true>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, dout, dout_ld, dout_coff, flow,
-                           flow_ld, C, H, W, dfeat, dfeat_ld, npix, dout_bf16, far_flag);
-        } else {
-                    hipLaunchKernelGGL(warp_bwd_far_kernel<false>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, dout, dout_ld, dout_coff, flow,
-                           flow_ld, C, H, W, dfeat, dfeat_ld, npix, dout_bf16, far_flag);
-        }
+        with_bools([&](auto GB) {
+            hipLaunchKernelGGL(warp_bwd_far_kernel<GB()>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, dout, dout_ld, dout_coff, flow,
+                               flow_ld, C, H, W, dfeat, dfeat_ld, npix, dout_bf16, far_flag);
+        }, dfeat_bf16);
         return check_launch("warp_backward(far)");
     }
     NVQ_REQUIRE(!overwrite, "warp_backward: the overwrite mode needs the gather form (records != NULL)");
@@ -1107,12 +1101,10 @@ int nvq_warp_backward_ex(const float* dout, int dout_ld, int dout_coff, const fl
     if (hipMemsetAsync(far_flag, 0, sizeof(int), s) != hipSuccess || hipMemsetAsync(count, 0, sizeof(int) * ntiles, s) != hipSuccess)
         return check_launch("warp_backward_ex(memset)");
     const dim3 tgrid((unsigned)ntiles);
-#define NVQ_WS(F_, D_) hipLaunchKernelGGL((warp_bwd_src_kernel<F_, D_>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, feat, \
-                                          feat_ld, flow, flow_ld, C, H, W, dfeat, dfeat_ld, dflow, dflow_ld, rec_w, rec_code,      \
-                                          tilesX, tilesY, far_flag)
-    if (feat_bf16) { if (dout_bf16) NVQ_WS(true, true); else NVQ_WS(true, false); }
-    else { if (dout_bf16) NVQ_WS(false, true); else NVQ_WS(false, false); }
-#undef NVQ_WS
+    with_bools([&](auto FB, auto DB) {
+        hipLaunchKernelGGL((warp_bwd_src_kernel<FB(), DB()>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, feat, feat_ld, flow,
+                           flow_ld, C, H, W, dfeat, dfeat_ld, dflow, dflow_ld, rec_w, rec_code, tilesX, tilesY, far_flag);
+    }, feat_bf16, dout_bf16);
     int rc = check_launch("warp_backward_ex(src)");
     if (rc) return rc;
     const int pgrid = ceil_div(npix, 256) < 2048 ? ceil_div(npix, 256) : 2048;
@@ -1126,12 +1118,11 @@ int nvq_warp_backward_ex(const float* dout, int dout_ld, int dout_coff, const fl
                        (const int*)offs, (const int*)ent_raw, ent, ntiles, (const int*)far_flag);
     rc = check_launch("warp_backward_ex(bins)");
     if (rc) return rc;
-#define NVQ_WG(D_, F_) hipLaunchKernelGGL((warp_bwd_gather_det_kernel<D_, F_>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, \
-                                          rec_w, rec_code, C, H, W, tilesX, tilesY, dfeat, dfeat_ld, (const int*)count,          \
-                                          (const int*)offs, (const int*)ent, (const int*)far_nw)
-    if (dout_bf16) { if (dfeat_bf16) NVQ_WG(true, true); else NVQ_WG(true, false); }
-    else { if (dfeat_bf16) NVQ_WG(false, true); else NVQ_WG(false, false); }
-#undef NVQ_WG
+    with_bools([&](auto DB, auto GB) {
+        hipLaunchKernelGGL((warp_bwd_gather_det_kernel<DB(), GB()>), tgrid, dim3(256), 0, s, dout, dout_ld, dout_coff, rec_w, rec_code,
+                           C, H, W, tilesX, tilesY, dfeat, dfeat_ld, (const int*)count, (const int*)offs, (const int*)ent,
+                           (const int*)far_nw);
+    }, dout_bf16, dfeat_bf16);
     return check_launch("warp_backward_ex(gather)");
 }
 

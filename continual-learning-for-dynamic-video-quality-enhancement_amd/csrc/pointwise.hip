@@ -1176,28 +1176,28 @@ static bool pow2_c4(int C) {
 static int blocks_for(long npix, int C);
 
 // BatchNorm backward, first half: the per-group sums  sum(g), sum(g xhat)  (g = dy masked by relu(bn(x)) > 0) in
-// sums[G][2C] inside the workspace, and dgamma / dbeta.  Used by nvq_bn_relu_backward and nvq_pw_bn_backward (pw_bwd.hip).
+// sums[G][2C] inside the workspace, and dgamma / dbeta (added to when `accumulate`).  Used by nvq_bn_relu_backward and
+// nvq_pw_bn_backward (pw_bwd.hip).
 static void launch_bn_bwd_reduce(dim3 grid, hipStream_t s, const float* dy, int dy_ld, const float* x, int x_ld, int C,
                                  long group_pix, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                  int dy_bf16, int x_bf16, float* part) {
-#define NVQ_BNR(D_, X_) hipLaunchKernelGGL((bn_bwd_reduce_kernel<D_, X_>), grid, dim3(256), 0, s, dy, dy_ld, x, x_ld, C, group_pix, \
-                                           mean, invstd, gamma, beta, part)
-    if (dy_bf16) { if (x_bf16) NVQ_BNR(true, true); else NVQ_BNR(true, false); }
-    else { if (x_bf16) NVQ_BNR(false, true); else NVQ_BNR(false, false); }
-#undef NVQ_BNR
+    with_bools([&](auto DB, auto XB) {
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<DB(), XB()>), grid, dim3(256), 0, s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd,
+                           gamma, beta, part);
+    }, dy_bf16, x_bf16);
 }
 
-int bn_backward_sums(const float* dy, int dy_ld, const float* x, int x_ld, int C, int G, long group_pix, const float* mean,
-                     const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, float* workspace,
-                     size_t workspace_bytes, int dy_bf16, int x_bf16, float** sums_out, hipStream_t s) {
+int bn_backward_sums(const char* who, const float* dy, int dy_ld, const float* x, int x_ld, int C, int G, long group_pix,
+                     const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                     float* workspace, size_t workspace_bytes, int accumulate, int dy_bf16, int x_bf16, float** sums_out, hipStream_t s) {
     const int nblk = blocks_for(group_pix, C);
     const size_t part_floats = (size_t)G * nblk * 2 * C;
-    if ((part_floats + (size_t)G * 2 * C) * sizeof(float) > workspace_bytes) { set_error("bn backward: workspace"); return NVQ_EWORKSPACE; }
+    if ((part_floats + (size_t)G * 2 * C) * sizeof(float) > workspace_bytes) { set_error("%s: workspace", who); return NVQ_EWORKSPACE; }
     float* sums = workspace + part_floats;
     launch_bn_bwd_reduce(dim3(nblk, G), s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd, gamma, beta, dy_bf16, x_bf16, workspace);
     int rc = check_launch("bn_bwd_reduce");
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums, dgamma, dbeta, 0);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums, dgamma, dbeta, accumulate);
     *sums_out = sums;
     return check_launch("bn_bwd_finalize");
 }
@@ -1209,12 +1209,18 @@ int bn_bwd_finalize_launch(const float* part, int nblk, int C, int G, float* sum
     return check_launch("bn_bwd_finalize");
 }
 
+// the order in which the groups are folded into the running statistics: order_host, or the identity when null
+static GroupOrder group_order(const int* order_host, int G) {
+    GroupOrder order;
+    for (int i = 0; i < NVQ_MAX_T; ++i) order.g[i] = i < G ? (order_host ? order_host[i] : i) : 0;
+    return order;
+}
+
 // part[g][blk][2C] = {sum, sum of squares} -> mean / invstd per group; the groups are folded into the running statistics in
 // `order_host` (identity when null).  Shared by nvq_bn_stats and the fused forward kernel (dwpw_fwd.hip).
 int bn_finalize_launch(const float* part, int nblk, int C, int G, long group_pix, float eps, float momentum,
                        const int* order_host, float* mean, float* invstd, float* rmean, float* rvar, hipStream_t s) {
-    GroupOrder order;
-    for (int i = 0; i < NVQ_MAX_T; ++i) order.g[i] = i < G ? (order_host ? order_host[i] : i) : 0;
+    const GroupOrder order = group_order(order_host, G);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, part, nblk, C, G, group_pix, eps, momentum, order, mean,
                        invstd, rmean, rvar);
     return check_launch("bn_finalize");
@@ -1257,12 +1263,11 @@ int nvq_head_forward(const float* frames, int B, int T, int Cin, int H, int W,
         const long nwg = (long)tilesX * tilesY * nslots * B;
         NVQ_REQUIRE(nwg < ((long)1 << 31), "head_forward: too many tiles");
         __bf16* i8 = reinterpret_cast<__bf16*>(img8);
-#define NVQ_HEAD_MFMA(NB) hipLaunchKernelGGL((head_mfma_kernel<NB>), dim3((unsigned)nwg), dim3(256), 0, s, frames, B, T, H, W, \
-                                             sm, weight, bias, out, out_ld, out_bf16, i8, tilesX, tilesY)
-        if (F == 16) NVQ_HEAD_MFMA(1);
-        else if (F == 32) NVQ_HEAD_MFMA(2);
-        else NVQ_HEAD_MFMA(4);
-#undef NVQ_HEAD_MFMA
+        int rc = with_consts("head_forward(mfma)", [&](auto NB) {
+            hipLaunchKernelGGL((head_mfma_kernel<NB()>), dim3((unsigned)nwg), dim3(256), 0, s, frames, B, T, H, W, sm, weight, bias,
+                               out, out_ld, out_bf16, i8, tilesX, tilesY);
+        }, one_of<1, 2, 4>(F / 16));
+        if (rc) return rc;
         return check_launch("head_forward(mfma)");
     }
     const int segsX = (W + HEAD_SEG - 1) / HEAD_SEG;
@@ -1294,12 +1299,12 @@ int nvq_head_wgrad(const float* frames, int B, int T, int Cin, int H, int W, con
     const size_t row = (size_t)F * K + F;
     if (row * nblk * sizeof(float) > workspace_bytes) { set_error("head_wgrad: workspace"); return NVQ_EWORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
-#define NVQ_LAUNCH_HW(CIN, AB) \
-    hipLaunchKernelGGL((head_wgrad_kernel<CIN, AB>), dim3(nblk), dim3(256), 0, s, frames, B, T, H, W, sm, dout, dout_ld, dout2, dout2_ld, act, act_ld, F, nseg, segsX, workspace)
-    if (Cin == 3) { if (act_bf16) NVQ_LAUNCH_HW(3, 1); else NVQ_LAUNCH_HW(3, 0); }
-    else { if (act_bf16) NVQ_LAUNCH_HW(1, 1); else NVQ_LAUNCH_HW(1, 0); }
-#undef NVQ_LAUNCH_HW
-    int rc = check_launch("head_wgrad");
+    int rc = with_consts("head_wgrad", [&](auto CIN, auto AB) {
+        hipLaunchKernelGGL((head_wgrad_kernel<CIN(), AB()>), dim3(nblk), dim3(256), 0, s, frames, B, T, H, W, sm, dout, dout_ld, dout2,
+                           dout2_ld, act, act_ld, F, nseg, segsX, workspace);
+    }, one_of<3, 1>(Cin), act_bf16);
+    if (rc) return rc;
+    rc = check_launch("head_wgrad");
     if (rc) return rc;
     // rows are [F*K weights | F biases]; reduce the two pieces separately (row stride = row)
     // by viewing the partials as nblk rows of `row` floats.
@@ -1337,20 +1342,16 @@ int nvq_dwconv_forward(const float* in, int in_ld, const float* weight, int C, f
         const int ntiles = tilesX * tilesY * N;
         int nwg = ntiles < DB_MAXWG ? ntiles : DB_MAXWG;
         if (nwg >= 8) nwg &= ~7;                              // multiple of the XCD count, see xcd_tile()
-#define NVQ_DWB(B_, E_)                                                                                                 \
-    hipLaunchKernelGGL((dwconv_bf16_kernel<B_, E_>), dim3(nwg, C / DB_C), dim3(DB_T), 0, (hipStream_t)stream,               \
-                       reinterpret_cast<const __bf16*>(in), in_ld, weight, C, out, out_ld, H, W, tilesX, tilesY, ntiles, flip, \
-                       out_bf16, make_dwbn(bn, C), ep)
+        // EPI 2: add and mask both bf16 and 8-byte addressable, 1: any other epilogue, 0: none
         const bool epb = epi && epi->add && epi->mask && epi->add_bf16 && epi->mask_bf16 && epi->add_ld % 4 == 0 &&
                          epi->mask_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(epi->add) & 7) == 0 &&
                          (reinterpret_cast<uintptr_t>(epi->mask) & 7) == 0;
-        if (bn && epb) NVQ_DWB(true, 2);
-        else if (bn && epi) NVQ_DWB(true, 1);
-        else if (bn) NVQ_DWB(true, 0);
-        else if (epb) NVQ_DWB(false, 2);
-        else if (epi) NVQ_DWB(false, 1);
-        else NVQ_DWB(false, 0);
-#undef NVQ_DWB
+        int rc = with_consts("dwconv_bf16", [&](auto HAS_BN, auto EPI) {
+            hipLaunchKernelGGL((dwconv_bf16_kernel<HAS_BN(), EPI()>), dim3(nwg, C / DB_C), dim3(DB_T), 0, (hipStream_t)stream,
+                               reinterpret_cast<const __bf16*>(in), in_ld, weight, C, out, out_ld, H, W, tilesX, tilesY, ntiles, flip,
+                               out_bf16, make_dwbn(bn, C), ep);
+        }, bn != nullptr, one_of<0, 1, 2>(epb ? 2 : epi ? 1 : 0));
+        if (rc) return rc;
         return check_launch("dwconv_bf16");
     }
     if (C % DT_C == 0) {
@@ -1406,22 +1407,40 @@ int nvq_dwconv_wgrad(const float* x, int x_ld, const float* dy, int dy_ld, int C
     return launch_reduce_partials(workspace, nblk, C * 9, 1.f, dweight, accumulate, (hipStream_t)stream);
 }
 
+// BatchNorm statistics, first stage: part[g][blk][2C] = {sum, sum of squares} in the workspace.  nvq_bn_stats and the reduce
+// phase of the synchronised form share it and differ in their second stage only.
+struct BnStatsGrid { int G, nblk; long group_pix; };
+static int bn_launch_stats_partial(const char* who, const float* x, int x_ld, int C, int N, int group_images, int H, int W,
+                                   float* workspace, size_t workspace_bytes, int x_bf16, hipStream_t s, BnStatsGrid* g) {
+    NVQ_REQUIRE(pow2_c4(C), "%s: C %d must be a power of two in [4,256]", who, C);
+    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "%s: groups", who);
+    NVQ_REQUIRE(x_ld % 4 == 0 && aligned16(x), "%s: ld", who);
+    g->G = N / group_images;
+    g->group_pix = (long)group_images * H * W;
+    g->nblk = blocks_for(g->group_pix, C);
+    if ((size_t)g->G * g->nblk * 2 * C * sizeof(float) > workspace_bytes) { set_error("%s: workspace", who); return NVQ_EWORKSPACE; }
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(g->nblk, g->G), dim3(256), 0, s, x, x_ld, C, g->group_pix, x_bf16, workspace);
+    return check_launch("bn_stats");
+}
+
 int nvq_bn_stats(const float* x, int x_ld, int C, int N, int group_images, int H, int W, float eps,
                  float momentum, const int* order_host, float* mean, float* invstd, float* running_mean,
                  float* running_var, float* workspace, size_t workspace_bytes, int x_bf16, void* stream) {
-    NVQ_REQUIRE(pow2_c4(C), "bn_stats: C %d must be a power of two in [4,256]", C);
-    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_stats: groups");
-    NVQ_REQUIRE(x_ld % 4 == 0 && aligned16(x), "bn_stats: ld");
-    const int G = N / group_images;
-    const long group_pix = (long)group_images * H * W;
-    const int nblk = blocks_for(group_pix, C);
-    if ((size_t)G * nblk * 2 * C * sizeof(float) > workspace_bytes) { set_error("bn_stats: workspace"); return NVQ_EWORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk, G), dim3(256), 0, s, x, x_ld, C, group_pix, x_bf16, workspace);
-    int rc = check_launch("bn_stats");
+    BnStatsGrid g;
+    int rc = bn_launch_stats_partial("bn_stats", x, x_ld, C, N, group_images, H, W, workspace, workspace_bytes, x_bf16, s, &g);
     if (rc) return rc;
-    return bn_finalize_launch(workspace, nblk, C, G, group_pix, eps, momentum, order_host, mean, invstd, running_mean,
+    return bn_finalize_launch(workspace, g.nblk, C, g.G, g.group_pix, eps, momentum, order_host, mean, invstd, running_mean,
                               running_var, s);
+}
+
+// Element-wise BatchNorm passes index a group's quads with 32 bits: items = group_pix * C / 4 quads, pixel = item >> shift
+static int bn_ew_items(const char* who, long group_pix, int C, int* shift, unsigned* items) {
+    NVQ_REQUIRE(group_pix * (C / 4) < ((long)1 << 32) - 256 * EW_ITEMS, "%s: group of %ld pixels too large", who, group_pix);
+    *shift = 0;
+    while ((1 << *shift) < C / 4) ++*shift;
+    *items = (unsigned)(group_pix * (C / 4));
+    return NVQ_OK;
 }
 
 int nvq_bn_eval_stats(const float* running_mean, const float* running_var, int C, int G, float eps,
@@ -1444,16 +1463,16 @@ int nvq_bn_apply_relu(const float* x, int x_ld, int C, int N, int group_images, 
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0, "bn_apply_relu: groups");
     const int G = N / group_images;
     const long group_pix = (long)group_images * H * W;
-    NVQ_REQUIRE(group_pix * (C / 4) < ((long)1 << 32) - 256 * EW_ITEMS, "bn_apply_relu: group of %ld pixels too large", group_pix);
-    int shift = 0;
-    while ((1 << shift) < C / 4) ++shift;
-    const unsigned items = (unsigned)(group_pix * (C / 4));
-#define NVQ_BNA(A_)                                                                                                            \
-    hipLaunchKernelGGL(bn_apply_relu_kernel<A_>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, (hipStream_t)stream, \
-                       x, x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, res, res_ld, outA, outA_ld, outA_coff,        \
-                       (long)(split_images < N ? split_images : N) * H * W, outB, outB_ld, outB_coff, x_bf16, out_bf16, res_bf16)
-    if (x_bf16 && out_bf16 && (res_bf16 || !res)) NVQ_BNA(true); else NVQ_BNA(false);
-#undef NVQ_BNA
+    int shift;
+    unsigned items;
+    int rc = bn_ew_items("bn_apply_relu", group_pix, C, &shift, &items);
+    if (rc) return rc;
+    with_bools([&](auto ALL_BF16) {
+        hipLaunchKernelGGL(bn_apply_relu_kernel<ALL_BF16()>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0,
+                           (hipStream_t)stream, x, x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, res, res_ld, outA,
+                           outA_ld, outA_coff, (long)(split_images < N ? split_images : N) * H * W, outB, outB_ld, outB_coff, x_bf16,
+                           out_bf16, res_bf16);
+    }, x_bf16 && out_bf16 && (res_bf16 || !res));
     return check_launch("bn_apply_relu");
 }
 
@@ -1467,22 +1486,15 @@ int nvq_bn_relu_backward(const float* dy, int dy_ld, const float* x, int x_ld, i
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_relu_backward: groups");
     const int G = N / group_images;
     const long group_pix = (long)group_images * H * W;
-    const int nblk = blocks_for(group_pix, C);
-    const size_t part_floats = (size_t)G * nblk * 2 * C;
-    if ((part_floats + (size_t)G * 2 * C) * sizeof(float) > workspace_bytes) { set_error("bn_relu_backward: workspace"); return NVQ_EWORKSPACE; }
-    float* sums = workspace + part_floats;
     hipStream_t s = (hipStream_t)stream;
-    launch_bn_bwd_reduce(dim3(nblk, G), s, dy, dy_ld, x, x_ld, C, group_pix, mean, invstd, gamma, beta, dy_bf16, x_bf16, workspace);
-    int rc = check_launch("bn_bwd_reduce");
+    float* sums;
+    int rc = bn_backward_sums("bn_relu_backward", dy, dy_ld, x, x_ld, C, G, group_pix, mean, invstd, gamma, beta, dgamma, dbeta,
+                              workspace, workspace_bytes, accumulate, dy_bf16, x_bf16, &sums, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(C), dim3(256), 0, s, workspace, nblk, C, G, sums,
-                       dgamma, dbeta, accumulate);
-    rc = check_launch("bn_bwd_finalize");
+    int shift;
+    unsigned items;
+    rc = bn_ew_items("bn_relu_backward", group_pix, C, &shift, &items);
     if (rc) return rc;
-    NVQ_REQUIRE(group_pix * (C / 4) < ((long)1 << 32) - 256 * EW_ITEMS, "bn_relu_backward: group of %ld pixels too large", group_pix);
-    int shift = 0;
-    while ((1 << shift) < C / 4) ++shift;
-    const unsigned items = (unsigned)(group_pix * (C / 4));
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, s, dy, dy_ld, x,
                        x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, sums, training, dx, dx_ld, dy_bf16,
                        x_bf16, dx_bf16, nullptr, nullptr);
@@ -1495,25 +1507,18 @@ int nvq_bn_relu_backward(const float* dy, int dy_ld, const float* x, int x_ld, i
 // the global sums and reads the pixel count from device memory.  With local sums the pair is bit-identical to the one-call form.
 int nvq_bn_stats_reduce(const float* x, int x_ld, int C, int N, int group_images, int H, int W, double* stats, float* workspace,
                         size_t workspace_bytes, int x_bf16, void* stream) {
-    NVQ_REQUIRE(pow2_c4(C), "bn_stats_reduce: C %d must be a power of two in [4,256]", C);
-    NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_stats_reduce: groups");
-    NVQ_REQUIRE(x_ld % 4 == 0 && aligned16(x) && stats, "bn_stats_reduce: ld");
-    const int G = N / group_images;
-    const long group_pix = (long)group_images * H * W;
-    const int nblk = blocks_for(group_pix, C);
-    if ((size_t)G * nblk * 2 * C * sizeof(float) > workspace_bytes) { set_error("bn_stats_reduce: workspace"); return NVQ_EWORKSPACE; }
+    NVQ_REQUIRE(stats, "bn_stats_reduce: stats");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk, G), dim3(256), 0, s, x, x_ld, C, group_pix, x_bf16, workspace);
-    int rc = check_launch("bn_stats");
+    BnStatsGrid g;
+    int rc = bn_launch_stats_partial("bn_stats_reduce", x, x_ld, C, N, group_images, H, W, workspace, workspace_bytes, x_bf16, s, &g);
     if (rc) return rc;
-    return bn_stats_sums(workspace, nblk, C, G, group_pix, stats, s);
+    return bn_stats_sums(workspace, g.nblk, C, g.G, g.group_pix, stats, s);
 }
 
 int nvq_bn_stats_finish(const double* stats, int C, int G, float eps, float momentum, const int* order_host, float* mean,
                         float* invstd, float* running_mean, float* running_var, void* stream) {
     NVQ_REQUIRE(C > 0 && G > 0 && G <= NVQ_MAX_T && stats && mean && invstd, "bn_stats_finish: C %d G %d", C, G);
-    GroupOrder order;
-    for (int i = 0; i < NVQ_MAX_T; ++i) order.g[i] = i < G ? (order_host ? order_host[i] : i) : 0;
+    const GroupOrder order = group_order(order_host, G);
     hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, stats, C, G, eps,
                        momentum, order, mean, invstd, running_mean, running_var);
     return check_launch("bn_stats_finish");
@@ -1564,11 +1569,10 @@ int nvq_bn_relu_backward_finish(const float* dy, int dy_ld, const float* x, int 
     NVQ_REQUIRE(group_images > 0 && N % group_images == 0 && N / group_images <= NVQ_MAX_T, "bn_relu_backward_finish: groups");
     const int G = N / group_images;
     const long group_pix = (long)group_images * H * W;
-    NVQ_REQUIRE(group_pix * (C / 4) < ((long)1 << 32) - 256 * EW_ITEMS, "bn_relu_backward_finish: group of %ld pixels too large",
-                group_pix);
-    int shift = 0;
-    while ((1 << shift) < C / 4) ++shift;
-    const unsigned items = (unsigned)(group_pix * (C / 4));
+    int shift;
+    unsigned items;
+    int rc = bn_ew_items("bn_relu_backward_finish", group_pix, C, &shift, &items);
+    if (rc) return rc;
     hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ceil_div((long)items, 256 * EW_ITEMS), G), dim3(256), 0, (hipStream_t)stream,
                        dy, dy_ld, x, x_ld, C, shift, items, group_pix, mean, invstd, gamma, beta, nullptr, 1, dx, dx_ld, dy_bf16,
                        x_bf16, dx_bf16, sums, count);
@@ -1583,12 +1587,10 @@ int nvq_axpy_slice(float* dst, int dst_ld, int dst_coff, const float* src, int s
                 "axpy_slice: alignment (C %d ld %d/%d)", C, dst_ld, src_ld);
     const long total = npix * (C / 4);
     if (total == 0) return NVQ_OK;
-    if (src_bf16)
-        hipLaunchKernelGGL(axpy_slice_kernel<true>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dst, dst_ld,
+    with_bools([&](auto SB) {
+        hipLaunchKernelGGL(axpy_slice_kernel<SB()>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dst, dst_ld,
                            dst_coff, src, src_ld, src_coff, mask, mask_ld, mask_coff, C, alpha, accumulate, total);
-    else
-        hipLaunchKernelGGL(axpy_slice_kernel<false>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dst, dst_ld,
-                           dst_coff, src, src_ld, src_coff, mask, mask_ld, mask_coff, C, alpha, accumulate, total);
+    }, src_bf16);
     return check_launch("axpy_slice");
 }
 

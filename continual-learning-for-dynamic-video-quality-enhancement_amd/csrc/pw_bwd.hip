@@ -16,9 +16,9 @@
 
 namespace nvq {
 
-int bn_backward_sums(const float* dy, int dy_ld, const float* x, int x_ld, int C, int G, long group_pix, const float* mean,
-                     const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, float* workspace,
-                     size_t workspace_bytes, int dy_bf16, int x_bf16, float** sums_out, hipStream_t s);   // pointwise.hip
+int bn_backward_sums(const char* who, const float* dy, int dy_ld, const float* x, int x_ld, int C, int G, long group_pix,
+                     const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                     float* workspace, size_t workspace_bytes, int accumulate, int dy_bf16, int x_bf16, float** sums_out, hipStream_t s);   // pointwise.hip
 int launch_wgrad_reduce(const float* part, int nsplit, int nci, int nco, int taps, int cout, int cin_w, float alpha,
                         int accumulate, float* dw, hipStream_t s);                                        // conv_igemm.hip
 
@@ -277,17 +277,16 @@ static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const fl
             if (!dgamma) dgamma = sink;
             if (!dbeta) dbeta = sink + PC;
         }
-        rc = bn_backward_sums(dy, dy_ld, p, p_ld, PC, G, group_pix, mean, invstd, gamma, beta, dgamma, dbeta, workspace + part_floats,
-                              sums_bytes, dy_bf16, 1, &sums, s);
+        rc = bn_backward_sums("bn backward", dy, dy_ld, p, p_ld, PC, G, group_pix, mean, invstd, gamma, beta, dgamma, dbeta,
+                              workspace + part_floats, sums_bytes, 0, dy_bf16, 1, &sums, s);
         if (rc) return rc;
     }
     PwBwdArgs a{dy, dy_ld, reinterpret_cast<const __bf16*>(p), p_ld, reinterpret_cast<const __bf16*>(d), d_ld, mean, invstd, gamma,
                 beta, sums, weight, reinterpret_cast<__bf16*>(dd), dd_ld, workspace, group_pix, G, training, tpg, (int)ntiles,
                 1.f / (float)group_pix, dsums, count};
-#define NVQ_PWB(D_, W_) hipLaunchKernelGGL((pw_bn_bwd_kernel<D_, W_>), dim3(nsplit), dim3(256), 0, s, a)
-    if (wg) { if (dy_bf16) NVQ_PWB(true, true); else NVQ_PWB(false, true); }
-    else { if (dy_bf16) NVQ_PWB(true, false); else NVQ_PWB(false, false); }
-#undef NVQ_PWB
+    with_bools([&](auto DB, auto WG) {
+        hipLaunchKernelGGL((pw_bn_bwd_kernel<DB(), WG()>), dim3(nsplit), dim3(256), 0, s, a);
+    }, dy_bf16, wg);
     rc = check_launch("pw_bn_backward");
     if (rc || !wg) return rc;
     return launch_wgrad_reduce(workspace, nsplit, 2, 2, 1, PC, PC, 1.f, 0, dweight, s);

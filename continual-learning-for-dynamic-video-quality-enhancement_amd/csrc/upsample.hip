@@ -195,11 +195,11 @@ int nvq_shuffle_clamp_backward(const float* dout, const uint8_t* pass, int B, in
     const long total = (long)B * H * W;
     const bool fast = Cimg == 3 && s >= 2 && s <= 4 && du_ld == (3 * s * s + 3) / 4 * 4 && aligned16(du) &&
                       (reinterpret_cast<uintptr_t>(dout) & 15) == 0 && (reinterpret_cast<uintptr_t>(pass) & 3) == 0;
-#define NVQ_SCB(S_) hipLaunchKernelGGL(shuffle_clamp_bwd_kernel<S_>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, \
-                                       dout, pass, Cimg, H, W, s, du, du_ld, total)
-    if (fast && s == 2) NVQ_SCB(2); else if (fast && s == 3) NVQ_SCB(3); else if (fast && s == 4) NVQ_SCB(4); else NVQ_SCB(0);
-#undef NVQ_SCB
-    return check_launch("shuffle_clamp_backward");
+    int rc = with_consts("shuffle_clamp_backward", [&](auto S) {      // S 0: the general kernel, any scale
+        hipLaunchKernelGGL(shuffle_clamp_bwd_kernel<S()>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, dout, pass,
+                           Cimg, H, W, s, du, du_ld, total);
+    }, one_of<0, 2, 3, 4>(fast ? s : 0));
+    return rc ? rc : check_launch("shuffle_clamp_backward");
 }
 
 int nvq_pixel_shuffle(float* u, int u_ld, int B, int C, int H, int W, int s, float* img, int backward, void* stream) {

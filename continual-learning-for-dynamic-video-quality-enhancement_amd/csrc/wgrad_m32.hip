@@ -576,33 +576,16 @@ int conv_wgrad_m32(const nvq_wgrad_desc& d, hipStream_t s) {
     if (wgs >= 8) wgs &= ~7;                                  // multiple of the XCD count: see xcd_tile()
     NVQ_REQUIRE((size_t)wgs * nci * nco * d.ksize * d.ksize <= (size_t)WGRAD_MAX_SLABS * 9 && wgs <= 512,
                 "conv_wgrad(bf16, all-ci): %d workgroups x %d x %d blocks exceed the workspace", wgs, nci, nco);
-    if (d.ksize == 1) {
-#define NVQ_LAUNCH_W1(NCI, NCO) \
-    hipLaunchKernelGGL((wgrad1_m32_kernel<NCI, NCO>), dim3(wgs), dim3(WM_NTHR), 0, s, d, tilesX, tilesY, ntiles)
-#define NVQ_W1_ROW(NCI) do { if (nco == 1) NVQ_LAUNCH_W1(NCI, 1); else NVQ_LAUNCH_W1(NCI, 2); } while (0)
-        switch (nci) {
-            case 2: NVQ_W1_ROW(2); break;
-            case 3: NVQ_W1_ROW(3); break;
-            case 4: NVQ_W1_ROW(4); break;
-            case 5: NVQ_W1_ROW(5); break;
-            case 6: NVQ_W1_ROW(6); break;
-            case 7: NVQ_W1_ROW(7); break;
-            default: NVQ_W1_ROW(8); break;
-        }
-#undef NVQ_W1_ROW
-#undef NVQ_LAUNCH_W1
-        return wgs;
-    }
-#define NVQ_LAUNCH_WM(NCI) hipLaunchKernelGGL((wgrad_m32_kernel<NCI>), dim3(wgs), dim3(WM_NTHR), 0, s, d, tilesX, tilesY, ntiles)
-    switch (nci) {
-        case 2: NVQ_LAUNCH_WM(2); break;
-        case 3: NVQ_LAUNCH_WM(3); break;
-        case 4: NVQ_LAUNCH_WM(4); break;
-        case 5: NVQ_LAUNCH_WM(5); break;
-        default: NVQ_LAUNCH_WM(6); break;
-    }
-#undef NVQ_LAUNCH_WM
-    return wgs;
+    int rc;
+    if (d.ksize == 1)
+        rc = with_consts("conv_wgrad(bf16, all-ci, 1x1)", [&](auto NCI, auto NCO) {
+            hipLaunchKernelGGL((wgrad1_m32_kernel<NCI(), NCO()>), dim3(wgs), dim3(WM_NTHR), 0, s, d, tilesX, tilesY, ntiles);
+        }, one_of<2, 3, 4, 5, 6, 7, 8>(nci), one_of<1, 2>(nco));
+    else
+        rc = with_consts("conv_wgrad(bf16, all-ci, 3x3)", [&](auto NCI) {
+            hipLaunchKernelGGL((wgrad_m32_kernel<NCI()>), dim3(wgs), dim3(WM_NTHR), 0, s, d, tilesX, tilesY, ntiles);
+        }, one_of<2, 3, 4, 5, 6>(nci));
+    return rc ? rc : wgs;
 }
 
 }  // namespace nvq

@@ -233,6 +233,37 @@ def test_dwconv_backward_ex(monkeypatch, with_bn):
     assert torch.isnan(sent).all()
 
 
+@pytest.mark.parametrize("form", ["epilogue", "bn + epilogue", "bn + sums"])
+def test_dwconv_backward_ex_other_forms(form):
+    """NVQ_NO_WGRAD with the add / mask epilogue (without and with the BatchNorm input) and with the BatchNorm-backward sums:
+    dw_bwd_kernel<., ., ., false> forms 1, 3 and 4 give the bits of the forms with the weight gradient"""
+    from nerve_cl import _engine, _nvq
+    g = torch.Generator().manual_seed(4)
+    N, H, W, T = 6, 21, 70, 3
+    dev = "cuda"
+    r = lambda *s: torch.randn(*s, generator=g).to(dev)
+    x, dy = r(N, H, W, 64).bfloat16(), r(N, H, W, 64).bfloat16()
+    wt = r(64, 1, 3, 3)
+    bn = (r(T, 64) * 0.1, r(T, 64).abs() + 0.5, r(64), r(64) * 0.1, N // T) if form != "epilogue" else None
+    kw = [dict(), dict()]
+    if form == "bn + sums":
+        for k in kw:
+            k.update(bn_sums=torch.zeros(T, 2, 64, device=dev), bn_dgamma=torch.zeros(64, device=dev),
+                     bn_dbeta=torch.zeros(64, device=dev))
+    else:
+        add, mask = r(N, H, W, 64), r(N, H, W, 64).bfloat16()
+        for k in kw:
+            k.update(add=add, mask=mask)
+    ws = _engine.workspace(torch.device(dev))
+    dx0, dw0, dx1 = torch.empty_like(x), torch.empty(64, 1, 3, 3, device=dev), torch.empty_like(x)
+    _nvq.dwconv_backward(x, bn, dy, wt, dx0, dw0, ws, **kw[0])
+    _nvq.dwconv_backward(x, bn, dy, wt, dx1, None, ws, **kw[1])
+    assert torch.equal(dx1.view(torch.int16), dx0.view(torch.int16))
+    for name in kw[0]:
+        if name.startswith("bn_"):
+            assert bits_equal(kw[1][name], kw[0][name]) and kw[0][name].abs().max().item() > 0, name
+
+
 def test_cbam_ex(monkeypatch):
     from nerve_cl import _engine, _nvq
     g = torch.Generator().manual_seed(3)

@@ -60,6 +60,8 @@ CONV_CASES = [
     (16, 16, 16, 3, 1, 40, 70),
     (192, 192, 64, 3, 1, 8, 35),
     (64, 64, 5, 3, 1, 6, 9),
+    (40, 40, 12, 1, 1, 9, 33),     # 1x1 with at most 16 / at most 32 output channels: the <1, 1> and <2, 1> forms
+    (64, 64, 32, 1, 2, 8, 32),
 ]
 
 
@@ -652,7 +654,8 @@ def to_nhwc_bf16(x, ld=None, coff=0):
 
 @pytest.mark.parametrize("cin,cout,k,N,H,W", [(64, 32, 3, 2, 13, 37), (224, 64, 1, 1, 11, 40), (192, 32, 3, 1, 8, 35),
                                               (128, 64, 3, 1, 9, 33), (32, 2, 3, 1, 8, 32),
-                                              (96, 32, 3, 2, 41, 37), (192, 32, 3, 1, 16, 70), (64, 24, 3, 1, 33, 32)])
+                                              (96, 32, 3, 2, 41, 37), (192, 32, 3, 1, 16, 70), (64, 24, 3, 1, 33, 32),
+                                              (64, 8, 1, 1, 9, 33), (64, 32, 1, 2, 8, 32)])      # 1x1: conv_bf16_kernel<1 | 2, 1, true>
 def test_conv_bf16_stored_input_and_output(K, cin, cout, k, N, H, W):
     """Input read as stored bf16 (no rounding in the kernel), output written as bf16 (rounded once) or fp32."""
     x, w, b = bf(rnd(N, cin, H, W)), rnd(cout, cin, k, k, scale=0.2), rnd(cout)
@@ -704,7 +707,11 @@ def test_conv_bf16_stored_dense_block_epilogues(K):
                                               # an odd number of 32-channel units: 64-channel chunks + a 32-channel tail with
                                               # its own pixel-split count in one launch (wgrad_bf16_mixed_kernel)
                                               (96, 32, 3, 2, 19, 70), (160, 32, 3, 3, 33, 41), (96, 128, 3, 2, 24, 33),
-                                              (224, 64, 3, 1, 17, 50)])
+                                              (224, 64, 3, 1, 17, 50),
+                                              # 1x1, 64 input channels, fewer than 64 output channels: wgrad_bf16_kernel<1, t, t, 64>
+                                              (64, 32, 1, 2, 9, 33),
+                                              # fewer than 64 input channels: the 32-ci workgroups also with bf16 x and dy
+                                              (32, 32, 3, 1, 9, 33), (32, 40, 1, 1, 9, 33)])
 def test_conv_bf16_stored_weight_gradient(K, xb, yb, cin, cout, k, N, H, W):
     x, dy = bf(rnd(N, cin, H, W)), bf(rnd(N, cout, H, W, seed=3))
     w = rnd(cout, cin, k, k).requires_grad_()
@@ -1611,3 +1618,137 @@ def test_rdb_tail_forward_fused(K, N, H, W, out16):
     full = torch.cat([cat[:, :cin], bf(y4)], 1)
     ref = 0.2 * F.conv2d(full, bf(wl), bl) + cat[:, :Fc]
     assert rel(from_nhwc(ob.float(), Fc), ref) < 5e-3
+
+
+# ----------------------------------------------------------------------------- storage-flag arms of the host dispatch
+# One case per kernel form that no test above selects (profiles/host_dispatch.txt lists every form with its test).  The flags
+# change how a value is loaded or stored, nothing else: each case runs the form next to the one already tested on tensors that
+# hold the same (bf16-representable) values.
+def test_warp_forward_fp32_features_bf16_output(K):
+    """warp_fwd_kernel<false, true>: fp32 features warped into a bf16 tensor = the fp32 output rounded once"""
+    C, B, H, W = 32, 2, 9, 20
+    feat = to_nhwc(bf(rnd(B, C, H, W)))
+    flow = to_nhwc(rnd(B, 2, H, W, seed=7) * 1.7, 4)
+    w32 = torch.zeros(B, H, W, 3 * C, device="cuda")
+    w16 = torch.zeros(B, H, W, 3 * C, device="cuda", dtype=torch.bfloat16)
+    K.warp_forward(K.Sl(feat), flow, K.Sl(w32, C, 2 * C))
+    K.warp_forward(K.Sl(feat), flow, K.Sl(w16, C, 2 * C))
+    assert torch.equal(w16, w32.bfloat16()) and w32[..., 2 * C:].abs().max().item() > 0
+    assert w16[..., :2 * C].abs().max().item() == 0
+
+
+@pytest.mark.parametrize("T", [3, 5])
+def test_softmax_weighted_sum_storage_forms(K, T):
+    """tsum_fwd_kernel<4, 4 | 8, 2> with a bf16 `weighted` (and fp32 / bf16 `aligned`), tsum_bwd_kernel with a bf16 dweighted:
+    against the fp32-stored run of test_softmax_weighted_sum on the same values"""
+    C, B, H, W = 16, 1, 6, 7
+    Tp = K.pad4(T)
+    a32 = to_nhwc(bf(rnd(B, T * C, H, W)))
+    lg = to_nhwc(rnd(B, T, H, W, seed=3) * 3, Tp)
+    dw32 = to_nhwc(bf(rnd(B, C, H, W, seed=6)))
+    dgap = (rnd(B, C, seed=8) * 0.1).cuda()
+    runs = {}
+    for ab in (a32, a32.bfloat16()):
+        for wdt in (torch.float32, torch.bfloat16):
+            attn, wt = torch.empty(B, H, W, Tp, device="cuda"), torch.empty(B, H, W, C, device="cuda", dtype=wdt)
+            gp = torch.empty(B, K.tsum_blocks(H, W), C, device="cuda")
+            K.tsum_forward(ab, lg, T, C, attn, wt, gp)
+            dal = torch.empty(B, H, W, T * C, device="cuda", dtype=ab.dtype)
+            dlg = torch.empty(B, H, W, Tp, device="cuda")
+            K.tsum_backward(dw32.to(wdt), dgap, ab, attn, T, C, dal, dlg)
+            runs[ab.dtype, wdt] = (attn, wt, gp, dal, dlg)
+    ref = runs[torch.float32, torch.float32]
+    for (adt, wdt), (attn, wt, gp, dal, dlg) in runs.items():
+        assert torch.equal(attn[..., :T], ref[0][..., :T]) and torch.equal(gp, ref[2]), (adt, wdt)   # GAP sums: unrounded values
+        assert torch.equal(wt, ref[1].to(wdt)) and torch.equal(dal, ref[3].to(adt)) and torch.equal(dlg, ref[4]), (adt, wdt)
+
+
+def test_batchnorm_relu_backward_storage_forms(K):
+    """bn_bwd_reduce_kernel<dy bf16, x bf16>, all four, <true, false> among them: equal to the fp32-stored run"""
+    C, B, G, H, W = 32, 2, 3, 9, 14
+    N = B * G
+    x32 = to_nhwc(bf(rnd(N, C, H, W) * 1.5 + 0.3))
+    dy32 = to_nhwc(bf(rnd(N, C, H, W, seed=12)))
+    gamma, beta = (1 + 0.2 * rnd(C)).cuda(), (0.1 * rnd(C, seed=2)).cuda()
+    mean, invstd = torch.empty(G, C, device="cuda"), torch.empty(G, C, device="cuda")
+    ws = ws_tensor(K)
+    K.bn_stats(x32, B, list(range(G)), mean, invstd, None, None, ws)
+    outs = []
+    for dyb in (dy32, dy32.bfloat16()):
+        for xb in (x32, x32.bfloat16()):
+            dx = torch.empty(N, H, W, C, device="cuda")
+            dg, db = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
+            K.bn_relu_backward(dyb, xb, B, mean, invstd, gamma, beta, True, dx, dg, db, ws)
+            outs.append((dx, dg, db))
+    for o in outs[1:]:
+        for a, b in zip(o, outs[0]):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("with_bn", [False, True])
+@pytest.mark.parametrize("add16", [False, True])
+def test_dwconv_bf16_epilogue_forms(K, with_bn, add16):
+    """dwconv_bf16_kernel<bn, EPI>: EPI 1 (fp32 add, bf16 mask) and EPI 2 (both bf16), without and with the fused BatchNorm
+    input, against the reference ops on the same bf16 operands (the bound of test_depthwise_backward_...: one bf16 rounding)"""
+    C, B, G, H, W = 64, 2, 3, 9, 14
+    N = B * G
+    x = bf(rnd(N, C, H, W, seed=1) * 1.5 + 0.2)
+    wd = rnd(C, 1, 3, 3, seed=3)
+    xb = to_nhwc_bf16(x)
+    bn, xin = None, x
+    if with_bn:
+        gamma, beta = (1 + 0.2 * rnd(C, seed=4)).cuda(), (0.1 * rnd(C, seed=5)).cuda()
+        m0, i0 = torch.empty(G, C, device="cuda"), torch.empty(G, C, device="cuda")
+        K.bn_stats(xb, B, list(range(G)), m0, i0, None, None, ws_tensor(K))
+        bn = (m0, i0, gamma, beta, B)
+        r = torch.empty(N, H, W, C, device="cuda", dtype=torch.bfloat16)
+        K.bn_apply_relu(xb, B, m0, i0, gamma, beta, None, K.Sl(r), N)
+        xin = from_nhwc(r.float())
+    add_c = bf(rnd(N, C, H, W, seed=6))
+    mask_c = bf(rnd(N, C, H, W, seed=7)).clamp_min(0)
+    add = to_nhwc_bf16(add_c) if add16 else to_nhwc(add_c)
+    out = torch.zeros(N, H, W, C, device="cuda", dtype=torch.bfloat16)
+    K.dwconv_forward(xb, wd.cuda(), out, bn=bn, add=add, mask=to_nhwc_bf16(mask_c))
+    want = (F.conv2d(xin, wd, None, padding=1, groups=C) + add_c) * (mask_c > 0)
+    assert rel(from_nhwc(out.float()), want) < 5e-3
+
+
+def test_head_forward_and_wgrad_one_channel(K):
+    """head_fwd_kernel<1> and head_wgrad_kernel<1, 0 | 1>: gray frames, as test_head_forward_and_wgrad"""
+    Fc, B, T, H, W = 32, 2, 3, 9, 14
+    frames = rnd(B, T, 1, H, W).abs()
+    w = rnd(Fc, 1, 3, 3, scale=0.4).requires_grad_()
+    b = rnd(Fc, scale=0.1).requires_grad_()
+    slots = [1, 0, 2]
+    ref = torch.stack([F.relu(F.conv2d(frames[:, t], w, b, padding=1)) for t in slots], 0)
+    dout = rnd(T, B, Fc, H, W, seed=4)
+    ref.backward(dout)
+    out = torch.empty(T * B, H, W, Fc, device="cuda")
+    K.head_forward(frames.cuda(), slots, w.detach().cuda(), b.detach().cuda(), out)
+    assert rel(from_nhwc(out), ref.detach().reshape(T * B, Fc, H, W)) < TOL
+    for act in (out, out.bfloat16()):
+        dw, db = torch.empty(Fc, 1, 3, 3, device="cuda"), torch.empty(Fc, device="cuda")
+        K.head_wgrad(frames.cuda(), slots, to_nhwc(dout.reshape(T * B, Fc, H, W)), act, dw, db, ws_tensor(K))
+        assert rel(dw, w.grad) < TOL and rel(db, b.grad) < TOL
+
+
+@pytest.mark.parametrize("nci", [2, 3, 4, 5, 6, 7, 8])
+def test_conv_bf16_weight_gradient_1x1_all_input_channels(K, nci):
+    """wgrad1_m32_kernel<nci, 1 | 2> (variant 2 forces the all-input-channel kernel at any size): 1x1, 64 .. 256 input and 32 / 64
+    output channels, interleaved bf16 x, against autograd and against the split kernel (variant 1), two ragged tiles"""
+    N, H, W = 1, 9, 33
+    cin = 32 * nci
+    x = bf(rnd(N, cin, H, W))
+    xs = to_nhwc_bf16(x)
+    ws = ws_tensor(K)
+    for cout in (32, 64):
+        dy = bf(rnd(N, cout, H, W, seed=3))
+        w = rnd(cout, cin, 1, 1).requires_grad_()
+        F.conv2d(x, w, None).backward(dy)
+        outs = []
+        for variant in (2, 1):
+            dw, db = torch.full((cout, cin, 1, 1), 7.0, device="cuda"), torch.full((cout,), 7.0, device="cuda")
+            K.conv_wgrad(K.Sl(xs), cin, K.Sl(to_nhwc_bf16(dy)), dw, db, ws, 1, math=K.MATH_BF16, variant=variant)
+            outs.append((dw, db))
+        assert rel(outs[0][0], w.grad) < TOL and rel(outs[0][1], dy.sum((0, 2, 3))) < TOL
+        assert rel(outs[0][0], outs[1][0]) < TOL and rel(outs[0][1], outs[1][1]) < TOL

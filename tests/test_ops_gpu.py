@@ -305,6 +305,22 @@ def test_bf16_storage_variants_of_the_frame_recovery_ops():
     assert a.dtype == B16 and rel(a.float(), b) < TOLB
 
 
+def test_cast_slice_every_storage_pair():
+    """nvq_cast_slice, cast_slice_kernel<dst bf16, src bf16>, all four: a 24-channel slice scaled and added into a wider tensor;
+    fp32 arithmetic on the stored values, one rounding when the destination is bf16"""
+    from nerve_cl import _ops
+    torch.manual_seed(11)
+    src32 = torch.randn(2, 5, 6, 32).bfloat16().float().cuda()
+    dst32 = torch.randn(2, 5, 6, 40).bfloat16().float().cuda()
+    want = dst32.clone()
+    want[..., 8:32] += 0.5 * src32[..., 4:28]
+    for ddt in (torch.float32, torch.bfloat16):
+        for sdt in (torch.float32, torch.bfloat16):
+            dst = dst32.to(ddt, copy=True)
+            _ops.cast_slice_(dst, src32.to(sdt), 24, dst_coff=8, src_coff=4, alpha=0.5, accumulate=True)
+            assert torch.equal(dst, want.to(ddt)), (ddt, sdt)
+
+
 def test_standalone_layer_modules_match_the_reference_layers_semantics():
     """the calls of the reference's tests/test_models.py:19-38 (on HIP tensors) plus values against torch modules holding
     the same parameters"""
