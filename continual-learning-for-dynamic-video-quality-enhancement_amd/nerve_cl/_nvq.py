@@ -243,6 +243,11 @@ SIGNATURES = {
     "nvq_psi_finish": (ci, [vp, vp, ci, cl, cl, vp, vp, vp]),
     "nvq_cell_descriptor": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "nvq_metric_window_update": (ci, [vp, vp, vp, ci, cf, cf, vp, vp, vp]),
+    # Kolmogorov-Smirnov drift test (csrc/ks.hip)
+    "nvq_sort_columns": (ci, [vp, vp, ci, ci, ci, vp, vp]),
+    "nvq_ks_statistic": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
+    "nvq_ks_pvalue": (ci, [vp, ci, ci, ci, vp, vp]),
+    "nvq_ks_finish": (ci, [vp, ci, vp, vp, vp, vp]),
     # federated aggregation and differential privacy on flat buffers (csrc/federated.hip)
     "nvq_fed_workspace_bytes": (sz, [ci, cl]),
     "nvq_fed_delta_norms": (ci, [vp, cl, ci, vp, cl, vp, vp, sz, vp]),
@@ -1483,6 +1488,40 @@ def metric_window_update(value: torch.Tensor, ring: torch.Tensor, state: torch.T
     assert state.dtype == torch.int32 and state.numel() == 2 and mean.dtype == torch.float64 and flag.dtype == torch.bool
     check(lib().nvq_metric_window_update(ptr(value), ptr(ring), ptr(state), ring.numel(), float(baseline), float(threshold),
                                          ptr(mean), ptr(flag), stream()), "nvq_metric_window_update")
+
+
+# ----------------------------------------------------------------------------- Kolmogorov-Smirnov drift test (csrc/ks.hip)
+KS_MAX_N = 4096     # rows of one set: a column is sorted in LDS
+
+
+def sort_columns(x: torch.Tensor, index: Optional[torch.Tensor], out: torch.Tensor) -> None:
+    """out (d, n) fp32 = the ascending columns of x (rows, d) fp32, or of the n rows the int32 index tensor names"""
+    n = _rows(x, index)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (x.shape[1], n)
+    check(lib().nvq_sort_columns(ptr(x), ptr(index), n, x.shape[0], x.shape[1], ptr(out), stream()), "nvq_sort_columns")
+
+
+def ks_statistic(ref_sorted: torch.Tensor, cur_sorted: torch.Tensor, h: torch.Tensor, stat: torch.Tensor) -> None:
+    """h (d,) int32 = lcm(n1, n2) times the two-sided statistic of every feature, stat (d,) float64 the statistic, from
+    ascending columns (d, n1) and (d, n2) fp32"""
+    d, n1 = ref_sorted.shape
+    assert ref_sorted.dtype == torch.float32 and cur_sorted.dtype == torch.float32 and cur_sorted.shape[0] == d
+    assert h.dtype == torch.int32 and stat.dtype == torch.float64 and h.numel() == d and stat.numel() == d
+    check(lib().nvq_ks_statistic(ptr(ref_sorted), ptr(cur_sorted), n1, cur_sorted.shape[1], d, ptr(h), ptr(stat), stream()),
+          "nvq_ks_statistic")
+
+
+def ks_pvalue(h: torch.Tensor, n1: int, n2: int, p: torch.Tensor) -> None:
+    """p (d,) float64 = the exact two-sided p-value of every h (d,) int32 for sets of n1 and n2 values"""
+    assert h.dtype == torch.int32 and p.dtype == torch.float64 and h.numel() == p.numel()
+    check(lib().nvq_ks_pvalue(ptr(h), n1, n2, h.numel(), ptr(p), stream()), "nvq_ks_pvalue")
+
+
+def ks_finish(p: torch.Tensor, threshold: float, score: torch.Tensor, flag: torch.Tensor) -> None:
+    """score (float64 scalar) = p.numel() * min(p), flag (bool scalar) = score < threshold, compared in double"""
+    assert p.dtype == torch.float64 and score.dtype == torch.float64 and flag.dtype == torch.bool
+    thr = C.c_double(float(threshold))                                  # read by the library before the call returns
+    check(lib().nvq_ks_finish(ptr(p), p.numel(), C.byref(thr), ptr(score), ptr(flag), stream()), "nvq_ks_finish")
 
 
 # ----------------------------------------------------------------------------- federated rounds and differential privacy

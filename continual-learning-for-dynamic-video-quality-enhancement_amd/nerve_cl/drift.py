@@ -15,12 +15,15 @@ Deliberate differences from the reference:
 * The reference subsample is drawn once in ``set_reference`` (its Gram sum is cached), not at every ``detect``.
 * PSI bin edges are computed on the host in float64 from one copy of the reference, once per reference (``psi_reference``): the
   single host round trip of this module.
-* ``method="ks"`` is not implemented (it needs per-feature sorts and scipy's exact small-sample p-values).
+* The reference's ``method="ks"`` lives in a class of its own, ``KSDriftDetector`` (``ks_2samp`` underneath; csrc/ks.hip,
+  DESIGN.md section 27): per-feature sorts in LDS and the exact two-sided p-value as a lattice walk, without scipy.
+  ``DriftDetector(method="ks")`` itself still refuses.
 * On the device the decision thresholds travel as fp32 kernel arguments: a score within 2^-24 relative of the threshold may be
   decided differently from the float64 comparison of the CPU composition.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -29,7 +32,8 @@ import torch
 
 from nerve_cl import _nvq
 
-__all__ = ["DriftResult", "DriftDetector", "ModelDriftMonitor", "mmd_rbf", "psi", "psi_reference", "frame_descriptor"]
+__all__ = ["DriftResult", "DriftDetector", "ModelDriftMonitor", "mmd_rbf", "psi", "psi_reference", "frame_descriptor",
+           "ks_2samp", "KSDriftDetector"]
 
 PSI_THRESHOLD = 0.2          # reference detector.py:155
 PSI_EPS = 1e-10
@@ -371,3 +375,181 @@ class ModelDriftMonitor:
     def poll(self) -> bool:
         """the device route's latest decision, read to the host"""
         return bool(self._flag.item()) if self._flag is not None else False
+
+
+# ----------------------------------------------------------------------------------------------- Kolmogorov-Smirnov (csrc/ks.hip)
+KS_MAX_SAMPLES = _nvq.KS_MAX_N          # one column of a set is sorted in LDS
+
+
+def _ks_sizes(n1: int, n2: int) -> Tuple[int, int, int]:
+    """(a, b, lcm): the distribution functions differ by (a x - b y) / lcm after x values of the first and y of the second set"""
+    g = math.gcd(n1, n2)
+    return n2 // g, n1 // g, n1 // g * n2
+
+
+def _ks_sorted(x: torch.Tensor, index: Optional[torch.Tensor]) -> torch.Tensor:
+    """The rows of x (rows, d) fp32 in use as ascending feature-major columns (d, n): fp32 from one launch on a HIP tensor,
+    float64 from torch.sort on the CPU (where -0.0 and +0.0 compare equal as well)."""
+    if not x.is_cuda:
+        rows = x if index is None else x[index.long()]
+        return torch.sort(rows.double().T.contiguous(), dim=1).values
+    n = x.shape[0] if index is None else index.numel()
+    out = torch.empty(x.shape[1], n, dtype=torch.float32, device=x.device)
+    with _nvq.device_guard(x.device):
+        _nvq.sort_columns(x, index, out)
+    return out
+
+
+def _ks_statistic_cpu(rs: torch.Tensor, cs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(h, D): h = lcm * D as exact integers, from right ranks of every value of either sample in both sorted samples"""
+    a, b, lcm = _ks_sizes(rs.shape[1], cs.shape[1])
+    both = torch.cat([rs, cs], 1)
+    c1 = torch.searchsorted(rs, both, right=True)
+    c2 = torch.searchsorted(cs, both, right=True)
+    h = (a * c1 - b * c2).abs().max(1).values
+    return h, h.double() / float(lcm)
+
+
+def _ks_pvalue_cpu(h: torch.Tensor, n1: int, n2: int) -> torch.Tensor:
+    """The exact two-sided p-value of every h (int64, (d,)): the walk of csrc/ks.hip, one anti-diagonal x + y = s of the lattice
+    per step for all features at once.  The mass at (x, y) moves to (x + 1, y) with weight (n1 - x) / rem and to (x, y + 1)
+    with (n2 - y) / rem, rem = n1 + n2 - (x + y); what arrives outside |a x - b y| < h is added to p and leaves the walk.  Only
+    the cells that the widest band (the largest h) can reach are carried."""
+    a, b, _ = _ks_sizes(n1, n2)
+    A, N = a + b, n1 + n2
+    d = h.numel()
+    hmax = int(h.max())
+    p = torch.zeros(d, dtype=torch.float64)
+    if hmax > 0:
+        hcol = h.reshape(d, 1)
+        mass, m0 = torch.ones(d, 1, dtype=torch.float64), 0                 # mass[:, i] is cell x = m0 + i of the previous step
+        for s in range(1, N + 1):
+            t = b * (s - 1)
+            lo = max(0, s - 1 - n2, (t - hmax) // A + 1)                    # live cells of step s - 1 under the widest band
+            hi = min(n1, s - 1, -((-(t + hmax)) // A) - 1)
+            x0, x1 = max(lo, s - n2), min(hi + 1, n1, s)                    # the cells they reach
+            if lo > hi or x0 > x1:
+                break
+            pad = torch.nn.functional.pad(mass, (1, 1))                     # pad[:, j] is cell m0 - 1 + j
+            x = torch.arange(x0, x1 + 1)
+            left, own = pad[:, x0 - m0:x1 - m0 + 1], pad[:, x0 - m0 + 1:x1 - m0 + 2]
+            new = (left * (n1 - x + 1).double() + own * (n2 - (s - 1 - x)).clamp(min=0).double()) / float(N - s + 1)
+            outside = (A * x - b * s).abs().reshape(1, -1) >= hcol
+            p += torch.where(outside, new, torch.zeros(())).sum(1)
+            mass, m0 = torch.where(outside, torch.zeros(()), new), x0
+    p[h <= 0] = 1.0
+    return p.clamp_(max=1.0)
+
+
+def _ks_from_sorted(rs: torch.Tensor, cs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(statistic, pvalue), float64 (d,), from ascending feature-major columns of either device"""
+    d, n1 = rs.shape
+    n2 = cs.shape[1]
+    if not rs.is_cuda:
+        h, stat = _ks_statistic_cpu(rs, cs)
+        return stat, _ks_pvalue_cpu(h, n1, n2)
+    h = torch.empty(d, dtype=torch.int32, device=rs.device)
+    stat = torch.empty(d, dtype=torch.float64, device=rs.device)
+    p = torch.empty(d, dtype=torch.float64, device=rs.device)
+    with _nvq.device_guard(rs.device):
+        _nvq.ks_statistic(rs, cs, h, stat)
+        _nvq.ks_pvalue(h, n1, n2, p)
+    return stat, p
+
+
+def _ks_check_rows(n: int, what: str) -> None:
+    if n > KS_MAX_SAMPLES:
+        raise ValueError(f"{what}: {n} rows, a Kolmogorov-Smirnov set has at most {KS_MAX_SAMPLES}")
+
+
+def ks_2samp(ref: torch.Tensor, cur: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two-sided two-sample Kolmogorov-Smirnov test of every feature: ``ref`` (n1, ...) and ``cur`` (n2, ...) are flattened per
+    row to d features; returns (statistic, pvalue), two float64 (d,) tensors on the samples' device, the numbers that
+    ``scipy.stats.ks_2samp`` gives in its exact mode (which its ``auto`` picks for sets this small).  A set has at most 4096
+    rows.  Values that compare equal are ties (-0.0 and +0.0 too), infinities are ordinary values; NaN is not supported (the
+    result is then unspecified)."""
+    a, b = _rows(ref, "ref"), _rows(cur, "cur")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"ks_2samp: rows of {a.shape[1]} and {b.shape[1]} features")
+    if a.device != b.device:
+        raise ValueError(f"ks_2samp: ref on {a.device}, cur on {b.device}")
+    _ks_check_rows(a.shape[0], "ks_2samp: ref")
+    _ks_check_rows(b.shape[0], "ks_2samp: cur")
+    return _ks_from_sorted(_ks_sorted(a, None), _ks_sorted(b, None))
+
+
+class KSDriftDetector:
+    """The reference's ``DriftDetector(method="ks")``: a two-sample Kolmogorov-Smirnov test per feature, the score
+    ``min(p_values) * d`` (Bonferroni without a clamp: it can exceed 1), drift when ``score < threshold``.  The methods and
+    their contracts are ``DriftDetector``'s; ``detect`` also names the features: ``details["p_values"]`` and
+    ``details["statistics"]`` are float64 (d,) tensors on the data's device.  A set with more than ``max_samples`` rows is
+    subsampled by the module's rule, the reference once in ``set_reference`` (where it is also sorted, once), the current set at
+    every detect."""
+
+    def __init__(self, threshold: float = 0.05, window_size: int = 1000, max_samples: int = KS_MAX_SAMPLES,
+                 generator: Optional[torch.Generator] = None):
+        if not 1 <= max_samples <= KS_MAX_SAMPLES:
+            raise ValueError(f"max_samples must be in [1, {KS_MAX_SAMPLES}]")
+        if window_size < 1:
+            raise ValueError("window_size must be >= 1")
+        self.method, self.threshold, self.window_size, self.max_samples = "ks", threshold, window_size, max_samples
+        self.generator = generator
+        self.reference_data: Optional[torch.Tensor] = None
+        self._window: Optional[torch.Tensor] = None
+        self._fill = 0
+        self._ref_index: Optional[torch.Tensor] = None
+        self._ref_sorted: Optional[torch.Tensor] = None      # (d, n_ref) ascending columns of the reference rows in use
+
+    def set_reference(self, data: torch.Tensor) -> None:
+        """Set the reference distribution: the data stay on their device, the subsample is drawn and its columns sorted here."""
+        ref = _rows(data, "reference")
+        self.reference_data = ref
+        self._ref_index = _subsample(ref.shape[0], self.max_samples, ref.device, self.generator)
+        self._ref_sorted = _ks_sorted(ref, self._ref_index)
+
+    def _scores(self, current: torch.Tensor):
+        if self.reference_data is None:
+            raise ValueError("Reference data not set")
+        ref, cur = self.reference_data, _rows(current, "current")
+        if cur.shape[1] != ref.shape[1]:
+            raise ValueError(f"current rows have {cur.shape[1]} features, the reference {ref.shape[1]}")
+        if cur.device != ref.device:
+            raise ValueError(f"current data on {cur.device}, the reference on {ref.device}")
+        ic = _subsample(cur.shape[0], self.max_samples, cur.device, self.generator)
+        stat, p = _ks_from_sorted(self._ref_sorted, _ks_sorted(cur, ic))
+        if not cur.is_cuda:
+            score = p.min() * float(p.numel())
+            return score, score < self.threshold, p, stat
+        score = torch.empty((), dtype=torch.float64, device=cur.device)
+        flag = torch.empty((), dtype=torch.bool, device=cur.device)
+        with _nvq.device_guard(cur.device):
+            _nvq.ks_finish(p, self.threshold, score, flag)
+        return score, flag, p, stat
+
+    def detect_device(self, current: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(score, is_drift) as a float64 and a bool scalar tensor on the data's device; no host synchronisation."""
+        return self._scores(current)[:2]
+
+    def detect(self, current: torch.Tensor) -> DriftResult:
+        """Detect drift between the reference and ``current``; raises ValueError("Reference data not set") without one."""
+        score, flag, p, stat = self._scores(current)
+        if score.is_cuda:
+            both = torch.stack([score, flag.double()]).cpu()            # the one host copy
+            s, f = float(both[0]), bool(both[1] != 0)
+        else:
+            s, f = float(score), bool(flag)
+        return DriftResult(is_drift=f, score=s, threshold=self.threshold, method="ks", details={"p_values": p, "statistics": stat})
+
+    def update(self, sample: torch.Tensor) -> Optional[DriftResult]:
+        """Add one sample (any shape) to the preallocated window on its device; a DriftResult once ``window_size`` samples
+        have arrived (the window then starts over), else None."""
+        row = torch.as_tensor(sample).detach().reshape(-1)
+        if self._window is None or self._window.shape[1] != row.numel() or self._window.device != row.device:
+            self._window = torch.empty(self.window_size, row.numel(), dtype=torch.float32, device=row.device)
+            self._fill = 0
+        self._window[self._fill].copy_(row)
+        self._fill += 1
+        if self._fill < self.window_size:
+            return None
+        self._fill = 0
+        return self.detect(self._window)

@@ -934,6 +934,31 @@ int nvq_cell_descriptor(const float* x, int B, int C, int H, int W, int gh, int 
 int nvq_metric_window_update(const float* value, float* ring, int* state, int window, float baseline, float threshold,
                              double* mean_out, unsigned char* flag_out, void* stream);
 
+/* ------------------------------------------------------------------ Kolmogorov-Smirnov drift test (csrc/ks.hip, DESIGN.md
+ * section 27).  The reference detector's method="ks": scipy.stats.ks_2samp per feature, two-sided, exact p-values.  A set has
+ * 1 .. 4096 rows (one column is sorted in LDS); every entry point returns NVQ_EINVAL on a null pointer, a row count outside
+ * that range or d < 1 before anything is launched.  NaN inputs are not supported: the answers are then unspecified, but no
+ * access leaves its buffer.
+ *
+ * nvq_sort_columns: out (d x n, feature-major fp32) = every feature's n values in ascending order, from the row-major fp32
+ * matrix x (rows x d); index (device, may be NULL): value i of a feature comes from matrix row index[i], an index outside
+ * [0, rows) reads as 0; without one the first n rows.  -0.0 is written as +0.0.  Bitonic network over the next power of two,
+ * padded with +inf in LDS only. */
+int nvq_sort_columns(const float* x, const int* index, int n, int rows, int d, float* out, void* stream);
+/* ref_sorted (d x n1), cur_sorted (d x n2): ascending feature-major columns.  With g = gcd(n1, n2), a = n2 / g, b = n1 / g:
+ * h_out[f] = max over every value v of either column of |a #{ref <= v} - b #{cur <= v}| (ranks after all copies of v:
+ * searchsorted(side='right'), which is what makes ties come out as in scipy), exact integers; d_out[f] = h / lcm(n1, n2),
+ * one division in double: the two-sided statistic. */
+int nvq_ks_statistic(const float* ref_sorted, const float* cur_sorted, int n1, int n2, int d, int* h_out, double* d_out,
+                     void* stream);
+/* p_out[f] = P(D >= h[f] / lcm(n1, n2)) under the null hypothesis, exactly (up to rounding): the mass that a walk over the
+ * draws of the pooled sample without replacement carries out of the band |a x - b y| < h.  Positive terms only, summed in a
+ * fixed order: the bits depend on (n1, n2, h[f]) alone.  h <= 0 gives 1, h > lcm gives 0.  One workgroup per feature. */
+int nvq_ks_pvalue(const int* h, int n1, int n2, int d, double* p_out, void* stream);
+/* *score_out = d * min_i p[i] (Bonferroni, not clamped), *flag_out (one byte) = score < *threshold_host, compared in double.
+ * threshold_host points to one double in HOST memory, read before the call returns (this ABI passes no double by value). */
+int nvq_ks_finish(const double* p, int d, const double* threshold_host, double* score_out, unsigned char* flag_out, void* stream);
+
 /* ------------------------------------------------------------------ federated rounds and differential privacy
  * (csrc/federated.hip).  Flat fp32 buffers, sums in double, no atomics; every grid depends on the sizes
  * only and a thread owns whole quads in the 16-byte form (everything 16-byte aligned, stride % 4 == 0) and in the scalar form
