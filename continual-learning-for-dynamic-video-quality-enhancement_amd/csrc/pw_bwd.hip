@@ -12,6 +12,12 @@
 // tiles are plain pixel ranges (cut at the BatchNorm groups' boundaries: the statistics are per frame group).  Workgroups
 // are persistent over tiles and keep the weight-gradient accumulators (one 16-ci block x the four 16-co blocks per wave) in
 // registers; partial 32 x 32 slabs go through the weight-gradient reduce kernel (fixed order, double: deterministic).
+//
+// NVQ_PW_RECOMPUTE: p is what nvq_dwpw_forward made of this d and this weight, p = bf16(d W^T) - and the tile's d is in LDS
+// anyway (the weight gradient's operand).  Then p is not read: every wave forms the p of its 32 pixels again with the MFMAs of
+// dwpw_fwd_kernel's pointwise stage (same operand roles, same channel -> k slot mapping, same order of the two K = 32
+// accumulations, same rounding: the bits of the stored p, so no ReLU mask differs), takes dy from a third LDS image and
+// writes dp in the accumulator layout: 2 reads + 1 write (dy, d -> dd) for 16 more MFMAs and one more barrier per tile.
 #include "conv_common.h"
 
 namespace nvq {
@@ -50,12 +56,15 @@ __device__ __forceinline__ float bhi(unsigned u) { return __uint_as_float(u & 0x
 
 // WG = false (nvq_pw_bn_backward_ex, NVQ_NO_WGRAD): the input gradient alone - d is neither read nor staged, no weight-gradient
 // MFMA, no partial slabs; dd is formed by the same instructions in the same order as with WG.
-template <bool DYB, bool WG>
+// RP (NVQ_PW_RECOMPUTE; bf16 dy and WG only): p is formed again from the staged d instead of being read.
+template <bool DYB, bool WG, bool RP>
 __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) __bf16 lds[2 * TP * PS];
+    static_assert(!RP || (DYB && WG), "the recompute form stages d and a bf16 dy");
+    __shared__ __attribute__((aligned(16))) __bf16 lds[(RP ? 3 : 2) * TP * PS];
     __shared__ __attribute__((aligned(16))) float cst[MAXG][6][PC];   // mean, invstd, gamma, beta, mean(g), mean(g xhat)
     __bf16* dps = lds;
     __bf16* ds_ = lds + TP * PS;
+    __bf16* dys = lds + 2 * TP * PS;                         // (RP) the tile's dy
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, g4 = lane >> 4;
@@ -84,6 +93,17 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int j = 0; j < 8; ++j) wf[cb][kb][j] = (__bf16)a.w[(kb * 32 + 8 * g4 + j) * PC + cb * 16 + r];
+    // (RP) W fragments of the pointwise conv as dwpw_fwd_kernel holds them (A operand: row = co, k = ci): element j =
+    // W[co = cb*16 + r][ci = kb*32 + 8 g4 + j]
+    bf16x8 wp[RP ? 4 : 1][2];
+    if constexpr (RP) {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) wp[cb][kb][j] = (__bf16)a.w[(cb * 16 + r) * PC + kb * 32 + 8 * g4 + j];
+    }
     f32x4 accw[4];
     if constexpr (WG) {
 #pragma unroll
@@ -112,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
             const bool ok = px < nvalid;
             okm |= (ok ? 1u : 0u) << k;
             const size_t pix = ok ? (size_t)(nbase + px) : 0;
-            rp[k] = *reinterpret_cast<const u32x4*>(p16 + pix * a.p_ld + 8 * piece);
+            if constexpr (!RP) rp[k] = *reinterpret_cast<const u32x4*>(p16 + pix * a.p_ld + 8 * piece);
             if constexpr (WG) rd[k] = *reinterpret_cast<const u32x4*>(d16 + pix * a.d_ld + 8 * piece);
             if constexpr (DYB) {
                 ry[k][0] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.dy) + pix * a.dy_ld + 8 * piece);
@@ -123,10 +143,26 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
             }
         }
     };
+    // the arithmetic of bn_bwd_apply_kernel (pointwise.hip) on one element: p, dy and the channel's constants -> dp
+    auto dp_of = [&](float x, float y, float m, float i, float g, float b, float s1, float s2) -> float {
+        const float h = (x - m) * i;
+        const float dv = (h * g + b > 0.f) ? y : 0.f;
+        return a.training ? g * i * (dv - s1 - h * s2) : g * i * dv;
+    };
     long cbase = 0;
-    int cvalid = 0;
-    auto commit = [&]() {                                  // registers -> LDS: dp formed on the way, d copied
-        cbase = nbase; cvalid = nvalid;
+    int cvalid = 0, cg = 0;                                // first pixel / valid pixels / group of the tile in LDS
+    auto commit = [&]() {                                  // registers -> LDS: dp formed on the way (RP: dy copied), d copied
+        cbase = nbase; cvalid = nvalid; cg = ng;
+        if constexpr (RP) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int px = px0 + 32 * k;
+                const u32x4 z = {0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(dys + px * PS + 8 * piece) = ry[k][0];
+                *reinterpret_cast<u32x4*>(ds_ + px * PS + 8 * piece) = (okm >> k) & 1 ? rd[k] : z;
+            }
+            return;
+        }
         float mv[8], iv[8], gv[8], bv[8], s1[8], s2[8];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -159,10 +195,8 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
             }
             bf16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {                  // the arithmetic of bn_bwd_apply_kernel (pointwise.hip)
-                const float h = (xv[e] - mv[e]) * iv[e];
-                const float dv = (h * gv[e] + bv[e] > 0.f) ? yv[e] : 0.f;
-                const float v = a.training ? gv[e] * iv[e] * (dv - s1[e] - h * s2[e]) : gv[e] * iv[e] * dv;
+            for (int e = 0; e < 8; ++e) {
+                const float v = dp_of(xv[e], yv[e], mv[e], iv[e], gv[e], bv[e], s1[e], s2[e]);
                 o[e] = (__bf16)(ok ? v : 0.f);
             }
             *reinterpret_cast<bf16x8*>(dps + px * PS + 8 * piece) = o;
@@ -185,6 +219,42 @@ __global__ __launch_bounds__(256, 2) void pw_bn_bwd_kernel(const PwBwdArgs a) {
         commit();
         __syncthreads();
         if (tile + (int)gridDim.x < a.ntiles) fetch(tile + gridDim.x);
+        if constexpr (RP) {
+            // ---- p of this wave's 32 pixels as dwpw_fwd_kernel formed it (B operand: the pixel's 64 channels of d; per
+            // accumulator kb = 0, then kb = 1; one rounding to bf16), and dp from it: lane (r, g4) holds channels
+            // cb*16 + 4 g4 .. + 3 of pixel 32 wave + 16 pb + r.  (The two pixel blocks one after the other: unrolled, the 2 x 96
+            // constants and both blocks' MFMAs are in flight at once and the prefetched tile goes to scratch.)
+#pragma unroll 1
+            for (int pb = 0; pb < 2; ++pb) {
+                const int px = 32 * wave + 16 * pb + r;
+                const bool ok = px < cvalid;
+                const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(ds_ + px * PS + 8 * g4);
+                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(ds_ + px * PS + 32 + 8 * g4);
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    f32x4 pa = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp[cb][0], b0, pa, 0, 0, 0);
+                    pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp[cb][1], b1, pa, 0, 0, 0);
+                    const int c0 = cb * 16 + 4 * g4;
+                    const float4 mv = *reinterpret_cast<const float4*>(&cst[cg][0][c0]);
+                    const float4 iv = *reinterpret_cast<const float4*>(&cst[cg][1][c0]);
+                    const float4 gv = *reinterpret_cast<const float4*>(&cst[cg][2][c0]);
+                    const float4 bv = *reinterpret_cast<const float4*>(&cst[cg][3][c0]);
+                    const float4 s1 = *reinterpret_cast<const float4*>(&cst[cg][4][c0]);
+                    const float4 s2 = *reinterpret_cast<const float4*>(&cst[cg][5][c0]);
+                    const uint2 yy = *reinterpret_cast<const uint2*>(dys + px * PS + c0);
+                    const bf16x4 pr = {(__bf16)pa[0], (__bf16)pa[1], (__bf16)pa[2], (__bf16)pa[3]};
+                    const float v0 = dp_of((float)pr[0], blo(yy.x), mv.x, iv.x, gv.x, bv.x, s1.x, s2.x);
+                    const float v1 = dp_of((float)pr[1], bhi(yy.x), mv.y, iv.y, gv.y, bv.y, s1.y, s2.y);
+                    const float v2 = dp_of((float)pr[2], blo(yy.y), mv.z, iv.z, gv.z, bv.z, s1.z, s2.z);
+                    const float v3 = dp_of((float)pr[3], bhi(yy.y), mv.w, iv.w, gv.w, bv.w, s1.w, s2.w);
+                    *reinterpret_cast<bf16x4*>(dps + px * PS + c0) =
+                        (bf16x4){(__bf16)(ok ? v0 : 0.f), (__bf16)(ok ? v1 : 0.f), (__bf16)(ok ? v2 : 0.f), (__bf16)(ok ? v3 : 0.f)};
+                    if (cb & 1) __builtin_amdgcn_sched_barrier(0);   // (two channel blocks' constants at a time: registers)
+                }
+            }
+            __syncthreads();                                // dp of every wave's pixels is in LDS
+        }
         // ---- input gradient of this wave's 32 pixels: dd[ci][px] = sum_co W^T[ci][co] dp[co][px]
         f32x4 acc[4][2];
 #pragma unroll
@@ -284,9 +354,13 @@ static int pw_bn_backward_impl(const float* dy, int dy_ld, int dy_bf16, const fl
     PwBwdArgs a{dy, dy_ld, reinterpret_cast<const __bf16*>(p), p_ld, reinterpret_cast<const __bf16*>(d), d_ld, mean, invstd, gamma,
                 beta, sums, weight, reinterpret_cast<__bf16*>(dd), dd_ld, workspace, group_pix, G, training, tpg, (int)ntiles,
                 1.f / (float)group_pix, dsums, count};
-    with_bools([&](auto DB, auto WG) {
-        hipLaunchKernelGGL((pw_bn_bwd_kernel<DB(), WG()>), dim3(nsplit), dim3(256), 0, s, a);
-    }, dy_bf16, wg);
+    // (the recompute form exists for bf16 dy with the weight gradient only: every other call reads p)
+    const bool rp = (flags & NVQ_PW_RECOMPUTE) && wg && dy_bf16;
+    rc = with_consts("pw_bn_backward", [&](auto FORM) {
+        constexpr int f = FORM();
+        hipLaunchKernelGGL((pw_bn_bwd_kernel<(f & 1) != 0, (f & 2) != 0, (f & 4) != 0>), dim3(nsplit), dim3(256), 0, s, a);
+    }, one_of<0, 1, 2, 3, 7>((dy_bf16 ? 1 : 0) | (wg ? 2 : 0) | (rp ? 4 : 0)));
+    if (rc) return rc;
     rc = check_launch("pw_bn_backward");
     if (rc || !wg) return rc;
     return launch_wgrad_reduce(workspace, nsplit, 2, 2, 1, PC, PC, 1.f, 0, dweight, s);
@@ -306,7 +380,7 @@ extern "C" int nvq_pw_bn_backward_ex(const float* dy, int dy_ld, int dy_bf16, co
                                      const float* gamma, const float* beta, int training, const float* weight, float* dd,
                                      int dd_ld, float* dgamma, float* dbeta, float* dweight, const float* sums_in,
                                      float* workspace, size_t workspace_bytes, int flags, void* stream) {
-    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "pw_bn_backward_ex: flags %d", flags);
+    NVQ_REQUIRE((flags & ~(NVQ_NO_WGRAD | NVQ_PW_RECOMPUTE)) == 0, "pw_bn_backward_ex: flags %d", flags);
     return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, training,
                                weight, dd, dd_ld, dgamma, dbeta, dweight, sums_in, workspace, workspace_bytes, flags, stream);
 }
@@ -318,7 +392,7 @@ extern "C" int nvq_pw_bn_backward_finish(const float* dy, int dy_ld, int dy_bf16
                                          const float* gamma, const float* beta, const float* weight, float* dd, int dd_ld,
                                          float* dweight, const double* sums, const double* count, float* workspace,
                                          size_t workspace_bytes, int flags, void* stream) {
-    NVQ_REQUIRE((flags & ~NVQ_NO_WGRAD) == 0, "pw_bn_backward_finish: flags %d", flags);
+    NVQ_REQUIRE((flags & ~(NVQ_NO_WGRAD | NVQ_PW_RECOMPUTE)) == 0, "pw_bn_backward_finish: flags %d", flags);
     NVQ_REQUIRE(sums && count, "pw_bn_backward_finish: sums / count");
     return pw_bn_backward_impl(dy, dy_ld, dy_bf16, p, p_ld, d, d_ld, N, group_images, H, W, mean, invstd, gamma, beta, 1, weight,
                                dd, dd_ld, nullptr, nullptr, dweight, nullptr, workspace, workspace_bytes, flags, stream, sums,

@@ -12,13 +12,15 @@
 // algorithmic bytes issued, of which the dy rows two consecutive units share are L2 hits.
 //
 // One persistent workgroup per CU (XCD-ordered tiles, two units per 4 x 32 tile), eight waves, one s_barrier per unit:
-//   * every wave holds accumulators: the 9 taps x 2 groups of CB 32-channel blocks are 18 (group, tap) jobs of CB accumulator
-//     blocks (M = ci, N = co, K = 16 pixels of a unit row; both operands transposed out of [pixel][channel] LDS images by
-//     ds_read_b64_tr_b16).  Waves w and w + 4 share a SIMD: six waves take two jobs, waves 2 and 3 three (12 / 12 / 15 / 15 jobs
-//     per SIMD).  The fragments of K step k + 1 are read under the MFMAs of step k - across units too: the barrier that hands
-//     unit u + 1 over sits in front of unit u's last MFMA batch;
-//   * ALL eight waves stage x (three 16-byte loads and three LDS stores per wave and unit), the six two-job waves also dy (with
-//     its halo; they sum it for the bias gradient, fp32, from the staged values): two units ahead in two register sets, unit
+//   * the NCI 32-channel blocks x 9 taps are 9 NCI accumulator blocks (M = ci, N = co, K = 16 pixels of a unit row; both
+//     operands transposed out of [pixel][channel] LDS images by ds_read_b64_tr_b16).  A wave owns a rectangle of blocks x taps
+//     (at most 9 = 144 accumulator registers), so an x fragment serves all its taps and a dy fragment all its blocks, and it
+//     multiplies no block it does not own.  The rectangles come from a table (wm_job): two block groups x four tap groups,
+//     paired on the SIMDs (waves w and w + 4 share one) as 6 / 6 / 8 / 7 accumulator blocks for NCI = 3, 8 / 8 / 10 / 10 for 4,
+//     10 / 10 / 13 / 12 for 5, 12 / 12 / 15 / 15 for 6.  The fragments of K step k + 1 are read under the MFMAs of step k -
+//     across units too: the barrier that hands unit u + 1 over sits in front of unit u's last MFMA batch;
+//   * ALL eight waves stage x (three 16-byte loads and three LDS stores per wave and unit), all but waves 2 and 3 also dy
+//     (with its halo; they sum it for the bias gradient, fp32, from the staged values): two units ahead in two register sets, unit
 //     u + 2 stored into the slot unit u was read from right behind barrier u + 1's last MFMA batch, then the loads of unit u + 4.
 // Loads are inline asm (uniform base + per-lane offset: one instruction) with counted s_waitcnt vmcnt by hand: with register
 // sets that rotate over loop iterations the compiler's own bookkeeping drains vmcnt(0) in front of every store pass.
@@ -75,12 +77,66 @@ __device__ __forceinline__ void hold(u32x4& r) { asm volatile("" : "+v"(r)); }  
 
 template <int NCI>
 struct WmCfg {
-    static constexpr int CB = (NCI + 1) / 2;                            // 32-channel blocks per wave (two block groups)
     static constexpr int UBYTES = WM_UPX * NCI * 64;                    // x bytes of a unit
     static constexpr int XPIECES = WM_UPX * NCI * 4;                    // its 16-byte pieces ...
     static constexpr int XPT = (XPIECES + WM_NTHR - 1) / WM_NTHR;       // ... per thread (ALL eight waves stage x)
     static constexpr int LDS = 2 * UBYTES + 2 * WM_YBYTES;
 };
+
+// The MFMA job of a wave: accumulators for the blocks [b0, b0 + nb) x the taps [t0, t0 + nt).  The blocks form two groups,
+// [0, CB) and [CB, NCI) with CB = ceil(NCI / 2), and each group's nine taps go to four waves as 2 / 2 / 2 / 3.  Waves w and
+// w + 4 share a SIMD, and the three-tap waves of the two groups sit on different SIMDs next to a two-tap wave.
+//   even NCI: the three-tap waves are 2 and 3, the ones that stage no dy ((3 blocks) x (3 taps) = 144 accumulator registers
+//             and the dy staging registers do not fit without scratch): blocks per SIMD 4 + 4, 4 + 4, 6 + 4, 6 + 4 halves of NCI
+//             (NCI = 6: 12 / 12 / 15 / 15);
+//   odd NCI:  group 1 is a block short, so its three-tap wave (7) can stage dy, and every SIMD holds one wave of either
+//             group: NCI = 3: 6 / 6 / 8 / 7 accumulator blocks per SIMD, NCI = 5: 10 / 10 / 13 / 12.
+// Flatter tables (7 / 7 / 7 / 6, 9 / 9 / 9 / 9, 12 / 12 / 11 / 10 from one-block and one-tap rectangles) were slower: a 2 x 2
+// rectangle reads one LDS fragment per MFMA, a 1 x 5, 1 x 3 or 2 x 1 one 1.2 - 1.5 (profiles/backward_unneeded_work.txt).
+struct WmJob { int b0, nb, t0, nt; };
+template <int NCI>
+constexpr WmJob wm_job(int w) {
+    constexpr int CB = (NCI + 1) / 2, RB = NCI - CB;
+    if constexpr (NCI & 1) {
+        constexpr WmJob t[8] = {{0, CB, 0, 2}, {0, CB, 2, 2}, {0, CB, 6, 3}, {0, CB, 4, 2}, {CB, RB, 0, 2}, {CB, RB, 2, 2}, {CB, RB, 4, 2}, {CB, RB, 6, 3}};
+        return t[w];
+    } else {
+        constexpr WmJob t[8] = {{0, CB, 0, 2}, {0, CB, 2, 2}, {0, CB, 6, 3}, {CB, RB, 6, 3}, {CB, RB, 0, 2}, {CB, RB, 2, 2}, {0, CB, 4, 2}, {CB, RB, 4, 2}};
+        return t[w];
+    }
+}
+constexpr bool wm_stages_dy(int w) { return w != 2 && w != 3; }
+// every (block, tap) in exactly one wave, at most 9 accumulator blocks per wave
+template <int NCI>
+constexpr bool wm_table_ok() {
+    int seen[6 * 9] = {};
+    for (int w = 0; w < 8; ++w) {
+        const WmJob j = wm_job<NCI>(w);
+        if (j.nb * j.nt > 9 || j.nb < 1 || j.nt < 1) return false;
+        if (j.b0 < 0 || j.b0 + j.nb > NCI || j.t0 < 0 || j.t0 + j.nt > 9) return false;
+        for (int b = j.b0; b < j.b0 + j.nb; ++b)
+            for (int t = j.t0; t < j.t0 + j.nt; ++t) ++seen[b * 9 + t];
+    }
+    for (int k = 0; k < NCI * 9; ++k)
+        if (seen[k] != 1) return false;
+    return true;
+}
+// is wave w the first of the table with its role (block count, tap count, dy staging)?  One role = one copy of the K loop.
+template <int NCI>
+constexpr bool wm_first_of_role(int w) {
+    const WmJob j = wm_job<NCI>(w);
+    for (int v = 0; v < w; ++v) {
+        const WmJob i = wm_job<NCI>(v);
+        if (i.nb == j.nb && i.nt == j.nt && wm_stages_dy(v) == wm_stages_dy(w)) return false;
+    }
+    return true;
+}
+template <class F>
+__device__ __forceinline__ void wm_each_wave(F&& f) {
+    f(std::integral_constant<int, 0>{}); f(std::integral_constant<int, 1>{}); f(std::integral_constant<int, 2>{});
+    f(std::integral_constant<int, 3>{}); f(std::integral_constant<int, 4>{}); f(std::integral_constant<int, 5>{});
+    f(std::integral_constant<int, 6>{}); f(std::integral_constant<int, 7>{});
+}
 
 }  // namespace
 
@@ -88,7 +144,8 @@ struct WmCfg {
 template <int NCI>
 __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_desc d, int tilesX, int tilesY, int ntiles) {
     using C = WmCfg<NCI>;
-    constexpr int CB = C::CB, XPT = C::XPT;
+    constexpr int XPT = C::XPT;
+    static_assert(wm_table_ok<NCI>(), "job table");
     static_assert(C::LDS <= 160 * 1024 && C::LDS >= WM_DYT * 32 && NCI >= 2 && NCI <= 6, "configuration");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[C::LDS];
     constexpr int YOFF = 2 * C::UBYTES;
@@ -104,25 +161,22 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
     const __bf16* dy16 = reinterpret_cast<const __bf16*>(d.dy);
     const int LU = d.x_ld >> 5;                               // 32-channel blocks of the leading tensor
 
-    // ---- roles.  The 9 taps x 2 block groups are 18 (group, tap) jobs of CB accumulator blocks each.  Waves w and w + 4 share
-    // a SIMD: waves 0, 1, 4, 5 (two MFMA waves per SIMD) and 6, 7 take two jobs, waves 2, 3 (next to 6, 7) three:
-    //   group 0 (blocks [0, CB)):   wave 0: taps 0, 1   wave 1: 2, 3   wave 6: 4, 5   wave 2: 6, 7, 8
-    //   group 1 (blocks [CB, NCI)): wave 4: taps 0, 1   wave 5: 2, 3   wave 7: 4, 5   wave 3: 6, 7, 8
-    // = 12 / 12 / 15 / 15 jobs' worth of MFMAs per SIMD instead of the 18 / 18 / 9 / 9 of six equal MFMA waves.  The six
-    // two-job waves also stage dy (with its halo) and sum it for the bias gradient; all eight stage x.
-    const bool three = wave == 2 || wave == 3;
-    const int grp = (wave == 0 || wave == 1 || wave == 2 || wave == 6) ? 0 : 1;
-    const int tap0 = three ? 6 : (wave == 6 || wave == 7) ? 4 : 2 * (wave & 1);
-    const int dyw = wave < 2 ? wave : (wave < 6 ? wave - 2 : wave - 2);     // index among the dy-staging waves (waves 2, 3: unused)
-    const int cb0 = grp * CB;
-    const int ncb = NCI - cb0 < CB ? NCI - cb0 : CB;
+    // ---- roles.  The MFMA job of this wave (blocks [cb0, cb0 + ncb) x taps [tap0, tap0 + ntap)) comes from the table of this
+    // NCI (wm_job).  The staging roles are bound to the wave index whatever the table says: all eight waves stage x, all but
+    // waves 2 and 3 also dy (with its halo), which they sum for the bias gradient.
+    const bool stages_dy = wm_stages_dy(wave);
+    int cb0 = 0, ncb = 0, tap0 = 0, ntap = 0;                 // (wave-uniform)
+    wm_each_wave([&](auto wtag) {
+        constexpr WmJob J = wm_job<NCI>(decltype(wtag)::value);
+        if (wave == decltype(wtag)::value) { cb0 = J.b0; ncb = J.nb; tap0 = J.t0; ntap = J.nt; }
+    });
 
     // ---- x staging, by every wave: piece j = tid + 512 k of a unit image [block][64 px][4 pieces] -> block (tid >> 8) + 2 k
     // (wave-uniform), unit row (tid >> 7) & 1 (wave-uniform), column (tid >> 2) & 31, piece tid & 3; its LDS address is linear
     // in j.  A load is one instruction: uniform base + one of two per-lane byte offsets.
     const int xcol = (tid >> 2) & 31, xsub = tid & 3, xrow = (wave >> 1) & 1, xblk0 = wave >> 2;   // (row, block: from the SGPR)
     const unsigned v_lead = (unsigned)((xcol * d.x_ld + 8 * xsub) * 2), v_plane = (unsigned)((xcol * 32 + 8 * xsub) * 2);
-    // dy staging, by the six two-job waves: piece j = dt + 384 k (k < 2) of the unit's [4 x 34 halo pixels][4 pieces]
+    // dy staging, by six waves: piece j = dt + 384 k (k < 2) of the unit's [4 x 34 halo pixels][4 pieces]
     const int dt = (wave < 2 ? wave : wave - 2) * 64 + lane;  // 0 .. 383 (waves 2, 3 never use it)
     struct Set { u32x4 x[XPT]; u32x4 y[2]; bool xok; unsigned char yok; };
     // Units are loaded in order; the tile of the next one is kept decoded: consecutive tiles of a workgroup are G / 8 apart in the
@@ -151,10 +205,10 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
     auto stamp = [&]() {};
 #endif
 
-    // One role = one instantiation: NT taps per wave, DY: the wave stages dy.  (Separate top-level branches: accumulators that
-    // are live across two copies of a loop in ONE branch make the register allocator spill.)
-    auto role = [&](auto nt_tag, auto dy_tag) {
-        constexpr int NT = decltype(nt_tag)::value;
+    // One role = one instantiation: NB blocks x NT taps per wave, DY: the wave stages dy.  (Separate top-level branches:
+    // accumulators that are live across two copies of a loop in ONE branch make the register allocator spill.)
+    auto role = [&](auto nb_tag, auto nt_tag, auto dy_tag) {
+        constexpr int NB = decltype(nb_tag)::value, NT = decltype(nt_tag)::value;
         constexpr bool DY = decltype(dy_tag)::value;
         constexpr int S = XPT + (DY ? 2 : 0);                 // loads per unit and thread (always exactly S: counted waits)
         // dy pieces of this thread: halo pixel hp (row hr, column hc), 16-byte piece dt & 3
@@ -246,19 +300,18 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
         };
         // ---- MFMA side.  A transposing read: lane (r = (q, p), hb) supplies the address of image row pix + q, columns 4p ..
         // 4p+3 of a 16-channel block and receives channel r of that block for pixels pix .. pix + 3; two reads (pix, pix + 4) =
-        // the 8 k values 8h .. 8h + 7 of an operand.  A wave of group 1 may own fewer than CB blocks (NCI = 3, 5): it runs the
-        // MFMAs of a phantom block on block 0's fragments and never writes that accumulator - the K loop stays free of branches.
+        // the 8 k values 8h .. 8h + 7 of an operand.  NB and NT are the role's own: every MFMA of the branch-free K loop feeds
+        // an accumulator that is stored.
         const int r = lane & 15, hb = (lane >> 4) & 1, h = lane >> 5;
         const int q = r >> 2, p = r & 3;
-        f32x16 acc[CB * NT];
+        f32x16 acc[NB * NT];
 #pragma unroll
-        for (int a = 0; a < CB * NT; ++a)
+        for (int a = 0; a < NB * NT; ++a)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
-        unsigned abase[CB], bbase[NT];
+        unsigned abase[NB], bbase[NT];
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-            abase[cb] = (unsigned)((cb < ncb ? cb0 + cb : 0) * (WM_UPX * 64) + (8 * h + q) * 64 + hb * 32 + 8 * p);
+        for (int cb = 0; cb < NB; ++cb) abase[cb] = (unsigned)((cb0 + cb) * (WM_UPX * 64) + (8 * h + q) * 64 + hb * 32 + 8 * p);
 #pragma unroll
         for (int j = 0; j < NT; ++j) {                        // dy pixel of x pixel (row, c) under tap (ky, kx): (row + 2 - ky, c + 2 - kx)
             const int t = tap0 + j, ky = t / 3, kx = t - 3 * ky;
@@ -273,12 +326,12 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
         // step k (pinned: the scheduler otherwise sinks every read to its first use) - ACROSS units too: the barrier that hands
         // unit u + 1 over sits in front of the last step's MFMAs of unit u, whose fragments are in registers by then (every read
         // of unit u has been waited for), and the first fragments of unit u + 1 are read under those MFMAs.
-        bf16x8 a[2][CB], b[2][NT];
+        bf16x8 a[2][NB], b[2][NT];
         auto load_step = [&](int u, int k, int buf) {
             const unsigned char* xs = lds + (u & 1) * C::UBYTES + ((k >> 1) * TW + 16 * (k & 1)) * 64;
             const unsigned char* ys = lds + (u & 1) * WM_YBYTES + ((k >> 1) * WM_HW + 16 * (k & 1)) * 64;
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) a[buf][cb] = tr2(xs + abase[cb]);
+            for (int cb = 0; cb < NB; ++cb) a[buf][cb] = tr2(xs + abase[cb]);
 #pragma unroll
             for (int j = 0; j < NT; ++j) b[buf][j] = tr2(ys + bbase[j]);
         };
@@ -299,7 +352,7 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
 #pragma unroll
-                    for (int cb = 0; cb < CB; ++cb)
+                    for (int cb = 0; cb < NB; ++cb)
                         acc[cb * NT + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][cb], b[cur][j], acc[cb * NT + j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -338,8 +391,7 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
         // ---- partial slabs [split][ci block][tap][ci 32][co 32] (the layout wgrad_reduce_kernel sums)
         // D[m][n]: n = co = lane & 31, m = ci = (e & 3) + 8 (e >> 2) + 4 h
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) {
-            if (cb >= ncb) continue;
+        for (int cb = 0; cb < NB; ++cb) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 float* part = d.workspace + ((size_t)(blockIdx.x * NCI + cb0 + cb) * 9 + tap0 + j) * (WG_C * WG_C);
@@ -349,14 +401,20 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
             }
         }
     };
-    if (three) role(std::integral_constant<int, 3>{}, std::false_type{});
-    else role(std::integral_constant<int, 2>{}, std::true_type{});
+    wm_each_wave([&](auto wtag) {                             // one branch per role of the table, taken by the waves that have it
+        constexpr int w = decltype(wtag)::value;
+        constexpr WmJob J = wm_job<NCI>(w);
+        if constexpr (wm_first_of_role<NCI>(w)) {
+            if (ncb == J.nb && ntap == J.nt && stages_dy == wm_stages_dy(w))
+                role(std::integral_constant<int, J.nb>{}, std::integral_constant<int, J.nt>{}, std::bool_constant<wm_stages_dy(w)>{});
+        }
+    });
 
     // ---- bias partials bias_part[split][32]: the dy-staging threads' sums (thread dt: channels 8 (dt & 3) .. + 7) meet in LDS
     if (d.dbias != nullptr) {                                 // (uniform)
         float* scratch = reinterpret_cast<float*>(lds);       // [384][8]
         __syncthreads();                                      // every wave is done with the LDS images
-        if (!three) {
+        if (stages_dy) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) scratch[8 * dt + e] = bsum[e];
         }
@@ -369,7 +427,6 @@ __global__ __launch_bounds__(WM_NTHR, 2) void wgrad_m32_kernel(const nvq_wgrad_d
             bp[(size_t)blockIdx.x * WG_C + tid] = sum;
         }
     }
-    (void)dyw;
 }
 
 // ---------------------------------------------------------------- 1x1 (the blocks' local feature fusion, lff)

@@ -165,6 +165,7 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
     sv.dw_in = []                     # (tensor, bn) the depthwise conv of layer k was fed with
     fuse_bn = K.dwconv_bn_fusable(feat0, F)
     fused_fwd = fuse_bn and F == 64 and math == K.MATH_BF16 and os.environ.get("NVQ_FUSED_DWPW", "1") != "0"
+    sv.pw_from_dwpw = fused_fwd       # every layer's p is dwpw_forward's bf16(d W^T): the backward may form it again from d
     for k in range(3):
         pre = f"feature_extractor.body.{k}."
         d = _new(dev, NI, H, W, F, dtype=act_dtype)
@@ -833,6 +834,9 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
         dd = _new(dev, NI, H, W, F, dtype=act_dtype)
         fused_bwd = (math == K.MATH_BF16 and act_dtype == torch.bfloat16 and F == 64 and sv.pws[k].dtype == torch.bfloat16
                      and sv.dws[k].dtype == torch.bfloat16)
+        # the pass behind the BatchNorm sums forms p again from the d tile it stages anyway (one tensor pass fewer, the
+        # same bits) when the forward made p from this d and this weight in the fused pass
+        recompute = fused_bwd and getattr(sv, "pw_from_dwpw", False) and os.environ.get("NVQ_PW_RECOMPUTE", "1") != "0"
         if bn_sync[k] is not None:
             # synchronised BatchNorm: {sum g, sum g xhat} of every rank, dx from the global sums and the forward's global count
             grp, st = bn_sync[k]
@@ -844,7 +848,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
                 _allreduce_sum_(bsums, grp)
                 K.pw_bn_backward_finish(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
                                         P[pre + "bn.bias"], P[pre + "pointwise.weight"], dd, G.get(pre + "pointwise.weight"), bsums,
-                                        cnt, ws)
+                                        cnt, ws, recompute=recompute)
             else:
                 dp = _new(dev, NI, H, W, F, dtype=act_dtype)
                 K.bn_relu_backward_reduce(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
@@ -860,7 +864,7 @@ def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinte
             dgam, dbet = bn_targets if bn_sums is not None else (G.get(pre + "bn.weight"), G.get(pre + "bn.bias"))
             K.pw_bn_backward(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
                              P[pre + "bn.bias"], sv.training, P[pre + "pointwise.weight"], dd, dgam, dbet,
-                             G.get(pre + "pointwise.weight"), ws, sums_in=bn_sums)
+                             G.get(pre + "pointwise.weight"), ws, sums_in=bn_sums, recompute=recompute)
             bn_sums = None
         else:
             dp = _new(dev, NI, H, W, F, dtype=act_dtype)

@@ -848,24 +848,29 @@ def dwpw_forward(x: torch.Tensor, bn, dw_weight: torch.Tensor, pw_weight: torch.
 
 
 def pw_bn_backward(dy: torch.Tensor, p: torch.Tensor, d: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
-                   training: bool, weight: torch.Tensor, dd: torch.Tensor, dgamma, dbeta, dweight, ws, sums_in=None) -> None:
+                   training: bool, weight: torch.Tensor, dd: torch.Tensor, dgamma, dbeta, dweight, ws, sums_in=None,
+                   recompute: bool = False) -> None:
     """Backward of pointwise conv -> BatchNorm -> ReLU in one pass (bf16 mode, 64 channels): see nvq_pw_bn_backward.
     dweight None (a frozen pointwise weight) and / or dgamma, dbeta None (a frozen BatchNorm affine): nvq_pw_bn_backward_ex,
-    dd is the same either way."""
+    dd is the same either way.  recompute: p is dwpw_forward's output on this d and this weight (NVQ_PW_RECOMPUTE) - the
+    pass behind the BatchNorm sums forms it again from d instead of reading it (the library does so with a bf16 dy and a
+    weight gradient; any other call reads p)."""
     N, H, W, _ = p.shape
     assert p.dtype == d.dtype == dd.dtype == torch.bfloat16 and tuple(weight.shape[:2]) == (64, 64)
     ev0 = TIMER.start() if TIMER is not None else None
     args = (ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], ptr(d), d.shape[-1], N, group_images, H, W, ptr(mean),
             ptr(invstd), ptr(gamma), ptr(beta), int(training), ptr(weight.contiguous()), ptr(dd), dd.shape[-1], ptr(dgamma),
             ptr(dbeta), ptr(dweight), ptr(sums_in), ptr(ws), ws.numel() * 4)
-    if dweight is None or dgamma is None or dbeta is None:
-        check(lib().nvq_pw_bn_backward_ex(*args, NO_WGRAD if dweight is None else 0, stream()), "nvq_pw_bn_backward_ex")
+    if dweight is None or dgamma is None or dbeta is None or recompute:
+        flags = (NO_WGRAD if dweight is None else 0) | (PW_RECOMPUTE if recompute else 0)
+        check(lib().nvq_pw_bn_backward_ex(*args, flags, stream()), "nvq_pw_bn_backward_ex")
     else:
         check(lib().nvq_pw_bn_backward(*args, stream()), "nvq_pw_bn_backward")
     if ev0 is not None:
         npx = N * H * W
         TIMER.stop(ev0, "pw_bn_bwd_kernel", 2.0 * npx * 64 * 64 * 2,
-                   npx * 64 * (2.0 * 2 + (2 if is_bf16(dy) else 4) * 2 + 2), f"n{N} 64->64 {'h' if is_bf16(dy) else 'f'}")
+                   npx * 64 * (2.0 * (1 if recompute and dweight is not None and is_bf16(dy) else 2)
+                               + (2 if is_bf16(dy) else 4) * 2 + 2), f"n{N} 64->64 {'h' if is_bf16(dy) else 'f'}")
 
 
 # ----------------------------------------------------------------------------- synchronised BatchNorm (reduce / finish)
@@ -931,13 +936,16 @@ def pw_bn_backward_reduce(dy: torch.Tensor, p: torch.Tensor, group_images: int, 
 
 
 def pw_bn_backward_finish(dy: torch.Tensor, p: torch.Tensor, d: torch.Tensor, group_images: int, mean, invstd, gamma, beta,
-                          weight: torch.Tensor, dd: torch.Tensor, dweight, sums: torch.Tensor, count: torch.Tensor, ws) -> None:
+                          weight: torch.Tensor, dd: torch.Tensor, dweight, sums: torch.Tensor, count: torch.Tensor, ws,
+                          recompute: bool = False) -> None:
+    """recompute: as in pw_bn_backward"""
     N, H, W, _ = p.shape
     assert p.dtype == d.dtype == dd.dtype == torch.bfloat16 and tuple(weight.shape[:2]) == (64, 64)
     check(lib().nvq_pw_bn_backward_finish(ptr(dy), dy.shape[-1], is_bf16(dy), ptr(p), p.shape[-1], ptr(d), d.shape[-1], N,
                                           group_images, H, W, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
                                           ptr(weight.contiguous()), ptr(dd), dd.shape[-1], ptr(dweight), ptr(sums), ptr(count),
-                                          ptr(ws), ws.numel() * 4, NO_WGRAD if dweight is None else 0, stream()),
+                                          ptr(ws), ws.numel() * 4,
+                                          (NO_WGRAD if dweight is None else 0) | (PW_RECOMPUTE if recompute else 0), stream()),
           "nvq_pw_bn_backward_finish")
 
 
@@ -979,6 +987,7 @@ def warp_forward(feat: Sl, flow: torch.Tensor, out: Sl):
 
 WARP_DETERMINISTIC = 1
 NO_WGRAD = 2        # NVQ_NO_WGRAD: the _ex entry points' input gradient without the weight gradient
+PW_RECOMPUTE = 4    # NVQ_PW_RECOMPUTE: nvq_pw_bn_backward_ex / _finish form p again from d instead of reading it
 
 
 def warp_backward(dout: Sl, feat: Sl, flow: torch.Tensor, dfeat: Sl, dflow: torch.Tensor, gather: bool = True,

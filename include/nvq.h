@@ -200,9 +200,14 @@ int nvq_pw_bn_backward(const float* dy, int dy_ld, int dy_bf16, const float* p, 
  * product (a frozen layer).  The input gradient is bit-identical to the full form's; the weight-gradient outputs are neither
  * written nor read and may be NULL. */
 #define NVQ_NO_WGRAD 2
+/* "p is the output of nvq_dwpw_forward on this d and this weight" (nvq_pw_bn_backward_ex / _finish): the pass behind the
+ * BatchNorm sums then forms p = bf16(d W^T) again from the d tile it stages anyway, bit for bit what is stored, instead of
+ * reading it - one tensor pass fewer, every output bit-identical.  Honoured with a bf16 dy and without NVQ_NO_WGRAD; any
+ * other call reads p as before.  The BatchNorm sums (sums_in == NULL) are still taken from the stored p. */
+#define NVQ_PW_RECOMPUTE 4
 /* nvq_pw_bn_backward with a flags word.  flags == 0: exactly nvq_pw_bn_backward.  NVQ_NO_WGRAD: dd alone - d is not read,
  * dweight is not written (may be NULL), no reduce launch.  dgamma / dbeta may be NULL (a frozen BatchNorm affine, with or without
- * the flag): the sums dd needs are still formed. */
+ * the flag): the sums dd needs are still formed.  NVQ_PW_RECOMPUTE: see above. */
 int nvq_pw_bn_backward_ex(const float* dy, int dy_ld, int dy_bf16, const float* p, int p_ld, const float* d, int d_ld,
                           int N, int group_images, int H, int W, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, int training, const float* weight, float* dd, int dd_ld,
