@@ -258,6 +258,9 @@ SIGNATURES = {
     "nvq_fed_update_gram": (ci, [vp, cl, ci, vp, cl, vp, vp, sz, vp]),
     "nvq_cluster_gram_kmeans": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
     "nvq_fed_aggregate_clusters": (ci, [vp, cl, ci, vp, ci, vp, cl, vp, vp, cf, cf, cf, cl, cl, cl, vp, cl, vp]),
+    # Byzantine-robust aggregation: trimmed mean / median, Krum selection (csrc/robust.hip)
+    "nvq_fed_trimmed_aggregate": (ci, [vp, cl, ci, vp, vp, ci, cf, cf, cl, cl, cl, vp, vp]),
+    "nvq_fed_krum_select": (ci, [vp, ci, vp, ci, ci, vp, vp, vp, vp]),
     # ABR agent: vectorised environment, fused act, GAE, PPO loss (csrc/abr.hip)
     "nvq_abr_env_reset": (ci, [vp, vp, vp, vp, ci, ci, cl, ci, vp]),
     "nvq_abr_env_step": (ci, [vp, vp, vp, _IP, ci, ci, ci, vp, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -1669,6 +1672,35 @@ def fed_aggregate_clusters(clients: torch.Tensor, n: int, labels: torch.Tensor, 
                                            None if bases is None else bases.data_ptr(), base_stride, ptr(weights), ptr(sq),
                                            float(clip_norm), float(server_lr), float(noise_std), int(seed), int(offset), n,
                                            out.data_ptr(), out_stride, stream()), "nvq_fed_aggregate_clusters")
+
+
+# ----------------------------------------------------------------------------- Byzantine-robust aggregation (csrc/robust.hip)
+FED_TRIM_MEDIAN = 64    # NVQ_FED_TRIM_MEDIAN: a trim of (K - 1) / 2 or more is the coordinate-wise median
+
+
+def fed_trimmed_aggregate(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], weights: Optional[torch.Tensor], trim: int,
+                          out: torch.Tensor, *, server_lr: float = 1.0, noise_std: float = 0.0, seed: int = 0,
+                          offset: int = 0) -> None:
+    """out[i] = base[i] + server_lr * (trimmed mean over the live rows of clients[k, i] - base[i]) + noise_std * z_i
+    (nvq_fed_trimmed_aggregate); a row is live when ``weights`` is None or weights[k] > 0; ``out`` may be ``base``"""
+    K, stride = _fed_rows(clients, n)
+    assert weights is None or (weights.dtype == torch.float64 and weights.numel() >= K)
+    assert out.dtype == torch.float32 and out.numel() >= n and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    check(lib().nvq_fed_trimmed_aggregate(clients.data_ptr(), stride, K, ptr(base), ptr(weights), int(trim), float(server_lr),
+                                          float(noise_std), int(seed), int(offset), n, ptr(out), stream()),
+          "nvq_fed_trimmed_aggregate")
+
+
+def fed_krum_select(gram: torch.Tensor, K: int, weights: Optional[torch.Tensor], num_byzantine: int, num_selected: int,
+                    out_weights: torch.Tensor, scores: torch.Tensor, order: torch.Tensor) -> None:
+    """Krum scores, order and 0/1 selection weights from the K x K float64 Gram of the updates (nvq_fed_krum_select); every output
+    stays on the device"""
+    assert gram.dtype == torch.float64 and gram.numel() >= K * K and 1 <= K <= FED_MAX_CLIENTS
+    assert weights is None or (weights.dtype == torch.float64 and weights.numel() >= K)
+    assert out_weights.dtype == torch.float64 and out_weights.numel() >= K and scores.dtype == torch.float64 and scores.numel() >= K
+    assert order.dtype == torch.int32 and order.numel() >= K
+    check(lib().nvq_fed_krum_select(ptr(gram), int(K), ptr(weights), int(num_byzantine), int(num_selected), ptr(out_weights),
+                                    ptr(scores), ptr(order), stream()), "nvq_fed_krum_select")
 
 
 # ----------------------------------------------------------------------------- ABR agent (csrc/abr.hip)

@@ -23,7 +23,9 @@ from nerve_cl._bucket import segments_of
 from nerve_cl.federated import _philox
 from nerve_cl.federated.privacy import DPOptimizer, PrivacyConfig, _Seg
 
-__all__ = ["aggregate_flat", "fedavg", "weighted_average", "FederatedTrainer", "start_server"]
+__all__ = ["aggregate_flat", "fedavg", "weighted_average", "FederatedTrainer", "start_server", "AGGREGATORS"]
+
+AGGREGATORS = ("fedavg", "median", "trimmed_mean", "krum", "multi_krum")
 
 
 # ----------------------------------------------------------------------------------------------- aggregation
@@ -166,7 +168,8 @@ class _Pack:
 
 class FederatedTrainer:
     """``FederatedTrainer(model, num_clients=10, clients_per_round=5, local_epochs=5, *, lr=1e-4, batch_size=16, loss=None,
-    privacy=None, update_clip=None, update_noise=0.0, server_lr=1.0, optimizer_impl="torch", seed=None)``
+    privacy=None, update_clip=None, update_noise=0.0, server_lr=1.0, optimizer_impl="torch", seed=None, aggregator="fedavg",
+    trim_ratio=0.1, num_byzantine=0, num_selected=None, after_client=None)``
 
     ``model(inputs) -> outputs`` is trained on every client's ``(inputs, targets)`` (``set_client_data``) with a fresh
     ``AdamW(lr)`` for ``local_epochs`` passes in batches of ``batch_size``, taken in order; ``loss`` defaults to ``nn.MSELoss()``
@@ -186,6 +189,15 @@ class FederatedTrainer:
     There is no re-clustering: a client whose data arrives after the split round belongs to no cluster, and a round that selects it
     raises ``ValueError``.  A selected client without samples is left out of its cluster's step.  ``load_cluster(c)`` copies a cluster's model into the network, ``load_mean()`` the weighted mean again; the round dict gains ``"clusters"``, the sizes.
 
+    ``aggregator``: ``"fedavg"`` (above), or a Byzantine-robust rule on the same client matrix (``nerve_cl.federated.robust``, DESIGN.md
+    section 28; no ``update_clip``, no clusters): ``"median"`` and ``"trimmed_mean"`` (per coordinate, ``int(trim_ratio * m)`` values
+    dropped from each side, ``m`` the selected clients with samples) are one ``nvq_fed_trimmed_aggregate`` per matrix; ``"krum"`` and
+    ``"multi_krum"`` select 1 or ``num_selected`` (default ``m - num_byzantine``) clients by the Gram matrix of their whole updates and
+    average those, and the round dict gains ``"selected_weights"`` (1.0 per chosen client, in the order of ``last_selected``).  A
+    client without samples is never read by these rules, and integer buffers take the mean over the Krum selection, else the
+    sample-weighted one.  ``after_client(client_id, model)`` is called under ``no_grad`` after a client's local training and before
+    its weights are copied into its row: the hook with which a script or a test inspects or poisons a client.
+
     On the GPU the weights of every HIP-backed network inside ``model`` are one flat buffer: the clients' results are the rows of a
     persistent ``[clients_per_round, n]`` matrix and a round ends with one ``nvq_fed_delta_norms`` (only with ``update_clip``) and
     one ``nvq_fed_aggregate`` writing into ``flat_theta()``.  Everything else in the state dict (BatchNorm statistics, loose
@@ -196,7 +208,9 @@ class FederatedTrainer:
     def __init__(self, model: nn.Module, num_clients: int = 10, clients_per_round: int = 5, local_epochs: int = 5, *,
                  lr: float = 1e-4, batch_size: int = 16, loss=None, privacy: Optional[PrivacyConfig] = None,
                  update_clip: Optional[float] = None, update_noise: float = 0.0, server_lr: float = 1.0,
-                 optimizer_impl: str = "torch", seed: Optional[int] = None, num_clusters: int = 1, cluster_after: int = 0):
+                 optimizer_impl: str = "torch", seed: Optional[int] = None, num_clusters: int = 1, cluster_after: int = 0,
+                 aggregator: str = "fedavg", trim_ratio: float = 0.1, num_byzantine: int = 0, num_selected: Optional[int] = None,
+                 after_client=None):
         if not 1 <= num_clusters <= _nvq.CLUSTER_MAX:
             raise ValueError(f"num_clusters: 1 .. {_nvq.CLUSTER_MAX}")
         if cluster_after < 0:
@@ -207,6 +221,19 @@ class FederatedTrainer:
             raise NotImplementedError("update_clip with num_clusters > 1: per-cluster bases have no single update norm")
         if optimizer_impl not in ("torch", "bucket"):
             raise ValueError(f"optimizer_impl {optimizer_impl!r}: 'torch' or 'bucket'")
+        if aggregator not in AGGREGATORS:
+            raise ValueError(f"aggregator {aggregator!r}: one of {', '.join(AGGREGATORS)}")
+        if aggregator != "fedavg" and update_clip is not None:
+            raise NotImplementedError("update_clip with a robust aggregator: the clip coefficient is per row and breaks the "
+                                      "ordering the rows of a coordinate share")
+        if aggregator != "fedavg" and num_clusters > 1:
+            raise NotImplementedError("num_clusters > 1 with a robust aggregator")
+        if not trim_ratio >= 0.0:
+            raise ValueError(f"invalid trim_ratio: {trim_ratio}")
+        if num_byzantine < 0:
+            raise ValueError(f"invalid num_byzantine: {num_byzantine}")
+        if num_selected is not None and num_selected < 1:
+            raise ValueError(f"invalid num_selected: {num_selected}")
         if clients_per_round < 1 or clients_per_round > _nvq.FED_MAX_CLIENTS:
             raise ValueError(f"clients_per_round: 1 .. {_nvq.FED_MAX_CLIENTS}")
         if update_clip is not None and not update_clip > 0.0:
@@ -222,6 +249,9 @@ class FederatedTrainer:
         self.privacy = privacy
         self.update_clip, self.update_noise, self.server_lr = update_clip, float(update_noise), float(server_lr)
         self.optimizer_impl = optimizer_impl
+        self.aggregator, self.trim_ratio = aggregator, float(trim_ratio)
+        self.num_byzantine, self.num_selected = int(num_byzantine), num_selected
+        self.after_client = after_client
         self.seed = seed
         self._rng = random.Random(seed) if seed is not None else random
         self._noise_seed = random.Random(seed).getrandbits(62) if seed is not None else random.getrandbits(62)
@@ -330,6 +360,67 @@ class FederatedTrainer:
             pack.unpack(plan["rest_snap"])
         for t, rows in zip(plan["ints"], plan["int_rows"]):
             t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+
+    # ------------------------------------------------------------------ robust rounds
+    def _robust_plan(self, counts: List[int]) -> Tuple[int, int]:
+        """(trim, number selected) of this round from the sample counts, which the host knows; raises before any client trains"""
+        m = sum(1 for c in counts if c > 0)
+        f = self.num_byzantine
+        if self.aggregator == "median":
+            return _nvq.FED_TRIM_MEDIAN, 0
+        if self.aggregator == "trimmed_mean":
+            trim = int(self.trim_ratio * m + 1e-9)
+            if not 2 * trim < m:
+                raise ValueError(f"trim_ratio {self.trim_ratio} trims {trim} of {m} clients with samples from each side: nothing is left")
+            return trim, 0
+        if m < f + 3:
+            raise ValueError(f"{self.aggregator}: {m} clients with samples and num_byzantine = {f}: Krum needs at least f + 3")
+        if self.aggregator == "krum":
+            return 0, 1
+        return 0, (self.num_selected if self.num_selected is not None else m - f)
+
+    @torch.no_grad()
+    def _aggregate_robust(self, plan, K: int, trim: int, q: int) -> Optional[torch.Tensor]:
+        """``_aggregate`` with the robust rules: the sample counts only say which rows are live.  Median and
+        trimmed mean: one ``nvq_fed_trimmed_aggregate`` per matrix.  Krum: the Gram of the whole updates (the flat networks' and the
+        rest matrix's added), one ``nvq_fed_krum_select``, then the trim-0 pass per matrix with the selection as weights; returns
+        the selection."""
+        from nerve_cl.federated.clustering import update_gram
+        from nerve_cl.federated.robust import aggregate_flat_trimmed, krum_select
+        w = plan["weights"][:K]
+        dev, nets, pack = plan["dev"], plan["nets"], plan["pack"]
+        plain = self.update_noise == 0.0 and self.server_lr == 1.0
+        selected = None
+        if q:
+            gram = None
+            for rows, snap in zip(plan["rows"], plan["snaps"]):
+                g = update_gram(rows[:K], snap)
+                gram = g if gram is None else gram.add_(g)
+            if pack.total:
+                g = update_gram(plan["rest_rows"][:K], plan["rest_snap"])
+                gram = g if gram is None else gram.add_(g)
+            if gram is None:                           # a model without floating state: nothing to tell the clients apart by
+                gram = torch.zeros(K, K, dtype=torch.float64, device=w.device)
+            w = selected = krum_select(gram, self.num_byzantine, q, weights=w).weights
+        for j, (net, rows, snap) in enumerate(zip(nets, plan["rows"], plan["snaps"])):
+            flat = net.flat_theta()
+            with _nvq.device_guard(dev):
+                _nvq.fed_trimmed_aggregate(rows[:K], flat.numel(), None if plain else snap, w, trim, flat, server_lr=self.server_lr,
+                                           noise_std=self.update_noise, seed=self._noise_seed,
+                                           offset=self.global_round * (len(nets) + 1) + j)
+        if pack.total:
+            rest = plan["rest_rows"][:K]
+            if nets:                                   # next to the flat buffers: statistics and loose parameters, no rate, no noise
+                with _nvq.device_guard(dev):
+                    _nvq.fed_trimmed_aggregate(rest, rest.shape[1], None, w, trim, plan["rest_snap"])
+            else:                                      # no HIP-backed network (a plain module, any device): everything is here
+                aggregate_flat_trimmed(rest, trim, weights=w, base=None if plain else plan["rest_snap"], server_lr=self.server_lr,
+                                       noise_std=self.update_noise, seed=self._noise_seed, offset=self.global_round,
+                                       out=plan["rest_snap"])
+            pack.unpack(plan["rest_snap"])
+        for t, rows in zip(plan["ints"], plan["int_rows"]):
+            t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+        return selected
 
     # ------------------------------------------------------------------ clustered rounds
     def _cluster_weights(self) -> List[float]:
@@ -447,6 +538,7 @@ class FederatedTrainer:
         counts = [len(self.client_data[c][0]) for c in selected]
         if selected and not sum(counts) > 0:
             raise ValueError("train_round: every selected client has no samples (all-zero aggregation weights)")
+        robust = self._robust_plan(counts) if selected and self.aggregator != "fedavg" else None
         if self._plan is None:
             self._plan = self._build_plan()
         plan = self._plan
@@ -469,14 +561,19 @@ class FederatedTrainer:
                     self._restore(plan)
             loss_sum += self._train_client(plan, self.client_data[cid], seeds[k])
             with torch.no_grad():
+                if self.after_client is not None:
+                    self.after_client(cid, self.model)
                 for net, rows in zip(plan["nets"], plan["rows"]):
                     rows[k].copy_(net.flat_theta())
                 plan["pack"].pack(plan["rest_rows"][k])
                 for t, rows in zip(plan["ints"], plan["int_rows"]):
                     rows[k].copy_(t)
                 plan["weights"][k].fill_(float(cnt))
+        selection = None
         if K and clustered:
             self._aggregate_clusters(plan, selected, counts, K, split)
+        elif K and robust is not None:
+            selection = self._aggregate_robust(plan, K, *robust)
         elif K:
             self._aggregate(plan, K)
         self.global_round += 1
@@ -485,6 +582,8 @@ class FederatedTrainer:
         out = {"round": self.global_round, "clients": K, "samples": sum(counts), "train_loss": loss_sum / steps}
         if self.num_clusters > 1:
             out["clusters"] = self.cluster_sizes()
+        if selection is not None:
+            out["selected_weights"] = selection
         return out
 
     def train_round(self) -> Dict[str, float]:
@@ -492,4 +591,6 @@ class FederatedTrainer:
         training loss per sample over the clients' local steps."""
         out = self.train_round_device()
         out["train_loss"] = float(out["train_loss"])
+        if "selected_weights" in out:
+            out["selected_weights"] = out["selected_weights"].tolist()
         return out

@@ -9,7 +9,12 @@ to the global weights in place, and ends with one aggregation pass of csrc/feder
 clip-and-noise DPOptimizer (two launches on the gradient bucket); ``--update-clip`` / ``--update-noise`` / ``--server-lr`` act on
 the clients' whole updates in the aggregation pass.  ``--clusters C`` (with ``--cluster-after R`` plain rounds first) is clustered
 federated learning: one round clusters the clients by their updates (csrc/cluster.hip), every cluster then
-has its own model; the sizes are printed after the split and every cluster's evaluation loss at the end.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
+has its own model; the sizes are printed after the split and every cluster's evaluation loss at the end.  ``--aggregator`` chooses
+a Byzantine-robust rule instead of FedAvg (``median``, ``trimmed_mean`` with ``--trim-ratio``, ``krum`` / ``multi_krum`` with
+``--num-byzantine``; csrc/robust.hip), and ``--poison N`` makes the first N selected clients of every round
+hostile through the trainer's ``after_client`` hook: ``--poison-kind flip`` sends ``global - 10 (x - global)``, ``nan`` sends NaN
+weights.  With either option the evaluation loss of the global model over all clients' data is printed after every round: FedAvg
+breaks under ``--poison 1``, the robust rules hold.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
 """
 import argparse
 from pathlib import Path
@@ -20,6 +25,7 @@ import torch
 from _common import OPTIMIZER_IMPLS, pick_device
 from nerve_cl import ops
 from nerve_cl.federated import FederatedTrainer, PrivacyConfig
+from nerve_cl.federated.trainer import AGGREGATORS
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 from train_continual import _ClipAdapter, configure_precision
 
@@ -48,6 +54,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--clusters", type=int, default=1, metavar="C",
                     help="cluster the clients by their updates into C groups with one model each (default 1: plain FedAvg)")
     ap.add_argument("--cluster-after", type=int, default=0, metavar="R", help="plain FedAvg rounds before the round that clusters")
+    ap.add_argument("--aggregator", choices=AGGREGATORS, default="fedavg",
+                    help="how a round combines the clients' weights: FedAvg, or a Byzantine-robust rule (no --update-clip, no --clusters)")
+    ap.add_argument("--trim-ratio", type=float, default=0.1,
+                    help="trimmed_mean: the share of the clients dropped from each side of every coordinate")
+    ap.add_argument("--num-byzantine", type=int, default=0, metavar="F", help="krum / multi_krum: the number of clients assumed hostile")
+    ap.add_argument("--poison", type=int, default=0, metavar="N", help="the first N selected clients of every round send poisoned weights")
+    ap.add_argument("--poison-kind", choices=["flip", "nan"], default="flip",
+                    help="flip: global - 10 (x - global), the sign-flipped, scaled update; nan: NaN weights")
     ap.add_argument("--samples", type=int, default=100, help="clips per client (the reference's 100)")
     ap.add_argument("--features", type=int, default=64)
     ap.add_argument("--blocks", type=int, default=8)
@@ -57,6 +71,22 @@ def build_parser() -> argparse.ArgumentParser:
                     help="torch: torch.optim's fused AdamW (default); bucket: nerve_cl.optim.BucketAdamW on the flat buckets")
     ap.add_argument("--seed", type=int, default=0, help="client selection, data and every noise stream")
     return ap
+
+
+def evaluate(trainer) -> float:
+    """the mean loss of the model as it stands over every client's data"""
+    model, loss = trainer.model, ops.MSELoss()
+    was_training = model.training
+    model.eval()
+    total, seen = 0.0, 0
+    with torch.no_grad():
+        for xs, ys in trainer.client_data.values():
+            for i in range(0, len(xs), trainer.batch_size):
+                x, y = xs[i:i + trainer.batch_size], ys[i:i + trainer.batch_size]
+                total += float(loss(model(x), y)) * len(x)
+                seen += len(x)
+    model.train(was_training)
+    return total / max(seen, 1)
 
 
 def main() -> None:
@@ -75,16 +105,34 @@ def main() -> None:
     privacy = None
     if args.dp_enabled:
         privacy = PrivacyConfig(max_grad_norm=args.dp_max_grad_norm, noise_multiplier=args.dp_noise_multiplier)
+    poison = {"left": 0, "global": None}               # armed before every round: the clients still to poison, the global weights
+
+    def after_client(client_id, model):
+        if poison["left"] <= 0:
+            return
+        poison["left"] -= 1
+        for v, g in zip(model.state_dict().values(), poison["global"]):
+            if v.is_floating_point():
+                v.copy_(torch.full_like(v, float("nan")) if args.poison_kind == "nan" else g - 10.0 * (v - g))
+
     trainer = FederatedTrainer(_ClipAdapter(engine), num_clients=args.num_clients, clients_per_round=args.clients_per_round,
                                local_epochs=args.local_epochs, loss=ops.MSELoss(), privacy=privacy, update_clip=args.update_clip,
                                update_noise=args.update_noise, server_lr=args.server_lr, optimizer_impl=args.optimizer_impl,
-                               seed=args.seed, num_clusters=args.clusters, cluster_after=args.cluster_after)
+                               seed=args.seed, num_clusters=args.clusters, cluster_after=args.cluster_after,
+                               aggregator=args.aggregator, trim_ratio=args.trim_ratio, num_byzantine=args.num_byzantine,
+                               after_client=after_client if args.poison > 0 else None)
     for cid in range(args.num_clients):
         lr, hr = create_client_data(cid, args.samples)
         trainer.set_client_data(cid, (lr.to(device), hr.to(device)))          # on the device: a round copies nothing from the host
     for _ in range(args.num_rounds):
+        if args.poison > 0:
+            poison["left"] = args.poison
+            poison["global"] = [v.detach().clone() for v in trainer.model.state_dict().values()]
         m = trainer.train_round()
         print(f"Round {m['round']}: {m['clients']} clients, {m['samples']} samples, loss {m['train_loss']:.4f}")
+        if args.poison > 0 or args.aggregator != "fedavg":
+            chosen = f", selected {[int(w) for w in m['selected_weights']]}" if "selected_weights" in m else ""
+            print(f"  evaluation loss of the global model {evaluate(trainer):.4f}{chosen}")
         if args.clusters > 1 and m["round"] == args.cluster_after + 1:
             print(f"  clusters after the split: sizes {m['clusters']}, clients {trainer.client_cluster}")
     if trainer.cluster_models is not None:

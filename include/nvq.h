@@ -1036,6 +1036,32 @@ int nvq_fed_aggregate_clusters(const float* clients, long stride, int K, const i
                                long base_stride, const double* weights, const double* sq, float clip_norm, float server_lr,
                                float noise_std, long seed, long offset, long n, float* out, long out_stride, void* stream);
 
+/* ------------------------------------------------------------------ Byzantine-robust aggregation
+ * (csrc/robust.hip).  The same client matrix and the same rule as above: no atomics, size-only grids, sums
+ * in double in a fixed order, the same bits on every call and at every pointer alignment.
+ *
+ * A row k is live when weights == NULL or weights[k] > 0 (K device doubles); m = the number of live rows.  A row that is not live
+ * is never read, so a zero-weight row of NaN does not reach the result (it would through 0 * NaN in nvq_fed_aggregate).
+ *
+ * nvq_fed_trimmed_aggregate: per element i the live rows are sorted ascending by x_k[i] (NaN after +inf whatever its sign bit, as
+ * np.sort; -0.0 and +0.0 in either order), t = min(trim, (m - 1) / 2), a = the sum of d_k = (double) x_k[i] - (double) base[i] over
+ * the sorted positions t .. m - 1 - t, added in that order in double, divided by m - 2 t (m == 0: a = 0); v = (float) fma(server_lr,
+ * a, base[i]) rounded once, out[i] = fmaf(noise_std, z_i, v) with the noise stream of nvq_fed_aggregate ("Noise" above; noise_std
+ * == 0 skips the noise path).  base == NULL: zeros.  trim = 0 is the unweighted mean of the live rows; trim >= (K - 1) / 2, for
+ * which NVQ_FED_TRIM_MEDIAN stands, the coordinate-wise median (the middle value, or the mean of the two middle values).
+ * 1 <= K <= 64.  out may alias base; out must not alias clients.
+ *
+ * nvq_fed_krum_select: gram = the K * K doubles nvq_fed_update_gram leaves.  D_ij = max(0, G_ii + G_jj - 2 G_ij) over live i != j,
+ * a NaN distance replaced by +inf; c = min(max(m - num_byzantine - 2, 1), m - 1); scores[i] = the sum of the c smallest D_ij,
+ * added ascending in double (one live row: 0), +inf for a row that is not live.  order = the live rows by (score, index)
+ * ascending, NaN scores last, then the other rows by index; out_weights[k] = 1 for the first min(num_selected, m) rows of order,
+ * else 0.  One workgroup.  nvq_fed_trimmed_aggregate with trim = 0 and weights = out_weights then averages the selected rows. */
+#define NVQ_FED_TRIM_MEDIAN 64
+int nvq_fed_trimmed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, int trim,
+                              float server_lr, float noise_std, long seed, long offset, long n, float* out, void* stream);
+int nvq_fed_krum_select(const double* gram, int K, const double* weights, int num_byzantine, int num_selected,
+                        double* out_weights, double* scores, int* order, void* stream);
+
 /* ------------------------------------------------------------------ ABR agent: vectorised streaming environment, fused act,
  * GAE and the PPO loss (csrc/abr.hip).  No atomics; sums in double in a fixed order; plain vector stores.
  *
