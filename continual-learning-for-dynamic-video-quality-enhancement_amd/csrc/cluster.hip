@@ -6,8 +6,7 @@
 //
 // The flat-buffer rule of flat.h: no atomics, grids that depend on the sizes only, whole quads per lane in the vector and in
 // the scalar form alike, sums in double in a fixed order: the same bits on every call and at every pointer alignment.
-#include "flat.h"
-#include "philox.h"
+#include "fed.h"
 
 namespace nvq {
 
@@ -298,10 +297,8 @@ __global__ __launch_bounds__(256) void cluster_gram_kmeans_kernel(const double* 
 }
 
 // ------------------------------------------------------------------ one model per cluster
-__device__ __forceinline__ float clu_mix(double a, float b, double lr) { return (float)fma(lr, a, (double)b); }
-
 // order[start[c] .. start[c + 1]) = the members of cluster c in ascending k; per quad the clusters are taken in turn, each
-// with fed_aggregate_kernel's fma sequence over its members, so every client row is read once and C rows are written.
+// the fed_mean_quad / fed_mean_tail (fed.h) of its members, so every client row is read once and C rows are written.
 template <bool VEC, bool HAS_BASE, bool NOISE>
 __global__ __launch_bounds__(256) void fed_aggregate_clusters_kernel(const float* __restrict__ clients, long stride, int K,
                                                                      const int* __restrict__ labels, int C, const float* bases,
@@ -326,13 +323,8 @@ __global__ __launch_bounds__(256) void fed_aggregate_clusters_kernel(const float
             rank += k < tid && lab[k] == l;
             if (lab[k] == l) W += weights[k];
         }
-        double s = 1.0;
-        if (sq != nullptr) {
-            s = (double)clip_norm / (sqrt(sq[tid]) + 1e-6);
-            if (!(s < 1.0)) s = 1.0;
-        }
         order[before + rank] = tid;
-        coef[tid] = weights[tid] / W * s;
+        coef[tid] = weights[tid] / W * fed_clip(sq, tid, clip_norm);
     }
     if (tid <= C) {
         int m = 0;
@@ -341,6 +333,7 @@ __global__ __launch_bounds__(256) void fed_aggregate_clusters_kernel(const float
     }
     __syncthreads();
 
+    const auto row = [&](int m) { return order[m]; };
     const double lr = (double)server_lr;
     const long nq = n >> 2;
     for (long q = blockIdx.x * 256L + tid; q < nq; q += (long)gridDim.x * 256) {
@@ -348,43 +341,17 @@ __global__ __launch_bounds__(256) void fed_aggregate_clusters_kernel(const float
         if (HAS_BASE && base_stride == 0) b = ldq<VEC>(bases + 4 * q);  // a shared base: once, before any row is written
         for (int c = 0; c < C; ++c) {
             if (HAS_BASE && base_stride != 0) b = ldq<VEC>(bases + c * base_stride + 4 * q);
-            double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
-            for (int m = start[c]; m < start[c + 1]; ++m) {
-                const int k = order[m];
-                const float4 x = ldq<VEC>(clients + k * stride + 4 * q);
-                const double cf = coef[k];
-                ax = fma(cf, (double)x.x - (double)b.x, ax);
-                ay = fma(cf, (double)x.y - (double)b.y, ay);
-                az = fma(cf, (double)x.z - (double)b.z, az);
-                aw = fma(cf, (double)x.w - (double)b.w, aw);
-            }
-            float4 v = make_float4(clu_mix(ax, b.x, lr), clu_mix(ay, b.y, lr), clu_mix(az, b.z, lr), clu_mix(aw, b.w, lr));
-            if (NOISE) {
-                const float4 z = quad_normals(q, seed, offset + c);
-                v.x = fmaf(noise_std, z.x, v.x);
-                v.y = fmaf(noise_std, z.y, v.y);
-                v.z = fmaf(noise_std, z.z, v.z);
-                v.w = fmaf(noise_std, z.w, v.w);
-            }
-            stq<VEC>(out + c * out_stride + 4 * q, v);
+            stq<VEC>(out + c * out_stride + 4 * q, fed_mean_quad<VEC, NOISE>(clients, stride, q, b, coef, row, start[c], start[c + 1],
+                                                                              lr, noise_std, seed, offset + c));
         }
     }
-    const long t = 4 * nq + tid;                      // the n % 4 last floats: threads 0..2 of block 0
-    if (blockIdx.x == 0 && tid < 3 && t < n) {
+    const long t = 4 * nq + tid;
+    if (flat_tail(n, t)) {
         float b = (HAS_BASE && base_stride == 0) ? bases[t] : 0.f;
         for (int c = 0; c < C; ++c) {
             if (HAS_BASE && base_stride != 0) b = bases[c * base_stride + t];
-            double a = 0.0;
-            for (int m = start[c]; m < start[c + 1]; ++m) {
-                const int k = order[m];
-                a = fma(coef[k], (double)clients[k * stride + t] - (double)b, a);
-            }
-            float v = clu_mix(a, b, lr);
-            if (NOISE) {
-                const float4 z = quad_normals(nq, seed, offset + c);
-                v = fmaf(noise_std, tid == 0 ? z.x : (tid == 1 ? z.y : z.z), v);
-            }
-            out[c * out_stride + t] = v;
+            out[c * out_stride + t] = fed_mean_tail<NOISE>(clients, stride, t, nq, b, coef, row, start[c], start[c + 1], lr,
+                                                           noise_std, seed, offset + c);
         }
     }
 }
@@ -402,10 +369,9 @@ size_t nvq_fed_gram_workspace_bytes(int K, long n) {
 
 int nvq_fed_update_gram(const float* clients, long stride, int K, const float* base, long n, double* gram, float* workspace,
                         size_t workspace_bytes, void* stream) {
-    NVQ_REQUIRE(clients != nullptr && gram != nullptr && n >= 0, "fed_update_gram: clients / gram / n");
-    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_update_gram: K = %d outside 1 .. 64", K);
-    NVQ_REQUIRE(stride >= n, "fed_update_gram: stride %ld < n %ld", stride, n);
-    NVQ_REQUIRE(aligned8(gram) && aligned8(workspace), "fed_update_gram: gram and workspace must be 8-byte aligned");
+    int rc = fed_check("fed_update_gram", clients, stride, K, n);
+    if (rc) return rc;
+    NVQ_REQUIRE(gram != nullptr && aligned8(gram) && aligned8(workspace), "fed_update_gram: gram / 8-byte alignment");
     const int nb = flat_blocks(n), T = ceil_div(K, 16);
     if (workspace == nullptr || nvq_fed_gram_workspace_bytes(K, n) > workspace_bytes) {
         set_error("fed_update_gram: workspace");
@@ -413,7 +379,7 @@ int nvq_fed_update_gram(const float* clients, long stride, int K, const float* b
     }
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
-    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base));
+    const bool vec = fed_vec(clients, stride, base);
     const dim3 grid(nb), block(256);
     with_bools([&](auto V, auto B) {
         const auto kernel = T == 1   ? fed_update_gram_kernel<V(), B(), 1>
@@ -422,7 +388,7 @@ int nvq_fed_update_gram(const float* clients, long stride, int K, const float* b
                                      : fed_update_gram_kernel<V(), B(), 4>;
         hipLaunchKernelGGL(kernel, grid, block, 0, s, clients, stride, K, base, n, part);
     }, vec, base != nullptr);
-    int rc = check_launch("fed_update_gram");
+    rc = check_launch("fed_update_gram");
     if (rc) return rc;
     hipLaunchKernelGGL(fed_update_gram_final_kernel, dim3(16, gram_tiles(T)), dim3(256), 0, s, part, nb, K, T, gram);
     return check_launch("fed_update_gram_final");
@@ -445,22 +411,20 @@ int nvq_cluster_gram_kmeans(const double* gram, int K, int C, const int* init, i
 int nvq_fed_aggregate_clusters(const float* clients, long stride, int K, const int* labels, int C, const float* bases,
                                long base_stride, const double* weights, const double* sq, float clip_norm, float server_lr,
                                float noise_std, long seed, long offset, long n, float* out, long out_stride, void* stream) {
-    NVQ_REQUIRE(clients != nullptr && labels != nullptr && weights != nullptr && out != nullptr && n >= 0,
-                "fed_aggregate_clusters: clients / labels / weights / out / n");
-    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_aggregate_clusters: K = %d outside 1 .. 64", K);
+    int rc = fed_check("fed_aggregate_clusters", clients, stride, K, n, seed, offset, noise_std);
+    if (rc) return rc;
+    NVQ_REQUIRE(labels != nullptr && weights != nullptr && out != nullptr, "fed_aggregate_clusters: labels / weights / out");
     NVQ_REQUIRE(C >= 1 && C <= CLUSTER_MAX, "fed_aggregate_clusters: C = %d outside 1 .. %d", C, CLUSTER_MAX);
-    NVQ_REQUIRE(stride >= n && out_stride >= n, "fed_aggregate_clusters: stride %ld / out_stride %ld < n %ld", stride, out_stride, n);
+    NVQ_REQUIRE(out_stride >= n, "fed_aggregate_clusters: out_stride %ld < n %ld", out_stride, n);
     NVQ_REQUIRE(base_stride == 0 || (bases != nullptr && base_stride >= n), "fed_aggregate_clusters: base_stride %ld", base_stride);
-    NVQ_REQUIRE(seed >= 0 && offset >= 0, "fed_aggregate_clusters: seed and offset are non-negative");
-    NVQ_REQUIRE(noise_std >= 0.f && (sq == nullptr || clip_norm >= 0.f), "fed_aggregate_clusters: noise_std / clip_norm");
+    NVQ_REQUIRE(sq == nullptr || clip_norm >= 0.f, "fed_aggregate_clusters: clip_norm");
     NVQ_REQUIRE(sq == nullptr || base_stride == 0, "fed_aggregate_clusters: clipping needs one shared base");
     NVQ_REQUIRE(bases == nullptr || base_stride != 0 || C == 1 || out != bases,
                 "fed_aggregate_clusters: out may be bases only with one base per cluster");
     NVQ_REQUIRE(out != bases || C == 1 || out_stride == base_stride, "fed_aggregate_clusters: in place needs out_stride == base_stride");
     NVQ_REQUIRE(aligned8(weights) && aligned8(sq) && aligned4(labels), "fed_aggregate_clusters: table alignment");
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = aligned16(clients) && (stride & 3) == 0 && (bases == nullptr || (aligned16(bases) && (base_stride & 3) == 0)) &&
-                     aligned16(out) && (out_stride & 3) == 0;
+    const bool vec = fed_vec(clients, stride, bases, out) && (base_stride & 3) == 0 && (out_stride & 3) == 0;
     const dim3 grid(flat_blocks(n)), block(256);
     with_bools([&](auto V, auto B, auto N) {
         hipLaunchKernelGGL((fed_aggregate_clusters_kernel<V(), B(), N()>), grid, block, 0, s, clients, stride, K, labels, C, bases,

@@ -8,8 +8,7 @@
 // No atomics; every grid depends on the sizes only; every thread owns whole quads (4 consecutive floats) in the vector and
 // in the scalar form alike and adds in one order, so a result depends neither on pointer alignment nor on the call.  The
 // noise is Philox4x32-10 keyed by (seed), counted by (quad index, offset): a function of (seed, offset, element) alone.
-#include "flat.h"
-#include "philox.h"
+#include "fed.h"
 
 namespace nvq {
 
@@ -76,8 +75,7 @@ __global__ __launch_bounds__(256) void fed_delta_norms_final_kernel(const double
 }
 
 // ------------------------------------------------------------------ aggregate
-__device__ __forceinline__ float fed_mix(double a, float b, double lr) { return (float)fma(lr, a, (double)b); }
-
+// fed_mean_quad / fed_mean_tail (fed.h) over all K rows in index order
 template <bool VEC, bool HAS_BASE, bool NOISE>
 __global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restrict__ clients, long stride, int K,
                                                             const float* base, const double* __restrict__ weights,
@@ -88,48 +86,20 @@ __global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restr
         double W = 0.0;
         for (int k = 0; k < K; ++k) W += weights[k];
         const int k = threadIdx.x;
-        double s = 1.0;
-        if (sq != nullptr) {
-            s = (double)clip_norm / (sqrt(sq[k]) + 1e-6);
-            if (!(s < 1.0)) s = 1.0;
-        }
-        coef[k] = weights[k] / W * s;
+        coef[k] = weights[k] / W * fed_clip(sq, k, clip_norm);
     }
     __syncthreads();
+    const auto row = [](int m) { return m; };
     const double lr = (double)server_lr;
     const long nq = n >> 2;
     for (long q = blockIdx.x * 256L + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
         const float4 b = HAS_BASE ? ldq<VEC>(base + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-        double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const float4 x = ldq<VEC>(clients + k * stride + 4 * q);
-            const double c = coef[k];
-            ax = fma(c, (double)x.x - (double)b.x, ax);
-            ay = fma(c, (double)x.y - (double)b.y, ay);
-            az = fma(c, (double)x.z - (double)b.z, az);
-            aw = fma(c, (double)x.w - (double)b.w, aw);
-        }
-        float4 v = make_float4(fed_mix(ax, b.x, lr), fed_mix(ay, b.y, lr), fed_mix(az, b.z, lr), fed_mix(aw, b.w, lr));
-        if (NOISE) {
-            const float4 z = quad_normals(q, seed, offset);
-            v.x = fmaf(noise_std, z.x, v.x);
-            v.y = fmaf(noise_std, z.y, v.y);
-            v.z = fmaf(noise_std, z.z, v.z);
-            v.w = fmaf(noise_std, z.w, v.w);
-        }
-        stq<VEC>(out + 4 * q, v);
+        stq<VEC>(out + 4 * q, fed_mean_quad<VEC, NOISE>(clients, stride, q, b, coef, row, 0, K, lr, noise_std, seed, offset));
     }
-    const long t = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
-    if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
+    const long t = 4 * nq + threadIdx.x;
+    if (flat_tail(n, t)) {
         const float b = HAS_BASE ? base[t] : 0.f;
-        double a = 0.0;
-        for (int k = 0; k < K; ++k) a = fma(coef[k], (double)clients[k * stride + t] - (double)b, a);
-        float v = fed_mix(a, b, lr);
-        if (NOISE) {
-            const float4 z = quad_normals(nq, seed, offset);
-            v = fmaf(noise_std, threadIdx.x == 0 ? z.x : (threadIdx.x == 1 ? z.y : z.z), v);
-        }
-        out[t] = v;
+        out[t] = fed_mean_tail<NOISE>(clients, stride, t, nq, b, coef, row, 0, K, lr, noise_std, seed, offset);
     }
 }
 
@@ -206,13 +176,7 @@ __global__ __launch_bounds__(256) void dp_clip_noise_kernel(float* __restrict__ 
         a.y = __fmul_rn(a.y, cf);
         a.z = __fmul_rn(a.z, cf);
         a.w = __fmul_rn(a.w, cf);
-        if (NOISE) {
-            const float4 z = quad_normals(q, seed, offset);
-            a.x = fmaf(noise_scale, z.x, a.x);
-            a.y = fmaf(noise_scale, z.y, a.y);
-            a.z = fmaf(noise_scale, z.z, a.z);
-            a.w = fmaf(noise_scale, z.w, a.w);
-        }
+        fed_noise<NOISE>(a, noise_scale, q, seed, offset);
         const long e = 4 * q;                          // the slot's padding stays exactly zero: those draws are dropped
         if (e + 1 >= e1) a.y = 0.f;
         if (e + 2 >= e1) a.z = 0.f;
@@ -245,10 +209,9 @@ size_t nvq_fed_workspace_bytes(int K, long n) {
 
 int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* base, long n, double* sq, float* workspace,
                         size_t workspace_bytes, void* stream) {
-    NVQ_REQUIRE(clients != nullptr && sq != nullptr && n >= 0, "fed_delta_norms: clients / sq / n");
-    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_delta_norms: K = %d outside 1 .. 64", K);
-    NVQ_REQUIRE(stride >= n, "fed_delta_norms: stride %ld < n %ld", stride, n);
-    NVQ_REQUIRE(aligned8(sq) && aligned8(workspace), "fed_delta_norms: sq and workspace must be 8-byte aligned");
+    int rc = fed_check("fed_delta_norms", clients, stride, K, n);
+    if (rc) return rc;
+    NVQ_REQUIRE(sq != nullptr && aligned8(sq) && aligned8(workspace), "fed_delta_norms: sq / 8-byte alignment");
     const int nb = flat_blocks(n);
     if (workspace == nullptr || (size_t)nb * K * sizeof(double) > workspace_bytes) {
         set_error("fed_delta_norms: workspace");
@@ -256,7 +219,7 @@ int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* b
     }
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
-    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base));
+    const bool vec = fed_vec(clients, stride, base);
     const dim3 grid(nb), block(256);
     with_bools([&](auto V, auto B) {
         const auto kernel = K <= 8    ? fed_delta_norms_kernel<V(), B(), 8>
@@ -264,7 +227,7 @@ int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* b
                                       : fed_delta_norms_kernel<V(), B(), 64>;
         hipLaunchKernelGGL(kernel, grid, block, 0, s, clients, stride, K, base, n, part);
     }, vec, base != nullptr);
-    int rc = check_launch("fed_delta_norms");
+    rc = check_launch("fed_delta_norms");
     if (rc) return rc;
     hipLaunchKernelGGL(fed_delta_norms_final_kernel, dim3(K), dim3(256), 0, s, part, nb, K, sq);
     return check_launch("fed_delta_norms_final");
@@ -273,14 +236,13 @@ int nvq_fed_delta_norms(const float* clients, long stride, int K, const float* b
 int nvq_fed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, const double* sq,
                       float clip_norm, float server_lr, float noise_std, long seed, long offset, long n, float* out,
                       void* stream) {
-    NVQ_REQUIRE(clients != nullptr && weights != nullptr && out != nullptr && n >= 0, "fed_aggregate: clients / weights / out / n");
-    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_aggregate: K = %d outside 1 .. 64", K);
-    NVQ_REQUIRE(stride >= n, "fed_aggregate: stride %ld < n %ld", stride, n);
-    NVQ_REQUIRE(seed >= 0 && offset >= 0, "fed_aggregate: seed and offset are non-negative");
-    NVQ_REQUIRE(noise_std >= 0.f && (sq == nullptr || clip_norm >= 0.f), "fed_aggregate: noise_std / clip_norm");
+    int rc = fed_check("fed_aggregate", clients, stride, K, n, seed, offset, noise_std);
+    if (rc) return rc;
+    NVQ_REQUIRE(weights != nullptr && out != nullptr, "fed_aggregate: weights / out");
+    NVQ_REQUIRE(sq == nullptr || clip_norm >= 0.f, "fed_aggregate: clip_norm");
     NVQ_REQUIRE(aligned8(weights) && aligned8(sq), "fed_aggregate: weights and sq must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base)) && aligned16(out);
+    const bool vec = fed_vec(clients, stride, base, out);
     const dim3 grid(flat_blocks(n)), block(256);
     with_bools([&](auto V, auto B, auto N) {
         hipLaunchKernelGGL((fed_aggregate_kernel<V(), B(), N()>), grid, block, 0, s, clients, stride, K, base, weights, sq,

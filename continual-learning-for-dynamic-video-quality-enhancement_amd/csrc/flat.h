@@ -39,6 +39,9 @@ __device__ __forceinline__ void stq(float* p, float4 v) {
     }
 }
 
+// The n % 4 last floats belong to threads 0 .. 2 of block 0: whether this thread owns tail element t = 4 * (n >> 2) + threadIdx.x.
+__device__ __forceinline__ bool flat_tail(long n, long t) { return blockIdx.x == 0 && threadIdx.x < 3 && t < n; }
+
 // Sum over the 64 lanes of a wave, the 32, 16, ..., 1 xor-shuffle tree; valid in every lane.
 __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

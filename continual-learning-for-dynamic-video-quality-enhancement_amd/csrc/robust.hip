@@ -10,8 +10,7 @@
 // fixed order: the same bits on every call and at every pointer alignment.
 #include <utility>
 
-#include "flat.h"
-#include "philox.h"
+#include "fed.h"
 
 namespace nvq {
 
@@ -109,7 +108,7 @@ __device__ __forceinline__ double trimmed_element(const float* __restrict__ clie
 
 __device__ __forceinline__ float robust_mix(double sum, int cnt, float b, double lr) {
     const double a = cnt > 0 ? sum / (double)cnt : 0.0;
-    return (float)fma(lr, a, (double)b);
+    return fed_mix(a, b, lr);
 }
 
 // KMAX <= 16: the quad's four columns of keys live in registers at once (one 16-byte load per row).  KMAX >= 32: one column at a
@@ -160,23 +159,14 @@ __global__ __launch_bounds__(256) void fed_trimmed_kernel(const float* __restric
                 v.w = c == 3 ? r : v.w;
             }
         }
-        if (NOISE) {
-            const float4 z = quad_normals(q, seed, offset);
-            v.x = fmaf(noise_std, z.x, v.x);
-            v.y = fmaf(noise_std, z.y, v.y);
-            v.z = fmaf(noise_std, z.z, v.z);
-            v.w = fmaf(noise_std, z.w, v.w);
-        }
+        fed_noise<NOISE>(v, noise_std, q, seed, offset);
         stq<VEC>(out + 4 * q, v);
     }
     const long e = 4 * nq + threadIdx.x;              // the n % 4 last floats: threads 0..2 of block 0
     if (blockIdx.x == 0 && threadIdx.x < 3 && e < n) {
         const float b = HAS_BASE ? base[e] : 0.f;
         float v = robust_mix(trimmed_element<KMAX>(clients, stride, live, e, b, lo, hi), cnt, b, lr);
-        if (NOISE) {
-            const float4 z = quad_normals(nq, seed, offset);
-            v = fmaf(noise_std, threadIdx.x == 0 ? z.x : (threadIdx.x == 1 ? z.y : z.z), v);
-        }
+        fed_noise_tail<NOISE>(v, noise_std, nq, seed, offset);
         out[e] = v;
     }
 }
@@ -253,18 +243,15 @@ extern "C" {
 
 int nvq_fed_trimmed_aggregate(const float* clients, long stride, int K, const float* base, const double* weights, int trim,
                               float server_lr, float noise_std, long seed, long offset, long n, float* out, void* stream) {
-    NVQ_REQUIRE(clients != nullptr && out != nullptr && n >= 0, "fed_trimmed_aggregate: clients / out / n");
-    NVQ_REQUIRE(K >= 1 && K <= 64, "fed_trimmed_aggregate: K = %d outside 1 .. 64", K);
-    NVQ_REQUIRE(stride >= n, "fed_trimmed_aggregate: stride %ld < n %ld", stride, n);
-    NVQ_REQUIRE(trim >= 0, "fed_trimmed_aggregate: trim = %d", trim);
-    NVQ_REQUIRE(seed >= 0 && offset >= 0, "fed_trimmed_aggregate: seed and offset are non-negative");
-    NVQ_REQUIRE(noise_std >= 0.f, "fed_trimmed_aggregate: noise_std");
+    int rc = fed_check("fed_trimmed_aggregate", clients, stride, K, n, seed, offset, noise_std);
+    if (rc) return rc;
+    NVQ_REQUIRE(out != nullptr && trim >= 0, "fed_trimmed_aggregate: out / trim = %d", trim);
     NVQ_REQUIRE(aligned8(weights), "fed_trimmed_aggregate: weights must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = aligned16(clients) && (stride & 3) == 0 && (base == nullptr || aligned16(base)) && aligned16(out);
+    const bool vec = fed_vec(clients, stride, base, out);
     const dim3 grid(flat_blocks(n)), block(256);
     const int kmax = K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64;
-    int rc = with_consts("fed_trimmed_aggregate", [&](auto KM, auto V, auto B, auto N) {
+    rc = with_consts("fed_trimmed_aggregate", [&](auto KM, auto V, auto B, auto N) {
         hipLaunchKernelGGL((fed_trimmed_kernel<V(), B(), N(), KM()>), grid, block, 0, s, clients, stride, K, base, weights, trim,
                            server_lr, noise_std, seed, offset, n, out);
     }, one_of<8, 16, 32, 64>(kmax), vec, base != nullptr, noise_std != 0.f);

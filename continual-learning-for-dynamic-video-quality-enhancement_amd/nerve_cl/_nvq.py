@@ -1546,18 +1546,21 @@ def fed_workspace_bytes(K: int, n: int) -> int:
 
 
 def _fed_rows(clients: torch.Tensor, n: int) -> "tuple[int, int]":
-    assert clients.dtype == torch.float32 and clients.dim() == 2 and clients.stride(1) == 1, "clients: a [K][stride] fp32 matrix"
-    # (the row stride of a one-row matrix is arbitrary in torch and never used by the kernels: any value >= n serves)
-    K, stride = clients.shape[0], (clients.stride(0) if clients.shape[0] > 1 else max(clients.stride(0), clients.shape[1]))
-    assert 1 <= K <= FED_MAX_CLIENTS and stride >= n >= 0 and clients.shape[1] >= n, "clients: 1 .. 64 rows of at least n floats"
-    require_device(clients)
-    return K, stride
+    """(K, row stride) of the client matrix"""
+    assert 1 <= clients.shape[0] <= FED_MAX_CLIENTS and n >= 0, "clients: 1 .. 64 rows"
+    return clients.shape[0], _rows_stride(clients, n, "clients")
+
+
+def _fed_vectors(K: int, n: int, weights=None, sq=None, out=None, base=None) -> None:
+    """the per-client tables (float64, K values) and the vectors (fp32, n floats) of an aggregate wrapper, each if given"""
+    assert all(t is None or (t.dtype == torch.float64 and t.numel() >= K) for t in (weights, sq)), "weights / sq: K float64 values"
+    assert all(t is None or (t.dtype == torch.float32 and t.numel() >= n) for t in (out, base)), "out / base: fp32 vectors of n floats"
 
 
 def fed_delta_norms(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], sq: torch.Tensor, ws: torch.Tensor) -> None:
     """sq[k] = sum_i (clients[k, i] - base[i])^2 over the first n columns, in double (base None: the rows' own norms)"""
     K, stride = _fed_rows(clients, n)
-    assert sq.dtype == torch.float64 and sq.numel() >= K and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    _fed_vectors(K, n, sq=sq, base=base)
     check(lib().nvq_fed_delta_norms(clients.data_ptr(), stride, K, ptr(base), n, ptr(sq), ptr(ws), ws.numel() * 4, stream()),
           "nvq_fed_delta_norms")
 
@@ -1568,8 +1571,7 @@ def fed_aggregate(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], w
     """out[i] = base[i] + server_lr * sum_k c_k (clients[k, i] - base[i]) + noise_std * z_i (nvq_fed_aggregate); ``out`` may be
     ``base``"""
     K, stride = _fed_rows(clients, n)
-    assert weights.dtype == torch.float64 and weights.numel() >= K and (sq is None or (sq.dtype == torch.float64 and sq.numel() >= K))
-    assert out.dtype == torch.float32 and out.numel() >= n and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    _fed_vectors(K, n, weights, sq, out, base)
     check(lib().nvq_fed_aggregate(clients.data_ptr(), stride, K, ptr(base), ptr(weights), ptr(sq), float(clip_norm),
                                   float(server_lr), float(noise_std), int(seed), int(offset), n, ptr(out), stream()),
           "nvq_fed_aggregate")
@@ -1659,15 +1661,13 @@ def fed_aggregate_clusters(clients: torch.Tensor, n: int, labels: torch.Tensor, 
     ``bases``: None (zeros), a vector (one shared base) or a [C][stride] matrix (one base per cluster; ``out`` may be it)."""
     K, stride = _fed_rows(clients, n)
     assert labels.dtype == torch.int32 and labels.numel() >= K and 1 <= C <= CLUSTER_MAX
-    assert weights.dtype == torch.float64 and weights.numel() >= K and (sq is None or (sq.dtype == torch.float64 and sq.numel() >= K))
     assert out.shape[0] == C, "out: one row per cluster"
     out_stride = _rows_stride(out, n, "out")
     base_stride = 0
     if bases is not None and bases.dim() == 2:
         assert bases.shape[0] == C, "bases: one row per cluster"
         base_stride = _rows_stride(bases, n, "bases")
-    elif bases is not None:
-        assert bases.dtype == torch.float32 and bases.numel() >= n
+    _fed_vectors(K, n, weights, sq, base=bases if base_stride == 0 else None)
     check(lib().nvq_fed_aggregate_clusters(clients.data_ptr(), stride, K, ptr(labels), int(C),
                                            None if bases is None else bases.data_ptr(), base_stride, ptr(weights), ptr(sq),
                                            float(clip_norm), float(server_lr), float(noise_std), int(seed), int(offset), n,
@@ -1684,8 +1684,7 @@ def fed_trimmed_aggregate(clients: torch.Tensor, n: int, base: Optional[torch.Te
     """out[i] = base[i] + server_lr * (trimmed mean over the live rows of clients[k, i] - base[i]) + noise_std * z_i
     (nvq_fed_trimmed_aggregate); a row is live when ``weights`` is None or weights[k] > 0; ``out`` may be ``base``"""
     K, stride = _fed_rows(clients, n)
-    assert weights is None or (weights.dtype == torch.float64 and weights.numel() >= K)
-    assert out.dtype == torch.float32 and out.numel() >= n and (base is None or (base.dtype == torch.float32 and base.numel() >= n))
+    _fed_vectors(K, n, weights, None, out, base)
     check(lib().nvq_fed_trimmed_aggregate(clients.data_ptr(), stride, K, ptr(base), ptr(weights), int(trim), float(server_lr),
                                           float(noise_std), int(seed), int(offset), n, ptr(out), stream()),
           "nvq_fed_trimmed_aggregate")

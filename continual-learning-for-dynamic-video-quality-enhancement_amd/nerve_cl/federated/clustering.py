@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from nerve_cl import _engine, _nvq
-from nerve_cl.federated import _philox
+from nerve_cl.federated._flat import check_clients, device_weights, finish_cpu
 
 __all__ = ["UserProfile", "UserClustering", "ClusterResult", "update_gram", "update_similarity", "cluster_updates",
            "aggregate_flat_clustered"]
@@ -134,19 +134,10 @@ def _gram_workspace(dev, K: int, n: int) -> torch.Tensor:
     return ws
 
 
-def _check_clients(clients: torch.Tensor, base: Optional[torch.Tensor]) -> None:
-    if clients.dim() != 2 or clients.dtype != torch.float32:
-        raise ValueError("clients: a [K, n] float32 matrix")
-    if not 1 <= clients.shape[0] <= _nvq.FED_MAX_CLIENTS:
-        raise ValueError(f"clients: 1 .. {_nvq.FED_MAX_CLIENTS} rows")
-    if base is not None and (base.dtype != torch.float32 or base.numel() != clients.shape[1]):
-        raise ValueError("base: a float32 vector of n elements")
-
-
 def update_gram(clients: torch.Tensor, base: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``G[i, j] = sum_t (clients[i, t] - base[t]) (clients[j, t] - base[t])`` as a ``(K, K)`` float64 tensor on the clients' device
     (``base`` None: zeros).  On the GPU one ``nvq_fed_update_gram`` (fp64 matrix cores, symmetric bit for bit), nothing read back."""
-    _check_clients(clients, base)
+    check_clients(clients, base)
     K, n = clients.shape
     if clients.is_cuda:
         dev = clients.device
@@ -174,7 +165,7 @@ def cluster_updates(clients: torch.Tensor, num_clusters: int, base: Optional[tor
 
     On the GPU three launches (the Gram pass, its finishing launch, ``nvq_cluster_gram_kmeans``) and no synchronisation: every
     field of the result is a device tensor.  CPU tensors take the float64 Lloyd's of this module on the explicit updates."""
-    _check_clients(clients, base)
+    check_clients(clients, base)
     K, n = clients.shape
     C = int(num_clusters)
     if not 1 <= C <= min(_nvq.CLUSTER_MAX, K):
@@ -217,8 +208,7 @@ def aggregate_flat_clustered(clients: torch.Tensor, weights, labels, num_cluster
     On the GPU: ``nvq_fed_delta_norms`` (only with ``clip_norm``) and one ``nvq_fed_aggregate_clusters`` that reads every client row
     once; ``weights`` (float64) and ``labels`` (int32) given as device tensors are used as they are and nothing is read back.
     CPU tensors take the same formula in float64 torch operations."""
-    if clients.dim() != 2 or clients.dtype != torch.float32:
-        raise ValueError("clients: a [K, n] float32 matrix")
+    check_clients(clients)
     K, n = clients.shape
     C = int(num_clusters)
     if not 1 <= C <= _nvq.CLUSTER_MAX:
@@ -228,17 +218,16 @@ def aggregate_flat_clustered(clients: torch.Tensor, weights, labels, num_cluster
         raise ValueError("bases: a vector of n floats or a (C, n) matrix")
     if clip_norm is not None and not shared:
         raise ValueError("clip_norm needs one shared base: per-cluster bases have no single update norm")
-    if not isinstance(weights, torch.Tensor):
+    dev, host = clients.device, None
+    if not isinstance(weights, torch.Tensor):          # zeros are fine here (a cluster may be empty): not host_weights' contracts
         host = [float(w) for w in weights]
         if len(host) != K or any(w < 0 for w in host):
             raise ValueError("weights: K non-negative numbers")
-        weights = torch.tensor(host, dtype=torch.float64)
     if not isinstance(labels, torch.Tensor):
         labels = torch.tensor([int(v) for v in labels], dtype=torch.int32)
+    weights = device_weights(weights, host, dev).to(device=dev, dtype=torch.float64)
     if labels.numel() != K or weights.numel() != K:
         raise ValueError("labels and weights: one per client")
-    dev = clients.device
-    weights = weights.to(device=dev, dtype=torch.float64)
     labels = labels.to(device=dev, dtype=torch.int32)
     if out is None:
         out = torch.empty(C, n, dtype=torch.float32, device=dev)
@@ -254,7 +243,7 @@ def aggregate_flat_clustered(clients: torch.Tensor, weights, labels, num_cluster
                                         server_lr=server_lr, noise_std=noise_std, seed=seed, offset=offset)
         return out
     x = clients.double()
-    rows = []
+    rows = torch.empty(C, n, dtype=torch.float32)      # every base is read before out, which may be it, is written
     for c in range(C):
         b = torch.zeros(n, dtype=torch.float64) if bases is None else (bases if shared else bases[c]).double()
         member = labels == c
@@ -266,11 +255,8 @@ def aggregate_flat_clustered(clients: torch.Tensor, weights, labels, num_cluster
             if clip_norm is not None:
                 coef = coef * torch.clamp(clip_norm / (d.pow(2).sum(1).sqrt() + 1e-6), max=1.0)
             v = b + server_lr * (coef.view(-1, 1) * d).sum(0)
-        v = v.to(torch.float32)
-        if noise_std != 0.0:
-            v = (v.double() + noise_std * torch.from_numpy(_philox.normals(seed, offset + c, n))).to(torch.float32)
-        rows.append(v)
-    out.copy_(torch.stack(rows))
+        finish_cpu(v, noise_std, seed, offset + c, rows[c])
+    out.copy_(rows)
     return out
 
 

@@ -20,46 +20,17 @@ On CUDA tensors these are HIP kernels and nothing is read back; CPU tensors take
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Optional
+from typing import NamedTuple, Optional
 
 import torch
 
 from nerve_cl import _nvq
-from nerve_cl.federated import _philox
+from nerve_cl.federated._flat import check_clients, device_weights, finish_cpu, host_weights
 from nerve_cl.federated.clustering import update_gram
 
 __all__ = ["KrumResult", "aggregate_flat_trimmed", "aggregate_flat_median", "krum_select", "krum_aggregate_flat"]
 
 TRIM_MEDIAN = _nvq.FED_TRIM_MEDIAN
-
-
-def _check_clients(clients: torch.Tensor, base: Optional[torch.Tensor]) -> None:
-    if clients.dim() != 2 or clients.dtype != torch.float32:
-        raise ValueError("clients: a [K, n] float32 matrix")
-    if not 1 <= clients.shape[0] <= _nvq.FED_MAX_CLIENTS:
-        raise ValueError(f"clients: 1 .. {_nvq.FED_MAX_CLIENTS} rows")
-    if base is not None and (base.dtype != torch.float32 or base.numel() != clients.shape[1]):
-        raise ValueError("base: a float32 vector of n elements")
-
-
-def _host_weights(weights, K: int, what: str) -> Optional[List[float]]:
-    """the weights as host floats, checked, or None when they are None or live on the device (then they are used as they are)"""
-    if weights is None or (isinstance(weights, torch.Tensor) and weights.is_cuda):
-        if weights is not None and (weights.dtype != torch.float64 or weights.numel() != K):
-            raise ValueError(f"{what}: device weights are {K} float64 values")
-        return None
-    host = [float(w) for w in (weights.tolist() if isinstance(weights, torch.Tensor) else weights)]
-    if len(host) != K:
-        raise ValueError(f"{what}: {len(host)} weights for {K} clients")
-    if not any(w > 0 for w in host):
-        raise ValueError(f"{what}: no weight is positive, so no row is live")
-    return host
-
-
-def _device_weights(weights, host: Optional[List[float]], dev) -> Optional[torch.Tensor]:
-    if host is not None:
-        return torch.tensor(host, dtype=torch.float64).to(dev)
-    return weights
 
 
 def aggregate_flat_trimmed(clients: torch.Tensor, trim: int, weights=None, base: Optional[torch.Tensor] = None,
@@ -73,18 +44,18 @@ def aggregate_flat_trimmed(clients: torch.Tensor, trim: int, weights=None, base:
     ``weights`` only say which rows are live (None: all): a sequence or CPU tensor is checked on the host and raises ``ValueError``
     without a positive entry; a float64 tensor on the device is used as it is.  On the GPU one ``nvq_fed_trimmed_aggregate``,
     nothing read back."""
-    _check_clients(clients, base)
+    check_clients(clients, base)
     K, n = clients.shape
     trim = int(trim)
     if trim < 0:
         raise ValueError(f"invalid trim: {trim}")
-    host = _host_weights(weights, K, "aggregate_flat_trimmed")
+    host = host_weights(weights, K, "aggregate_flat_trimmed", allow_none=True, need="live")
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=clients.device)
     if clients.is_cuda:
         dev = clients.device
         with _nvq.device_guard(dev):
-            _nvq.fed_trimmed_aggregate(clients, n, base, _device_weights(weights, host, dev), trim, out, server_lr=server_lr,
+            _nvq.fed_trimmed_aggregate(clients, n, base, device_weights(weights, host, dev), trim, out, server_lr=server_lr,
                                        noise_std=noise_std, seed=seed, offset=offset)
         return out
     if host is None and weights is not None:
@@ -98,12 +69,7 @@ def aggregate_flat_trimmed(clients: torch.Tensor, trim: int, weights=None, base:
     for j in range(t, m - t):
         a = a + d[j]
     a = a / (m - 2 * t)
-    v = (b + server_lr * a).to(torch.float32)
-    if noise_std != 0.0:
-        z = torch.from_numpy(_philox.normals(seed, offset, n))
-        v = (v.double() + noise_std * z).to(torch.float32)
-    out.copy_(v)
-    return out
+    return finish_cpu(b + server_lr * a, noise_std, seed, offset, out)
 
 
 def aggregate_flat_median(clients: torch.Tensor, weights=None, base: Optional[torch.Tensor] = None, server_lr: float = 1.0,
@@ -138,7 +104,7 @@ def krum_select(gram: torch.Tensor, num_byzantine: int, num_selected: int = 1, w
         raise ValueError(f"invalid num_byzantine: {f}")
     if q < 1:
         raise ValueError(f"invalid num_selected: {q}")
-    host = _host_weights(weights, K, "krum_select")              # None: no weights, or weights on the device (used as they are)
+    host = host_weights(weights, K, "krum_select", allow_none=True, need="live")   # None: no weights, or used as they are
     if host is None and weights is not None and not gram.is_cuda:
         raise ValueError("krum_select: device weights with a Gram matrix on the CPU")
     if weights is None or host is not None:
@@ -151,7 +117,7 @@ def krum_select(gram: torch.Tensor, num_byzantine: int, num_selected: int = 1, w
         scores = torch.empty(K, dtype=torch.float64, device=dev)
         order = torch.empty(K, dtype=torch.int32, device=dev)
         with _nvq.device_guard(dev):
-            _nvq.fed_krum_select(gram.contiguous(), K, _device_weights(weights, host, dev), f, q, out_w, scores, order)
+            _nvq.fed_krum_select(gram.contiguous(), K, device_weights(weights, host, dev), f, q, out_w, scores, order)
         return KrumResult(out_w, scores, order)
     live = [k for k in range(K) if host is None or host[k] > 0]
     m = len(live)
@@ -181,11 +147,11 @@ def krum_aggregate_flat(clients: torch.Tensor, num_byzantine: int, num_selected:
     ``krum_select`` on ``update_gram(clients, base)`` and averaged by ``aggregate_flat_trimmed`` with ``trim = 0`` and the selection
     as weights.  On the GPU four launches (the Gram pass and its finishing launch, the selection, the mean) and no synchronisation.
     ``out`` may be ``base``."""
-    _check_clients(clients, base)
+    check_clients(clients, base)
     K = clients.shape[0]
-    host = _host_weights(weights, K, "krum_aggregate_flat")
+    host = host_weights(weights, K, "krum_aggregate_flat", allow_none=True, need="live")
     if clients.is_cuda:
-        weights = _device_weights(weights, host, clients.device)
+        weights = device_weights(weights, host, clients.device)
         if host is not None and sum(w > 0 for w in host) < int(num_byzantine) + 3:
             raise ValueError(f"krum_aggregate_flat: {sum(w > 0 for w in host)} live rows with num_byzantine = {num_byzantine}: "
                              "Krum needs at least f + 3")

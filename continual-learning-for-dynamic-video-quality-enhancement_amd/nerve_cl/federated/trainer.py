@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from nerve_cl import _engine, _nvq
 from nerve_cl._bucket import segments_of
-from nerve_cl.federated import _philox
+from nerve_cl.federated._flat import check_clients, device_weights, finish_cpu, host_weights
 from nerve_cl.federated.privacy import DPOptimizer, PrivacyConfig, _Seg
 
 __all__ = ["aggregate_flat", "fedavg", "weighted_average", "FederatedTrainer", "start_server", "AGGREGATORS"]
@@ -29,12 +29,6 @@ AGGREGATORS = ("fedavg", "median", "trimmed_mean", "krum", "multi_krum")
 
 
 # ----------------------------------------------------------------------------------------------- aggregation
-def _host_weights(weights) -> Optional[List[float]]:
-    if isinstance(weights, torch.Tensor):
-        return None if weights.is_cuda else [float(w) for w in weights.tolist()]
-    return [float(w) for w in weights]
-
-
 def aggregate_flat(clients: torch.Tensor, weights, base: Optional[torch.Tensor] = None, clip_norm: Optional[float] = None,
                    server_lr: float = 1.0, noise_std: float = 0.0, seed: int = 0, offset: int = 0,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -46,21 +40,14 @@ def aggregate_flat(clients: torch.Tensor, weights, base: Optional[torch.Tensor] 
     On the GPU: ``nvq_fed_delta_norms`` (only with ``clip_norm``) and ``nvq_fed_aggregate``, nothing read back; ``weights`` given
     as a float64 tensor on the device is used as it is (all-zero weights then give NaN), otherwise it is checked on the host and
     all-zero weights raise ``ValueError``.  CPU tensors take the same formula in float64 torch operations."""
-    if clients.dim() != 2 or clients.dtype != torch.float32:
-        raise ValueError("clients: a [K, n] float32 matrix")
+    check_clients(clients, base)
     K, n = clients.shape
-    host = _host_weights(weights)
-    if host is not None:
-        if len(host) != K:
-            raise ValueError(f"{len(host)} weights for {K} clients")
-        if any(w < 0 for w in host) or not sum(host) > 0:
-            raise ValueError("aggregate_flat: the weights are non-negative and not all zero")
+    host = host_weights(weights, K, "aggregate_flat", allow_none=False, need="sum")
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=clients.device)
     if clients.is_cuda:
         dev = clients.device
-        if host is not None:
-            weights = torch.tensor(host, dtype=torch.float64).to(dev)
+        weights = device_weights(weights, host, dev)
         with _nvq.device_guard(dev):
             sq = None
             if clip_norm is not None:
@@ -76,12 +63,7 @@ def aggregate_flat(clients: torch.Tensor, weights, base: Optional[torch.Tensor] 
     c = w / w.sum()
     if clip_norm is not None:
         c = c * torch.clamp(clip_norm / (d.pow(2).sum(1).sqrt() + 1e-6), max=1.0)
-    v = (b[0] + server_lr * (c.view(K, 1) * d).sum(0)).to(torch.float32)
-    if noise_std != 0.0:
-        z = torch.from_numpy(_philox.normals(seed, offset, n))
-        v = (v.double() + noise_std * z).to(torch.float32)
-    out.copy_(v)
-    return out
+    return finish_cpu(b[0] + server_lr * (c.view(K, 1) * d).sum(0), noise_std, seed, offset, out)
 
 
 def _is_float(t: torch.Tensor) -> bool:
@@ -332,34 +314,49 @@ class FederatedTrainer:
 
     # ------------------------------------------------------------------ a round
     @torch.no_grad()
-    def _aggregate(self, plan, K: int) -> None:
-        w = plan["weights"][:K]
-        clip = self.update_clip
-        plain = clip is None and self.update_noise == 0.0 and self.server_lr == 1.0
-        for j, (net, rows, snap) in enumerate(zip(plan["nets"], plan["rows"], plan["snaps"])):
+    def _aggregate(self, plan, K: int, w: torch.Tensor, step) -> None:
+        """The walk every rule shares: each HIP-backed network's rows into its flat buffer (network j's noise stream in a round is
+        ``global_round * (len(nets) + 1) + j``), the rest matrix into the packed statistics and loose parameters, the integer buffers'
+        mean under ``w``.  ``step(rows, n, base, out, *, full, offset)`` aggregates one matrix; ``full``: with the update clip, server
+        rate and noise, else the rule alone."""
+        nets, pack = plan["nets"], plan["pack"]
+        plain = self.update_clip is None and self.update_noise == 0.0 and self.server_lr == 1.0
+        for j, (net, rows, snap) in enumerate(zip(nets, plan["rows"], plan["snaps"])):
             flat = net.flat_theta()
-            n = flat.numel()
-            with _nvq.device_guard(plan["dev"]):
-                sq = None
-                if clip is not None:
-                    sq = plan["sq"]
-                    _nvq.fed_delta_norms(rows[:K], n, snap, sq, _engine.workspace(plan["dev"]))
-                _nvq.fed_aggregate(rows[:K], n, None if plain else snap, w, sq, flat, clip_norm=clip or 0.0,
-                                   server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed,
-                                   offset=self.global_round * (len(plan["nets"]) + 1) + j)
-        pack = plan["pack"]
+            step(rows[:K], flat.numel(), None if plain else snap, flat, full=True, offset=self.global_round * (len(nets) + 1) + j)
         if pack.total:
-            rest = plan["rest_rows"][:K]
-            if plan["nets"]:                           # next to the flat buffers: statistics and loose parameters, a plain mean
-                with _nvq.device_guard(plan["dev"]):
-                    _nvq.fed_aggregate(rest, rest.shape[1], None, w, None, plan["rest_snap"])
+            rest, snap = plan["rest_rows"][:K], plan["rest_snap"]
+            if nets:                                   # next to the flat buffers: statistics and loose parameters, the rule alone
+                step(rest, rest.shape[1], None, snap, full=False, offset=0)
             else:                                      # no HIP-backed network (a plain module, any device): everything is here
-                aggregate_flat(rest, w if w.is_cuda else w.tolist(), base=None if plain else plan["rest_snap"].clone(),
-                               clip_norm=clip, server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed,
-                               offset=self.global_round, out=plan["rest_snap"])
-            pack.unpack(plan["rest_snap"])
+                step(rest, rest.shape[1], None if plain else snap, snap, full=True, offset=self.global_round)
+            pack.unpack(snap)
         for t, rows in zip(plan["ints"], plan["int_rows"]):
             t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+
+    def _step_options(self, full: bool, offset: int) -> Dict[str, object]:
+        """the server rate and the noise stream of a ``full`` step as keywords; none for the rule alone"""
+        return dict(server_lr=self.server_lr, noise_std=self.update_noise, seed=self._noise_seed, offset=offset) if full else {}
+
+    def _aggregate_fedavg(self, plan, K: int) -> None:
+        """FedAvg: per matrix one ``nvq_fed_delta_norms`` (only with ``update_clip``) and one ``nvq_fed_aggregate``"""
+        w, clip, dev = plan["weights"][:K], self.update_clip, plan["dev"]
+
+        def step(rows, n, base, out, *, full, offset):
+            kw = self._step_options(full, offset)
+            if not plan["nets"]:                       # the public function: the CPU formula, or the same two launches
+                aggregate_flat(rows, w if w.is_cuda else w.tolist(), base=None if base is None else base.clone(), clip_norm=clip,
+                               out=out, **kw)
+                return
+            with _nvq.device_guard(dev):
+                sq = None
+                if full and clip is not None:
+                    sq = plan["sq"]
+                    _nvq.fed_delta_norms(rows, n, base, sq, _engine.workspace(dev))
+                    kw["clip_norm"] = clip
+                _nvq.fed_aggregate(rows, n, base, w, sq, out, **kw)
+
+        self._aggregate(plan, K, w, step)
 
     # ------------------------------------------------------------------ robust rounds
     def _robust_plan(self, counts: List[int]) -> Tuple[int, int]:
@@ -387,10 +384,7 @@ class FederatedTrainer:
         the selection."""
         from nerve_cl.federated.clustering import update_gram
         from nerve_cl.federated.robust import aggregate_flat_trimmed, krum_select
-        w = plan["weights"][:K]
-        dev, nets, pack = plan["dev"], plan["nets"], plan["pack"]
-        plain = self.update_noise == 0.0 and self.server_lr == 1.0
-        selected = None
+        w, pack, selected = plan["weights"][:K], plan["pack"], None
         if q:
             gram = None
             for rows, snap in zip(plan["rows"], plan["snaps"]):
@@ -402,24 +396,11 @@ class FederatedTrainer:
             if gram is None:                           # a model without floating state: nothing to tell the clients apart by
                 gram = torch.zeros(K, K, dtype=torch.float64, device=w.device)
             w = selected = krum_select(gram, self.num_byzantine, q, weights=w).weights
-        for j, (net, rows, snap) in enumerate(zip(nets, plan["rows"], plan["snaps"])):
-            flat = net.flat_theta()
-            with _nvq.device_guard(dev):
-                _nvq.fed_trimmed_aggregate(rows[:K], flat.numel(), None if plain else snap, w, trim, flat, server_lr=self.server_lr,
-                                           noise_std=self.update_noise, seed=self._noise_seed,
-                                           offset=self.global_round * (len(nets) + 1) + j)
-        if pack.total:
-            rest = plan["rest_rows"][:K]
-            if nets:                                   # next to the flat buffers: statistics and loose parameters, no rate, no noise
-                with _nvq.device_guard(dev):
-                    _nvq.fed_trimmed_aggregate(rest, rest.shape[1], None, w, trim, plan["rest_snap"])
-            else:                                      # no HIP-backed network (a plain module, any device): everything is here
-                aggregate_flat_trimmed(rest, trim, weights=w, base=None if plain else plan["rest_snap"], server_lr=self.server_lr,
-                                       noise_std=self.update_noise, seed=self._noise_seed, offset=self.global_round,
-                                       out=plan["rest_snap"])
-            pack.unpack(plan["rest_snap"])
-        for t, rows in zip(plan["ints"], plan["int_rows"]):
-            t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+
+        def step(rows, n, base, out, *, full, offset):     # on the device one nvq_fed_trimmed_aggregate, nothing read back
+            aggregate_flat_trimmed(rows, trim, weights=w, base=base, out=out, **self._step_options(full, offset))
+
+        self._aggregate(plan, K, w, step)
         return selected
 
     # ------------------------------------------------------------------ clustered rounds
@@ -575,7 +556,7 @@ class FederatedTrainer:
         elif K and robust is not None:
             selection = self._aggregate_robust(plan, K, *robust)
         elif K:
-            self._aggregate(plan, K)
+            self._aggregate_fedavg(plan, K)
         self.global_round += 1
         self.last_selected = selected
         steps = max(sum(counts) * self.local_epochs, 1)

@@ -10,10 +10,11 @@ def kernels(path):
         if m:
             name, body = m.group(1), []
         elif name is not None:
-            body.append(line)
-            if "s_endpgm" in line:
+            if line.startswith(".Lfunc_end"):         # not the first s_endpgm: the compiler lays cold blocks out behind it
                 yield name, body
                 name = None
+            else:
+                body.append(line)
 
 def events(body):
     out, run = [], 0
