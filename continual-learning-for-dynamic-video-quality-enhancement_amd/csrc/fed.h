@@ -1,7 +1,7 @@
 // What the sweeps over a [K, n] client matrix share (DESIGN.md sections 23, 25, 28): the server step, the clip coefficient, the
 // Gaussian-noise epilogue of a quad and of the n % 4 tail, the weighted mean of a set of rows around a base, and the host-side
-// argument checks of the nvq_fed_* entry points.  federated.hip, cluster.hip and robust.hip include this header in place of
-// flat.h and philox.h; a fifth aggregation rule includes it too and writes only what is its own.
+// argument checks of the nvq_fed_* entry points.  federated.hip, cluster.hip, robust.hip and fedopt.hip include this header in
+// place of flat.h and philox.h; a further aggregation rule includes it too and writes only what is its own.
 #pragma once
 #include "flat.h"
 #include "philox.h"
@@ -38,12 +38,11 @@ __device__ __forceinline__ void fed_noise_tail(float& v, float noise_std, long n
     v = fmaf(noise_std, threadIdx.x == 0 ? z.x : (threadIdx.x == 1 ? z.y : z.z), v);
 }
 
-// Quad q of b + lr * sum_m coef[row(m)] (x_row(m) - b) over m0 <= m < m1, plus noise: m ascending, one fma chain per lane
-// of the quad, in double.
-template <bool VEC, bool NOISE, class Row>
-__device__ __forceinline__ float4 fed_mean_quad(const float* __restrict__ clients, long stride, long q, float4 b,
-                                                const double* coef, Row row, int m0, int m1, double lr, float noise_std,
-                                                long seed, long offset) {
+// Quad q of the aggregated update sum_m coef[row(m)] (x_row(m) - b) over m0 <= m < m1, in double and not rounded: m ascending,
+// one fma chain per lane of the quad.
+template <bool VEC, class Row>
+__device__ __forceinline__ double4 fed_delta_quad(const float* __restrict__ clients, long stride, long q, float4 b,
+                                                  const double* coef, Row row, int m0, int m1) {
     double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
     for (int m = m0; m < m1; ++m) {
         const int k = row(m);
@@ -54,7 +53,28 @@ __device__ __forceinline__ float4 fed_mean_quad(const float* __restrict__ client
         az = fma(c, (double)x.z - (double)b.z, az);
         aw = fma(c, (double)x.w - (double)b.w, aw);
     }
-    float4 v = make_float4(fed_mix(ax, b.x, lr), fed_mix(ay, b.y, lr), fed_mix(az, b.z, lr), fed_mix(aw, b.w, lr));
+    return make_double4(ax, ay, az, aw);
+}
+
+// The same for tail element t = 4 nq + threadIdx.x.
+template <class Row>
+__device__ __forceinline__ double fed_delta_tail(const float* __restrict__ clients, long stride, long t, float b,
+                                                 const double* coef, Row row, int m0, int m1) {
+    double a = 0.0;
+    for (int m = m0; m < m1; ++m) {
+        const int k = row(m);
+        a = fma(coef[k], (double)clients[k * stride + t] - (double)b, a);
+    }
+    return a;
+}
+
+// Quad q of b + lr * (fed_delta_quad), plus noise.
+template <bool VEC, bool NOISE, class Row>
+__device__ __forceinline__ float4 fed_mean_quad(const float* __restrict__ clients, long stride, long q, float4 b,
+                                                const double* coef, Row row, int m0, int m1, double lr, float noise_std,
+                                                long seed, long offset) {
+    const double4 a = fed_delta_quad<VEC>(clients, stride, q, b, coef, row, m0, m1);
+    float4 v = make_float4(fed_mix(a.x, b.x, lr), fed_mix(a.y, b.y, lr), fed_mix(a.z, b.z, lr), fed_mix(a.w, b.w, lr));
     fed_noise<NOISE>(v, noise_std, q, seed, offset);
     return v;
 }
@@ -64,14 +84,22 @@ template <bool NOISE, class Row>
 __device__ __forceinline__ float fed_mean_tail(const float* __restrict__ clients, long stride, long t, long nq, float b,
                                                const double* coef, Row row, int m0, int m1, double lr, float noise_std,
                                                long seed, long offset) {
-    double a = 0.0;
-    for (int m = m0; m < m1; ++m) {
-        const int k = row(m);
-        a = fma(coef[k], (double)clients[k * stride + t] - (double)b, a);
-    }
-    float v = fed_mix(a, b, lr);
+    float v = fed_mix(fed_delta_tail(clients, stride, t, b, coef, row, m0, m1), b, lr);
     fed_noise_tail<NOISE>(v, noise_std, nq, seed, offset);
     return v;
+}
+
+// coef[k] = weights[k] / W * fed_clip(sq, k, clip_norm) in shared memory, W the sum of the K weights in index order; ends with
+// the barrier after which every thread may read coef.
+__device__ __forceinline__ void fed_coefficients(double* coef, const double* __restrict__ weights, const double* __restrict__ sq,
+                                                 float clip_norm, int K) {
+    if ((int)threadIdx.x < K) {
+        double W = 0.0;
+        for (int k = 0; k < K; ++k) W += weights[k];
+        const int k = threadIdx.x;
+        coef[k] = weights[k] / W * fed_clip(sq, k, clip_norm);
+    }
+    __syncthreads();
 }
 
 // ------------------------------------------------------------------ host side

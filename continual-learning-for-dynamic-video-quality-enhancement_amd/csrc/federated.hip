@@ -82,13 +82,7 @@ __global__ __launch_bounds__(256) void fed_aggregate_kernel(const float* __restr
                                                             const double* __restrict__ sq, float clip_norm, float server_lr,
                                                             float noise_std, long seed, long offset, long n, float* out) {
     __shared__ double coef[64];
-    if ((int)threadIdx.x < K) {
-        double W = 0.0;
-        for (int k = 0; k < K; ++k) W += weights[k];
-        const int k = threadIdx.x;
-        coef[k] = weights[k] / W * fed_clip(sq, k, clip_norm);
-    }
-    __syncthreads();
+    fed_coefficients(coef, weights, sq, clip_norm, K);
     const auto row = [](int m) { return m; };
     const double lr = (double)server_lr;
     const long nq = n >> 2;

@@ -261,6 +261,9 @@ SIGNATURES = {
     # Byzantine-robust aggregation: trimmed mean / median, Krum selection (csrc/robust.hip)
     "nvq_fed_trimmed_aggregate": (ci, [vp, cl, ci, vp, vp, ci, cf, cf, cl, cl, cl, vp, vp]),
     "nvq_fed_krum_select": (ci, [vp, ci, vp, ci, ci, vp, vp, vp, vp]),
+    # federated optimisation: FedOpt server rules, the FedProx gradient (csrc/fedopt.hip)
+    "nvq_fed_server_opt": (ci, [vp, cl, ci, vp, vp, vp, cf, ci, cf, cf, cf, cf, vp, vp, cf, cl, cl, cl, vp, vp]),
+    "nvq_fed_prox_grad": (ci, [vp, vp, vp, cl, cf, vp]),
     # ABR agent: vectorised environment, fused act, GAE, PPO loss (csrc/abr.hip)
     "nvq_abr_env_reset": (ci, [vp, vp, vp, vp, ci, ci, cl, ci, vp]),
     "nvq_abr_env_step": (ci, [vp, vp, vp, _IP, ci, ci, ci, vp, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -1700,6 +1703,38 @@ def fed_krum_select(gram: torch.Tensor, K: int, weights: Optional[torch.Tensor],
     assert order.dtype == torch.int32 and order.numel() >= K
     check(lib().nvq_fed_krum_select(ptr(gram), int(K), ptr(weights), int(num_byzantine), int(num_selected), ptr(out_weights),
                                     ptr(scores), ptr(order), stream()), "nvq_fed_krum_select")
+
+
+# ----------------------------------------------------------------------------- FedOpt server rules, FedProx (csrc/fedopt.hip)
+FED_OPT_AVGM, FED_OPT_ADAGRAD, FED_OPT_ADAM, FED_OPT_YOGI = 0, 1, 2, 3    # NVQ_FED_OPT_*
+
+
+def fed_server_opt(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], weights: torch.Tensor, sq: Optional[torch.Tensor],
+                   rule: int, m: Optional[torch.Tensor], v: Optional[torch.Tensor], out: torch.Tensor, *, clip_norm: float = 0.0,
+                   server_lr: float = 1.0, beta1: float = 0.9, beta2: float = 0.99, tau: float = 1e-3, noise_std: float = 0.0,
+                   seed: int = 0, offset: int = 0) -> None:
+    """out[i] = base[i] + server_lr * step_i + noise_std * z_i, where step is server momentum (FED_OPT_AVGM), Adagrad, Adam or Yogi
+    on the pseudo-gradient D_i = sum_k c_k (clients[k, i] - base[i]) and the moments ``m``, ``v`` (fp32, n floats) are stepped in
+    place (nvq_fed_server_opt); ``out`` may be ``base``, ``v`` may be None for FED_OPT_AVGM.  The library checks K, the rule, the
+    hyper-parameters and the required pointers."""
+    for what, t in (("clients", clients), ("base", base), ("m", m), ("v", v), ("out", out)):
+        if t is not None:
+            require_device(t, f"nvq_fed_server_opt: {what}")
+    K, stride = clients.shape[0], _rows_stride(clients, n, "clients")
+    _fed_vectors(K, n, weights, sq, out, base)
+    assert all(t is None or (t.dtype == torch.float32 and t.numel() >= n) for t in (m, v)), "m / v: fp32 vectors of n floats"
+    check(lib().nvq_fed_server_opt(clients.data_ptr(), stride, K, ptr(base), ptr(weights), ptr(sq), float(clip_norm), int(rule),
+                                   float(server_lr), float(beta1), float(beta2), float(tau), ptr(m), ptr(v), float(noise_std),
+                                   int(seed), int(offset), n, ptr(out), stream()), "nvq_fed_server_opt")
+
+
+def fed_prox_grad(grad: torch.Tensor, theta: torch.Tensor, anchor: torch.Tensor, mu: float) -> None:
+    """grad += mu * (theta - anchor) over flat fp32 buffers of grad.numel() floats, in double, rounded once (nvq_fed_prox_grad)"""
+    for what, t in (("grad", grad), ("theta", theta), ("anchor", anchor)):
+        require_device(t, f"nvq_fed_prox_grad: {what}")
+    n = grad.numel()
+    assert all(t.dtype == torch.float32 and t.numel() >= n for t in (grad, theta, anchor)), "grad / theta / anchor: fp32, n floats"
+    check(lib().nvq_fed_prox_grad(ptr(grad), ptr(theta), ptr(anchor), n, float(mu), stream()), "nvq_fed_prox_grad")
 
 
 # ----------------------------------------------------------------------------- ABR agent (csrc/abr.hip)

@@ -21,6 +21,7 @@ import torch.nn as nn
 from nerve_cl import _engine, _nvq
 from nerve_cl._bucket import segments_of
 from nerve_cl.federated._flat import check_clients, device_weights, finish_cpu, host_weights
+from nerve_cl.federated.fedopt import ServerOptimizer
 from nerve_cl.federated.privacy import DPOptimizer, PrivacyConfig, _Seg
 
 __all__ = ["aggregate_flat", "fedavg", "weighted_average", "FederatedTrainer", "start_server", "AGGREGATORS"]
@@ -151,7 +152,8 @@ class _Pack:
 class FederatedTrainer:
     """``FederatedTrainer(model, num_clients=10, clients_per_round=5, local_epochs=5, *, lr=1e-4, batch_size=16, loss=None,
     privacy=None, update_clip=None, update_noise=0.0, server_lr=1.0, optimizer_impl="torch", seed=None, aggregator="fedavg",
-    trim_ratio=0.1, num_byzantine=0, num_selected=None, after_client=None)``
+    trim_ratio=0.1, num_byzantine=0, num_selected=None, after_client=None, server_optimizer=None, server_betas=(0.9, 0.99),
+    server_tau=1e-3, prox_mu=0.0)``
 
     ``model(inputs) -> outputs`` is trained on every client's ``(inputs, targets)`` (``set_client_data``) with a fresh
     ``AdamW(lr)`` for ``local_epochs`` passes in batches of ``batch_size``, taken in order; ``loss`` defaults to ``nn.MSELoss()``
@@ -180,6 +182,24 @@ class FederatedTrainer:
     sample-weighted one.  ``after_client(client_id, model)`` is called under ``no_grad`` after a client's local training and before
     its weights are copied into its row: the hook with which a script or a test inspects or poisons a client.
 
+    ``server_optimizer`` (``server_betas=(0.9, 0.99)``, ``server_tau=1e-3``): one of ``SERVER_OPTIMIZERS`` (``"fedavgm"``,
+    ``"fedadagrad"``, ``"fedadam"``, ``"fedyogi"``: FedOpt, ``nerve_cl.federated.fedopt``; no clusters).  The
+    aggregated update is the pseudo-gradient of a server optimizer whose learning rate is ``server_lr``.  BEWARE: an adaptive rule
+    moves every coordinate by about ``server_lr`` per round; the default 1.0 is a FedAvg value, not an Adam value (try 1e-3 ..
+    1e-1).  Each HIP-backed network's matrix takes ``nvq_fed_server_opt`` in place of ``nvq_fed_aggregate`` (still one launch, two
+    with ``update_clip``).  With a robust ``aggregator`` the rule first runs alone into a persistent scratch vector and the ``K =
+    1`` form of the kernel steps from the snapshot towards it with the round's noise: the pseudo-gradient is then that of the fp32
+    aggregate.  The server optimizer steps parameters only.  BatchNorm statistics and integer buffers always take the plain rule
+    (next to HIP-backed networks the rest matrix does so as a whole, its loose parameters included); for a model without
+    HIP-backed networks the floating parameters are then packed first and the floating buffers after them, and only the
+    parameters' columns take the server step (without ``server_optimizer`` the packing stays in state-dict order).
+    ``server_state_dict()`` / ``load_server_state_dict()`` carry the moments.
+
+    ``prox_mu > 0`` is FedProx: after ``loss.backward()`` and before the (DP) optimizer step every trainable parameter's gradient
+    gains ``prox_mu * (theta - theta_restored)``, ``theta_restored`` being what the client was reset to (the round snapshot, or its
+    cluster's model).  A bucketed network whose gradients are its bucket takes one ``nvq_fed_prox_grad``; loose parameters,
+    networks with frozen layers and CPU modules one ``add_`` per parameter.  ``prox_mu = 0`` launches nothing.
+
     On the GPU the weights of every HIP-backed network inside ``model`` are one flat buffer: the clients' results are the rows of a
     persistent ``[clients_per_round, n]`` matrix and a round ends with one ``nvq_fed_delta_norms`` (only with ``update_clip``) and
     one ``nvq_fed_aggregate`` writing into ``flat_theta()``.  Everything else in the state dict (BatchNorm statistics, loose
@@ -192,9 +212,16 @@ class FederatedTrainer:
                  update_clip: Optional[float] = None, update_noise: float = 0.0, server_lr: float = 1.0,
                  optimizer_impl: str = "torch", seed: Optional[int] = None, num_clusters: int = 1, cluster_after: int = 0,
                  aggregator: str = "fedavg", trim_ratio: float = 0.1, num_byzantine: int = 0, num_selected: Optional[int] = None,
-                 after_client=None):
+                 after_client=None, server_optimizer: Optional[str] = None, server_betas: Sequence[float] = (0.9, 0.99),
+                 server_tau: float = 1e-3, prox_mu: float = 0.0):
         if not 1 <= num_clusters <= _nvq.CLUSTER_MAX:
             raise ValueError(f"num_clusters: 1 .. {_nvq.CLUSTER_MAX}")
+        if server_optimizer is not None:
+            ServerOptimizer(server_optimizer, server_lr, server_betas, server_tau)     # its checks: ValueError
+            if num_clusters > 1:
+                raise NotImplementedError("server_optimizer with num_clusters > 1: there are no per-cluster server moments")
+        if not prox_mu >= 0.0:
+            raise ValueError(f"invalid prox_mu: {prox_mu}")
         if cluster_after < 0:
             raise ValueError(f"invalid cluster_after: {cluster_after}")
         if num_clusters > 1 and num_clients > _nvq.FED_MAX_CLIENTS:
@@ -234,6 +261,9 @@ class FederatedTrainer:
         self.aggregator, self.trim_ratio = aggregator, float(trim_ratio)
         self.num_byzantine, self.num_selected = int(num_byzantine), num_selected
         self.after_client = after_client
+        self.server_optimizer, self.prox_mu = server_optimizer, float(prox_mu)
+        self.server_betas, self.server_tau = (float(server_betas[0]), float(server_betas[1])), float(server_tau)
+        self._server_opts: List[ServerOptimizer] = []         # one per stepped parameter vector, in the order of _aggregate
         self.seed = seed
         self._rng = random.Random(seed) if seed is not None else random
         self._noise_seed = random.Random(seed).getrandbits(62) if seed is not None else random.getrandbits(62)
@@ -258,14 +288,24 @@ class FederatedTrainer:
         nets = [sg.net for sg in segs if sg.net is not None] if dev.type == "cuda" else []
         flat_names = {n for sg in segs if sg.net is not None and dev.type == "cuda" for n in sg.names}
         sd = model.state_dict()                       # detached tensors that share the parameters' and buffers' memory
-        rest_f = [t for k, t in sd.items() if k not in flat_names and _is_float(t)]
+        rest_names = [k for k, t in sd.items() if k not in flat_names and _is_float(t)]
+        params = dict(model.named_parameters())
+        n_params = 0
+        if self.server_optimizer is not None and not nets:     # the server optimizer steps parameters only: they come first
+            first = [k for k in rest_names if k in params]
+            rest_names = first + [k for k in rest_names if k not in params]
+            n_params = _Pack([sd[k] for k in first]).total
+        rest_f = [sd[k] for k in rest_names]
         rest_i = [t for k, t in sd.items() if k not in flat_names and not _is_float(t)]
         K = self.clients_per_round if self.num_clusters == 1 else max(self.clients_per_round, self.num_clients)
-        plan = {"dev": dev, "nets": nets, "pack": _Pack(rest_f), "ints": rest_i,
+        plan = {"dev": dev, "nets": nets, "pack": _Pack(rest_f), "ints": rest_i, "n_params": n_params,
+                # FedProx: the trainable parameters of the rest matrix with their place in the pack
+                "prox_rest": [(params[k], i) for i, k in enumerate(rest_names) if k in params and params[k].requires_grad],
                 "rows": [torch.zeros(K, net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
                 "snaps": [torch.zeros(net._bucket_layout()[1], dtype=torch.float32, device=dev) for net in nets],
                 "weights": torch.zeros(K, dtype=torch.float64, device=dev),
                 "sq": torch.zeros(K, dtype=torch.float64, device=dev),
+                "one": torch.ones(1, dtype=torch.float64, device=dev), "scratch": {},
                 "dp_segs": [_Seg(sg) for sg in segs] if self.privacy is not None else None}
         p = plan["pack"]
         plan["rest_rows"] = torch.zeros(K, max(p.total, 4), dtype=torch.float32, device=dev)
@@ -289,8 +329,31 @@ class FederatedTrainer:
         for t, s in zip(plan["ints"], plan["int_snap"]):
             t.copy_(s)
 
-    def _train_client(self, plan, data, seed: int) -> torch.Tensor:
-        """local training on the model in place; returns the sum of batch loss x batch size as a 0-dim tensor on the device"""
+    @torch.no_grad()
+    def _prox(self, plan, anchor) -> None:
+        """FedProx: every trainable parameter's gradient gains ``prox_mu * (theta - anchor)``.  ``anchor``: (one flat vector per
+        HIP-backed network, the packed rest row), what the client was reset to.  A network whose gradients are the views of its
+        last gradient bucket takes one ``nvq_fed_prox_grad`` on the bucket; everything else one ``add_`` per parameter."""
+        mu = self.prox_mu
+        net_anchors, rest_anchor = anchor
+        for net, a in zip(plan["nets"], net_anchors):
+            mask = net.grad_alias_mask()
+            if mask is not None and all(mask):
+                with _nvq.device_guard(plan["dev"]):
+                    _nvq.fed_prox_grad(net._last_grad_bucket, net.flat_theta(), a, mu)
+                continue
+            views = net._bucket_views(a)
+            for n, p in net._named_params():
+                if p.grad is not None:
+                    p.grad.add_(p.detach() - views[n], alpha=mu)
+        views = plan["pack"].views(rest_anchor)
+        for p, i in plan["prox_rest"]:
+            if p.grad is not None:
+                p.grad.add_(p.detach() - views[i], alpha=mu)
+
+    def _train_client(self, plan, data, seed: int, anchor=None) -> torch.Tensor:
+        """local training on the model in place; returns the sum of batch loss x batch size as a 0-dim tensor on the device.
+        ``anchor``: what ``_prox`` pulls towards (only read with ``prox_mu > 0``)."""
         dev = plan["dev"]
         xs, ys = data[0], data[1]
         if xs.device != dev:
@@ -308,6 +371,8 @@ class FederatedTrainer:
                 stepper.zero_grad()
                 loss = self.loss(self.model(x), y)
                 loss.backward()
+                if self.prox_mu > 0.0:
+                    self._prox(plan, anchor)
                 stepper.step()
                 total += loss.detach().float() * len(x)
         return total
@@ -318,21 +383,59 @@ class FederatedTrainer:
         """The walk every rule shares: each HIP-backed network's rows into its flat buffer (network j's noise stream in a round is
         ``global_round * (len(nets) + 1) + j``), the rest matrix into the packed statistics and loose parameters, the integer buffers'
         mean under ``w``.  ``step(rows, n, base, out, *, full, offset)`` aggregates one matrix; ``full``: with the update clip, server
-        rate and noise, else the rule alone."""
+        rate and noise, else the rule alone; ``opt``: the ``ServerOptimizer`` of that vector, which then takes the server step.
+        With ``server_optimizer`` the server step is for parameters: the flat buffers, or without a HIP-backed network the
+        columns ``[0, n_params)`` of the rest matrix; statistics take the rule alone."""
         nets, pack = plan["nets"], plan["pack"]
-        plain = self.update_clip is None and self.update_noise == 0.0 and self.server_lr == 1.0
+        sopt = self.server_optimizer is not None
+        plain = self.update_clip is None and self.update_noise == 0.0 and self.server_lr == 1.0 and not sopt
         for j, (net, rows, snap) in enumerate(zip(nets, plan["rows"], plan["snaps"])):
             flat = net.flat_theta()
-            step(rows[:K], flat.numel(), None if plain else snap, flat, full=True, offset=self.global_round * (len(nets) + 1) + j)
+            step(rows[:K], flat.numel(), None if plain else snap, flat, full=True, offset=self.global_round * (len(nets) + 1) + j,
+                 opt=self._server_opt(j) if sopt else None)
         if pack.total:
             rest, snap = plan["rest_rows"][:K], plan["rest_snap"]
             if nets:                                   # next to the flat buffers: statistics and loose parameters, the rule alone
                 step(rest, rest.shape[1], None, snap, full=False, offset=0)
+            elif sopt:                                 # a plain module: parameters first, then the statistics (_build_plan)
+                n_p, total = plan["n_params"], rest.shape[1]
+                if n_p:
+                    step(rest[:, :n_p], n_p, snap[:n_p], snap[:n_p], full=True, offset=self.global_round, opt=self._server_opt(0))
+                if n_p < total:
+                    step(rest[:, n_p:], total - n_p, None, snap[n_p:], full=False, offset=0)
             else:                                      # no HIP-backed network (a plain module, any device): everything is here
                 step(rest, rest.shape[1], None if plain else snap, snap, full=True, offset=self.global_round)
             pack.unpack(snap)
         for t, rows in zip(plan["ints"], plan["int_rows"]):
             t.copy_(_int_mean(rows[:K], w.to(rows.device)))
+
+    def _server_opt(self, j: int) -> ServerOptimizer:
+        """the server optimizer of stepped vector j (a HIP-backed network's flat buffer, or the packed parameters), made on first use"""
+        while len(self._server_opts) <= j:
+            self._server_opts.append(ServerOptimizer(self.server_optimizer, self.server_lr, self.server_betas, self.server_tau))
+        return self._server_opts[j]
+
+    @staticmethod
+    def _scratch(plan, n: int) -> torch.Tensor:
+        """a persistent fp32 vector of n floats on the plan's device (a robust rule's aggregate before the server step)"""
+        if n not in plan["scratch"]:
+            plan["scratch"][n] = torch.empty(n, dtype=torch.float32, device=plan["dev"])
+        return plan["scratch"][n]
+
+    def server_state_dict(self) -> Dict[str, object]:
+        """the server optimizer's state: its name and one ``ServerOptimizer.state_dict()`` per stepped vector (none before the first
+        round with ``server_optimizer``)"""
+        return {"server_optimizer": self.server_optimizer, "states": [o.state_dict() for o in self._server_opts]}
+
+    def load_server_state_dict(self, state: Dict[str, object]) -> None:
+        if state["server_optimizer"] != self.server_optimizer:
+            raise ValueError(f"the state is {state['server_optimizer']!r}'s, this trainer runs {self.server_optimizer!r}")
+        opts = []
+        for sd in state["states"]:
+            opt = ServerOptimizer(self.server_optimizer, self.server_lr, self.server_betas, self.server_tau)
+            opt.load_state_dict(sd)
+            opts.append(opt)
+        self._server_opts = opts
 
     def _step_options(self, full: bool, offset: int) -> Dict[str, object]:
         """the server rate and the noise stream of a ``full`` step as keywords; none for the rule alone"""
@@ -342,8 +445,12 @@ class FederatedTrainer:
         """FedAvg: per matrix one ``nvq_fed_delta_norms`` (only with ``update_clip``) and one ``nvq_fed_aggregate``"""
         w, clip, dev = plan["weights"][:K], self.update_clip, plan["dev"]
 
-        def step(rows, n, base, out, *, full, offset):
+        def step(rows, n, base, out, *, full, offset, opt=None):
             kw = self._step_options(full, offset)
+            if opt is not None:                        # FedOpt: nvq_fed_server_opt in place of nvq_fed_aggregate
+                kw.pop("server_lr")
+                opt.step(rows, w if w.is_cuda else w.tolist(), base, clip_norm=clip, out=out, **kw)
+                return
             if not plan["nets"]:                       # the public function: the CPU formula, or the same two launches
                 aggregate_flat(rows, w if w.is_cuda else w.tolist(), base=None if base is None else base.clone(), clip_norm=clip,
                                out=out, **kw)
@@ -397,7 +504,15 @@ class FederatedTrainer:
                 gram = torch.zeros(K, K, dtype=torch.float64, device=w.device)
             w = selected = krum_select(gram, self.num_byzantine, q, weights=w).weights
 
-        def step(rows, n, base, out, *, full, offset):     # on the device one nvq_fed_trimmed_aggregate, nothing read back
+        def step(rows, n, base, out, *, full, offset, opt=None):   # on the device one nvq_fed_trimmed_aggregate, nothing read back
+            if opt is not None:                        # FedOpt: the rule alone into a scratch vector, then the K = 1 server step
+                agg = self._scratch(plan, n)
+                aggregate_flat_trimmed(rows, trim, weights=w, base=base, out=agg)
+                kw = self._step_options(full, offset)
+                kw.pop("server_lr")
+                one = plan["one"]
+                opt.step(agg.view(1, n), one if one.is_cuda else [1.0], base, out=out, **kw)
+                return
             aggregate_flat_trimmed(rows, trim, weights=w, base=base, out=out, **self._step_options(full, offset))
 
         self._aggregate(plan, K, w, step)
@@ -537,10 +652,13 @@ class FederatedTrainer:
         for k, (cid, cnt) in enumerate(zip(selected, counts)):
             with torch.no_grad():
                 if clustered and not split:
-                    self.load_cluster(self.client_cluster[cid])
+                    c = self.client_cluster[cid]
+                    self.load_cluster(c)
+                    anchor = ([cm[c] for cm in self.cluster_models], plan["rest_clusters"][c])
                 else:
                     self._restore(plan)
-            loss_sum += self._train_client(plan, self.client_data[cid], seeds[k])
+                    anchor = (plan["snaps"], plan["rest_snap"])
+            loss_sum += self._train_client(plan, self.client_data[cid], seeds[k], anchor)
             with torch.no_grad():
                 if self.after_client is not None:
                     self.after_client(cid, self.model)

@@ -14,7 +14,10 @@ a Byzantine-robust rule instead of FedAvg (``median``, ``trimmed_mean`` with ``-
 ``--num-byzantine``; csrc/robust.hip), and ``--poison N`` makes the first N selected clients of every round
 hostile through the trainer's ``after_client`` hook: ``--poison-kind flip`` sends ``global - 10 (x - global)``, ``nan`` sends NaN
 weights.  With either option the evaluation loss of the global model over all clients' data is printed after every round: FedAvg
-breaks under ``--poison 1``, the robust rules hold.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
+breaks under ``--poison 1``, the robust rules hold.  ``--server-opt`` runs a FedOpt server optimizer on the aggregated update
+(``fedavgm``, ``fedadagrad``, ``fedadam``, ``fedyogi`` with ``--server-beta1`` / ``--server-beta2`` / ``--server-tau``; ``--server-lr``
+is its learning rate, and 1.0 is far too large for the adaptive ones) and ``--prox-mu`` adds FedProx's proximal term to the local
+steps (csrc/fedopt.hip); ``--eval`` prints the evaluation loss after every round.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
 """
 import argparse
 from pathlib import Path
@@ -24,7 +27,7 @@ import torch
 
 from _common import OPTIMIZER_IMPLS, pick_device
 from nerve_cl import ops
-from nerve_cl.federated import FederatedTrainer, PrivacyConfig
+from nerve_cl.federated import SERVER_OPTIMIZERS, FederatedTrainer, PrivacyConfig
 from nerve_cl.federated.trainer import AGGREGATORS
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 from train_continual import _ClipAdapter, configure_precision
@@ -50,7 +53,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="clip every client's whole update to the 2-norm X in the aggregation pass (default: no clipping)")
     ap.add_argument("--update-noise", type=float, default=0.0, metavar="S",
                     help="standard deviation of the Gaussian noise added to the aggregated weights")
-    ap.add_argument("--server-lr", type=float, default=1.0, help="the aggregated update is scaled by this before it is applied")
+    ap.add_argument("--server-lr", type=float, default=1.0,
+                    help="the aggregated update is scaled by this before it is applied; with --server-opt the server optimizer's "
+                         "learning rate.  BEWARE: fedadagrad / fedadam / fedyogi move every weight by about this much per round, so "
+                         "the default 1.0 (a FedAvg value) is far too large for them: try 1e-3 .. 1e-1")
+    ap.add_argument("--server-opt", choices=SERVER_OPTIMIZERS, default=None,
+                    help="FedOpt: treat the aggregated update as a pseudo-gradient of server momentum (fedavgm), Adagrad, Adam or "
+                         "Yogi (no --clusters); see the warning at --server-lr")
+    ap.add_argument("--server-beta1", type=float, default=0.9, help="--server-opt: momentum")
+    ap.add_argument("--server-beta2", type=float, default=0.99, help="--server-opt fedadam / fedyogi: second-moment decay")
+    ap.add_argument("--server-tau", type=float, default=1e-3, help="--server-opt: adaptivity, the floor of the denominator")
+    ap.add_argument("--prox-mu", type=float, default=0.0, metavar="MU",
+                    help="FedProx: add MU / 2 |theta - theta_round|^2 to every client's objective (default 0: off)")
     ap.add_argument("--clusters", type=int, default=1, metavar="C",
                     help="cluster the clients by their updates into C groups with one model each (default 1: plain FedAvg)")
     ap.add_argument("--cluster-after", type=int, default=0, metavar="R", help="plain FedAvg rounds before the round that clusters")
@@ -62,6 +76,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--poison", type=int, default=0, metavar="N", help="the first N selected clients of every round send poisoned weights")
     ap.add_argument("--poison-kind", choices=["flip", "nan"], default="flip",
                     help="flip: global - 10 (x - global), the sign-flipped, scaled update; nan: NaN weights")
+    ap.add_argument("--eval", action="store_true", help="print the evaluation loss of the global model after every round")
     ap.add_argument("--samples", type=int, default=100, help="clips per client (the reference's 100)")
     ap.add_argument("--features", type=int, default=64)
     ap.add_argument("--blocks", type=int, default=8)
@@ -120,7 +135,9 @@ def main() -> None:
                                update_noise=args.update_noise, server_lr=args.server_lr, optimizer_impl=args.optimizer_impl,
                                seed=args.seed, num_clusters=args.clusters, cluster_after=args.cluster_after,
                                aggregator=args.aggregator, trim_ratio=args.trim_ratio, num_byzantine=args.num_byzantine,
-                               after_client=after_client if args.poison > 0 else None)
+                               after_client=after_client if args.poison > 0 else None, server_optimizer=args.server_opt,
+                               server_betas=(args.server_beta1, args.server_beta2), server_tau=args.server_tau,
+                               prox_mu=args.prox_mu)
     for cid in range(args.num_clients):
         lr, hr = create_client_data(cid, args.samples)
         trainer.set_client_data(cid, (lr.to(device), hr.to(device)))          # on the device: a round copies nothing from the host
@@ -130,7 +147,7 @@ def main() -> None:
             poison["global"] = [v.detach().clone() for v in trainer.model.state_dict().values()]
         m = trainer.train_round()
         print(f"Round {m['round']}: {m['clients']} clients, {m['samples']} samples, loss {m['train_loss']:.4f}")
-        if args.poison > 0 or args.aggregator != "fedavg":
+        if args.eval or args.poison > 0 or args.aggregator != "fedavg":
             chosen = f", selected {[int(w) for w in m['selected_weights']]}" if "selected_weights" in m else ""
             print(f"  evaluation loss of the global model {evaluate(trainer):.4f}{chosen}")
         if args.clusters > 1 and m["round"] == args.cluster_after + 1:

@@ -1062,6 +1062,38 @@ int nvq_fed_trimmed_aggregate(const float* clients, long stride, int K, const fl
 int nvq_fed_krum_select(const double* gram, int K, const double* weights, int num_byzantine, int num_selected,
                         double* out_weights, double* scores, int* order, void* stream);
 
+/* ------------------------------------------------------------------ Federated optimisation: FedOpt server rules and the FedProx
+ * gradient (csrc/fedopt.hip).  The same client matrix and the same rule as above: one launch each, no
+ * atomics, no workspace, size-only grids, the same bits on every call and at every pointer alignment.
+ *
+ * nvq_fed_server_opt: the sweep of nvq_fed_aggregate with a stateful server step.  Per element, everything in double: D = sum_k
+ * c_k (x_k[i] - base[i]) with c_k, the fma chain and its order exactly as in nvq_fed_aggregate; mp = m[i] and vp = v[i] widened;
+ * the hyper-parameters are the given floats widened.
+ *   NVQ_FED_OPT_AVGM     m' = fma(beta1, mp, D), step = m'; v is neither read nor written and may be NULL
+ *   the adaptive rules   m' = fma(beta1, mp, (1 - beta1) D), d2 = D * D rounded on its own, and
+ *   NVQ_FED_OPT_ADAGRAD  v' = vp + d2
+ *   NVQ_FED_OPT_ADAM     v' = fma(beta2, vp, (1 - beta2) d2)
+ *   NVQ_FED_OPT_YOGI     v' = vp - (1 - beta2) d2 sign(vp - d2), sign(0) = 0
+ *                        step = m' / (sqrt(v') + tau)
+ * out[i] = fmaf(noise_std, z_i, (float) fma(server_lr, step, base[i])) with the noise stream of nvq_fed_aggregate (noise_std == 0
+ * skips the noise path), m[i] = (float) m', v[i] = (float) v': the step uses the unrounded m' and v', so each stored value is the
+ * double chain rounded once.  AVGM with beta1 = 0 and m finite gives the bits of nvq_fed_aggregate.  base, weights, m and out
+ * are required, v for the adaptive rules; 0 <= beta1, beta2 < 1; tau > 0 for the adaptive rules; v >= 0 is the caller's (the
+ * usual start is tau^2).  out may alias base; out, m and v must not alias clients or each other.  K = 1 with weights = {1}
+ * steps from base towards a vector that another rule has aggregated.
+ *
+ * nvq_fed_prox_grad: grad[i] = (float) fma((double) mu, (double) theta[i] - (double) anchor[i], (double) grad[i]) in place, the
+ * gradient of mu / 2 |theta - anchor|^2 added to a flat gradient bucket; theta and anchor are only read.  mu >= 0; mu == 0
+ * launches nothing. */
+#define NVQ_FED_OPT_AVGM 0
+#define NVQ_FED_OPT_ADAGRAD 1
+#define NVQ_FED_OPT_ADAM 2
+#define NVQ_FED_OPT_YOGI 3
+int nvq_fed_server_opt(const float* clients, long stride, int K, const float* base, const double* weights, const double* sq,
+                       float clip_norm, int rule, float server_lr, float beta1, float beta2, float tau, float* m, float* v,
+                       float noise_std, long seed, long offset, long n, float* out, void* stream);
+int nvq_fed_prox_grad(float* grad, const float* theta, const float* anchor, long n, float mu, void* stream);
+
 /* ------------------------------------------------------------------ ABR agent: vectorised streaming environment, fused act,
  * GAE and the PPO loss (csrc/abr.hip).  No atomics; sums in double in a fixed order; plain vector stores.
  *
