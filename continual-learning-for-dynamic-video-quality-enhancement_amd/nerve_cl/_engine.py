@@ -35,11 +35,16 @@ DEBUG_CAPTURE: Optional[dict] = None
 _TAIL_ROWS = int(os.environ.get("NVQ_TAIL_ROWS", "0"))   # 4: the four-wave rdb_tail kernel (A/B switch, same results)
 
 
+def _on(name: str, default: str = "1") -> bool:
+    """An A/B switch of the environment, on unless "0"; read at every call (tests and tools/ flip them in a process)."""
+    return os.environ.get(name, default) != "0"
+
+
 def _fused_tail_ok(math: int, x: torch.Tensor, Cimg: int, scale: int) -> bool:
     """nvq_upsampler_tail_forward's domain: bf16 MFMA mode, a bf16-stored input, scale 2..4 with Cimg * scale^2 <= 16 / 32 / 64.
     (The exact-fp32 mode keeps the conv + nvq_shuffle_bicubic_clamp pair; NVQ_FUSED_TAIL=0 selects it in bf16 mode too.)"""
     return (math == K.MATH_BF16 and x.dtype == torch.bfloat16 and scale in (2, 3, 4)
-            and Cimg * scale * scale <= {2: 16, 3: 32, 4: 64}[scale] and os.environ.get("NVQ_FUSED_TAIL", "1") != "0")
+            and Cimg * scale * scale <= {2: 16, 3: 32, 4: 64}[scale] and _on("NVQ_FUSED_TAIL"))
 
 
 def _allreduce_sum_(t: torch.Tensor, group) -> None:
@@ -140,8 +145,38 @@ def _new(dev, *shape, dtype=torch.float32, zero=False):
 
 
 class Saved:
-    """Everything the backward needs; also the carrier of return_intermediate tensors."""
-    pass
+    """Everything the backward needs; also the carrier of return_intermediate tensors.  A plain attribute carrier: the
+    optional fields have class-level defaults, everything else is set by its producer.
+      forward:              g, frames, training, math, act_dtype, aligned, feat_oth, flow_acts, flow_bits, flow (None: T = 1),
+                            a1, a2, a1_bits, attn, weighted, cbam_dtype, gap, hid, ca, sm, amax, sa, nblk, cats, resout,
+                            planar, bits, fused, gr, passmask, xloc
+      _extract:             feat0 (None: forward(features=...), not differentiable), img8, dws, pws, acts, bn_mean,
+                            bn_invstd, bn_sync, dw_in, pw_from_dwpw
+      light_forward:        frames, training, math, act_dtype, scale, feat0, dws, pws, acts, bn_mean, bn_invstd, bn_sync,
+                            passmask, U, Up"""
+    feat0 = img8 = flow = None
+    bits = a1_bits = flow_bits = None   # one-bit ReLU masks (bf16 training)
+    bn_sync = ()                        # (always set by _extract / light_forward) per BatchNorm: (group, stats buffer) or None
+    pw_from_dwpw = False                # every extractor layer's p is dwpw_forward's bf16(d W^T)
+
+
+def _bn_stats(P, pre: str, p, B: int, order, mean, invstd, ws, training: bool, sync, fused: bool = False) -> None:
+    """The statistics of BatchNorm `pre` over p's len(order) frame groups -> mean, invstd.  sync = (process group, stats buffer):
+    reduce -> all-reduce -> finish (nn.SyncBatchNorm); else training: bn_stats; eval: the running statistics.  fused: the pass
+    that made p left the sums (sync) or the statistics (training) already.  Training counts the groups in num_batches_tracked."""
+    rmean, rvar = P[pre + "running_mean"], P[pre + "running_var"]
+    if sync is not None:
+        grp, st = sync
+        if not fused:
+            K.bn_stats_reduce(p, B, st, ws)
+        _allreduce_sum_(st, grp)
+        K.bn_stats_finish(st, len(order), order, mean, invstd, rmean, rvar, BN_EPS, BN_MOM)
+    elif training and not fused:
+        K.bn_stats(p, B, order, mean, invstd, rmean, rvar, ws, BN_EPS, BN_MOM)
+    if training:
+        P[pre + "num_batches_tracked"].add_(len(order))
+    else:
+        K.bn_eval_stats(rmean, rvar, len(order), mean, invstd, BN_EPS)
 
 
 def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, training: bool, math: int,
@@ -160,11 +195,11 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
                    img8=sv.img8, math=math)
     sv.feat0 = feat0
     sv.dws, sv.pws, sv.acts, sv.bn_mean, sv.bn_invstd = [], [], [], [], []
-    sv.bn_sync = []                   # per layer: (process group, forward stats buffer) of a synchronised BatchNorm, or None
+    sv.bn_sync = []
     cur, cur_bn = feat0, None         # cur_bn: BatchNorm + ReLU still to be applied to `cur` (fused into the consumer)
     sv.dw_in = []                     # (tensor, bn) the depthwise conv of layer k was fed with
     fuse_bn = K.dwconv_bn_fusable(feat0, F)
-    fused_fwd = fuse_bn and F == 64 and math == K.MATH_BF16 and os.environ.get("NVQ_FUSED_DWPW", "1") != "0"
+    fused_fwd = fuse_bn and F == 64 and math == K.MATH_BF16 and _on("NVQ_FUSED_DWPW")
     sv.pw_from_dwpw = fused_fwd       # every layer's p is dwpw_forward's bf16(d W^T): the backward may form it again from d
     for k in range(3):
         pre = f"feature_extractor.body.{k}."
@@ -173,10 +208,10 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
         mean, invstd = _new(dev, T, F), _new(dev, T, F)
         order = [slots.index(t) for t in range(T)]
         grp = sync.get(pre + "bn") if (training and sync) else None
-        st = K.new_bn_stats(dev, T, F) if grp is not None else None
-        if fused_fwd and grp is not None:
+        bsync = (grp, K.new_bn_stats(dev, T, F)) if grp is not None else None
+        if fused_fwd and bsync is not None:
             # synchronised BatchNorm: the fused pass leaves the per-frame sums, all ranks add them, then the statistics
-            K.dwpw_forward_sums(cur, cur_bn, P[pre + "depthwise.weight"], P[pre + "pointwise.weight"], d, p, B, st, ws)
+            K.dwpw_forward_sums(cur, cur_bn, P[pre + "depthwise.weight"], P[pre + "pointwise.weight"], d, p, B, bsync[1], ws)
         elif fused_fwd:
             # depthwise -> pointwise -> BatchNorm sums in one pass over the tensors (nvq_dwpw_forward)
             K.dwpw_forward(cur, cur_bn, P[pre + "depthwise.weight"], P[pre + "pointwise.weight"], d, p, B,
@@ -186,20 +221,9 @@ def _extract(P: Dict[str, torch.Tensor], frames: torch.Tensor, slots, F: int, tr
             K.dwconv_forward(cur, P[pre + "depthwise.weight"], d, bn=cur_bn)
             wp = K.conv_pack(P[pre + "pointwise.weight"], False, F, math=math)
             K.conv_forward(Sl(d), wp, None, Sl(p), 1, math=math)
-            if grp is not None:
-                K.bn_stats_reduce(p, B, st, ws)
-            elif training:
-                K.bn_stats(p, B, order, mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], ws, BN_EPS,
-                           BN_MOM)
-        if grp is not None:
-            _allreduce_sum_(st, grp)
-            K.bn_stats_finish(st, T, order, mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], BN_EPS, BN_MOM)
-        sv.bn_sync.append((grp, st) if grp is not None else None)
+        _bn_stats(P, pre + "bn.", p, B, order, mean, invstd, ws, training, bsync, fused=fused_fwd)
+        sv.bn_sync.append(bsync)
         sv.dw_in.append((cur, cur_bn))
-        if training:
-            P[pre + "bn.num_batches_tracked"].add_(T)
-        else:
-            K.bn_eval_stats(P[pre + "bn.running_mean"], P[pre + "bn.running_var"], T, mean, invstd, BN_EPS)
         if k < 2 and fuse_bn:
             # relu(bn(p)) is evaluated by the next depthwise conv (and by its weight gradient) while it stages p
             r, cur_bn = p, (mean, invstd, P[pre + "bn.weight"], P[pre + "bn.bias"], B)
@@ -247,7 +271,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     # before warping) are stored as bf16 like every other conv-internal tensor; their non-conv readers (correlation on
     # the matrix cores, warp, softmax-weighted sum) take a storage flag.  NVQ_BF16_FEATURES=0 keeps them fp32.
     feat_dtype = act_dtype if (act_dtype == torch.bfloat16 and math == K.MATH_BF16 and F in (32, 64)
-                               and os.environ.get("NVQ_BF16_FEATURES", "1") != "0") else torch.float32
+                               and _on("NVQ_BF16_FEATURES")) else torch.float32
     aligned = _new(dev, B, H, W, T * F, dtype=feat_dtype)
     feat_oth = _new(dev, max(NO, 1), H, W, F, dtype=feat_dtype)
     sv.aligned, sv.feat_oth = aligned, feat_oth
@@ -276,8 +300,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
         sv.flow_acts = [corr]
         # bf16 mode, training: the hidden layers also leave their ReLU masks as one bit per channel (the input-gradient conv of the
         # layer behind reads 4 bytes per 32 channels instead of the 64-byte activations, as in the dense blocks)
-        act_bits = (training and act_dtype == torch.bfloat16 and math == K.MATH_BF16
-                    and os.environ.get("NVQ_RELU_BITS", "1") != "0")
+        act_bits = training and act_dtype == torch.bfloat16 and math == K.MATH_BF16 and _on("NVQ_RELU_BITS")
         sv.flow_bits = [None] * 5
         for li, idx in enumerate((0, 2, 4, 6)):
             w = P[f"motion_estimator.flow_net.{idx}.weight"]
@@ -304,7 +327,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     logits = _new(dev, B, H, W, g.Tp)
     sv.a1_bits = (_new(dev, B, H, W, F // 32, dtype=torch.int32)
                   if (training and act_dtype == torch.bfloat16 and math == K.MATH_BF16 and F % 32 == 0
-                      and (aligned.dtype == torch.bfloat16 or F <= 32) and os.environ.get("NVQ_RELU_BITS", "1") != "0") else None)
+                      and (aligned.dtype == torch.bfloat16 or F <= 32) and _on("NVQ_RELU_BITS")) else None)
     K.conv_forward(Sl(aligned), packs.get("temporal_aggregator.attention.0.weight", False, T * F),
                    P["temporal_aggregator.attention.0.bias"], Sl(a1), 3, relu=True, math=math, bits=sv.a1_bits,
                    bits_mode=1 if sv.a1_bits is not None else 0)
@@ -317,8 +340,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     # bf16 activation mode: the aggregated features (the CBAM's input; one write, four reads per step) and the two gradients around
     # the CBAM backward are stored as bf16 like the tensors on either side of them; the pooled sums (GAP, channel mean / max,
     # dca) are formed from the unrounded values inside the kernels.  NVQ_BF16_CBAM=0 keeps them fp32.
-    cbam16 = (act_dtype == torch.bfloat16 and math == K.MATH_BF16 and nblocks > 0
-              and os.environ.get("NVQ_BF16_CBAM", "1") != "0")
+    cbam16 = act_dtype == torch.bfloat16 and math == K.MATH_BF16 and nblocks > 0 and _on("NVQ_BF16_CBAM")
     sv.cbam_dtype = torch.bfloat16 if cbam16 else torch.float32
     attn, weighted = _new(dev, B, H, W, g.Tp), _new(dev, B, H, W, F, dtype=sv.cbam_dtype)
     gap_partial = _new(dev, B, nblk, F)
@@ -332,8 +354,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     K.cbam_pool(weighted, ca, sm, amax)
     # bf16 mode: slice-planar dense-block buffers (K.CatBuf: x and every growth slice compact tensors of their own, whole
     # 128-B lines written by every layer); NVQ_PLANAR=0 or fp32 storage: one interleaved [B,H,W,CATLD] tensor per block
-    planar = (act_dtype == torch.bfloat16 and math == K.MATH_BF16 and F in (32, 64, 128)
-              and os.environ.get("NVQ_PLANAR", "1") != "0")
+    planar = act_dtype == torch.bfloat16 and math == K.MATH_BF16 and F in (32, 64, 128) and _on("NVQ_PLANAR")
     cats = [K.CatBuf(dev, B, H, W, F, LAYERS, g.CATLD, act_dtype, planar) for _ in range(nblocks)]
     sv.planar = planar
     # (with no dense blocks the CBAM kernel, an fp32 writer, fills this tensor)
@@ -352,7 +373,7 @@ def forward(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, nblocks: i
     use_bits = training and act_dtype == torch.bfloat16
     sv.bits = [[_new(dev, B, H, W, dtype=torch.int32) for _ in range(LAYERS)] for _ in range(nblocks)] if use_bits else None
     fuse_tail = (act_dtype == torch.bfloat16 and F == 64        # last dense layer + lff in one pass over the concat buffer
-                 and os.environ.get("NVQ_FUSE_TAIL", "1") != "0")
+                 and _on("NVQ_FUSE_TAIL"))
     for k in range(nblocks):
         cat = cats[k]
         for i in range(LAYERS - 1 if fuse_tail else LAYERS):
@@ -487,6 +508,13 @@ class _Grads:
         g = self.get(name)
         return g if g is not None else torch.empty_like(self.P[name])
 
+    def pair(self, wname: str, bname: Optional[str]):
+        """(weight, bias) targets of a conv, None when the plan forms neither; a frozen weight is a sink, a frozen bias None"""
+        dw, db = self.get(wname), self.get(bname) if bname else None
+        if dw is None and db is None:
+            return None
+        return (dw if dw is not None else torch.empty_like(self.P[wname])), db
+
     def check(self) -> None:
         bad = {n: c for n, c in self.writes.items() if c != 1}
         missing = self.plan.wgrad - set(self.writes)
@@ -497,15 +525,13 @@ def _wgrad(x: Sl, cin_w: int, dy: Sl, G: _Grads, wname: str, bname: Optional[str
            alpha=1.0, math=K.MATH_F32):
     """ws: the shared workspace (reduce behind the kernel) or a _ReduceQueue (reduce deferred into its next batch).  Nothing runs
     when neither gradient is planned; a frozen bias is not formed, a frozen weight next to a trained bias goes to a sink."""
-    dw, db = G.get(wname), G.get(bname) if bname else None
-    if dw is None and db is None:
+    t = G.pair(wname, bname)
+    if t is None:
         return
-    if dw is None:
-        dw = torch.empty_like(G.P[wname])
     if isinstance(ws, _ReduceQueue):
-        K.conv_wgrad(x, cin_w, dy, dw, db, ws.ws(), ksize, alpha=alpha, math=math, defer=ws.jobs)
+        K.conv_wgrad(x, cin_w, dy, t[0], t[1], ws.ws(), ksize, alpha=alpha, math=math, defer=ws.jobs)
     else:
-        K.conv_wgrad(x, cin_w, dy, dw, db, ws, ksize, alpha=alpha, math=math)
+        K.conv_wgrad(x, cin_w, dy, t[0], t[1], ws, ksize, alpha=alpha, math=math)
 
 
 def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, math: int = K.MATH_F32,
@@ -520,6 +546,355 @@ def extract_features(P: Dict[str, torch.Tensor], frames: torch.Tensor, F: int, m
         _extract(P, part, list(range(n)), F, False, math, act_dtype, Sl(out[t0:t0 + n].view(n * B, H, W, F)), n * B, None,
                  Saved())
     return out
+
+
+class _Bwd:
+    """The state of one backward() pass, shared by its stage functions: plain attributes."""
+
+    def __init__(self, P, sv: Saved, dout: torch.Tensor, G, plan: BackwardPlan, deterministic: bool, dinter: Optional[list]):
+        g = sv.g
+        self.P, self.sv, self.g, self.dout, self.plan, self.deterministic = P, sv, g, dout, plan, deterministic
+        self.G = _Grads(G, plan, P)
+        self.dinter = dinter if (dinter is not None and any(d is not None for d in dinter)) else None
+        self.dev, self.ws = dout.device, workspace(dout.device)
+        # Launch-bound steps (small frames: the 64x64 continual-learning step is ~330 dependent launches of a few microseconds):
+        # the conv weight gradients leave their partial sums in workspaces of their own and one launch per eight of them does the
+        # reduces (nvq_wgrad_reduce_batch; same sums, same order) - ~50 launches less per step.  Large frames keep the reduce
+        # behind each kernel, where its partial slabs (up to 56 MB) are still in the last-level cache.
+        self.small = g.B * g.H * g.W <= SMALL_STEP_PIXELS and K.TIMER is None
+        self.wq = _ReduceQueue(self.dev) if self.small else self.ws
+        self.packs = _Packs(P, sv.math)
+        # bf16 activation mode with reference frames: the feature gradient is FINISHED by the two correlation gradients, which
+        # write it as bf16 (dfeat16, _bwd_motion).  Its terms then never meet in an fp32 accumulator: the upsampler input-gradient
+        # conv's second output, the attention path's slice of daligned and the warp gradient are bf16 addends of those last
+        # passes (no fp32 gradient tensor, no axpy kernel, no read-modify-write).
+        self.feat16 = (sv.math == K.MATH_BF16 and sv.act_dtype == torch.bfloat16 and g.F in (32, 64) and sv.img8 is not None
+                       and g.NO > 0 and sv.aligned.dtype == torch.bfloat16 and _on("NVQ_BF16_FEATURE_GRAD"))
+        # (set by the stages: du, dg, dcats, dagg, dweighted, dgap_pix, dlogits, daligned, dfeat_all / _c / _c16 / _up, dcur)
+
+
+def _bwd_up(x: _Bwd) -> bool:
+    """upsampler tail: clamp / pixel-shuffle adjoint, the conv's weight and input gradients"""
+    g, sv, F = x.g, x.sv, x.g.F
+    x.du = _new(x.dev, g.B, g.H, g.W, g.Up)
+    K.shuffle_clamp_backward(x.dout, sv.passmask, g.s, x.du)
+    _capture("du", lambda: x.du)
+    _wgrad(Sl(sv.fused), F, Sl(x.du, g.U), x.G, "upsampler.conv.weight", "upsampler.conv.bias", x.wq, 3, math=sv.math)
+    if "up" not in x.plan.dx:
+        return False
+    # fp32 form: gradient w.r.t. the features of every frame (slot order); the centre frames' part is first written by the
+    # upsampler's input-gradient conv (out2 below), the other frames' by the warp backward (overwrite mode), the rest added
+    x.dfeat_all = _new(x.dev, g.B, 1, 1, F) if x.feat16 else _new(x.dev, g.NI, g.H, g.W, F)   # (feat16: only a pointer)
+    x.dfeat_c = x.dfeat_all[:g.B]
+    x.dfeat_c16 = _new(x.dev, g.B, g.H, g.W, F, dtype=torch.bfloat16) if x.feat16 else None
+    x.dfeat_up = Sl(x.dfeat_c16 if x.feat16 else x.dfeat_c)   # the centre frames' term as the conv below leaves it
+    x.dg = _new(x.dev, g.B, g.H, g.W, F, dtype=sv.act_dtype)
+    K.conv_forward(Sl(x.du), x.packs.get("upsampler.conv.weight", True, g.Up, F), None, Sl(x.dg), 3,
+                   out2=x.dfeat_up, mask=Sl(sv.gr), mask_c0=0, mask_c1=F, math=sv.math)
+    _capture("dg", lambda: x.dg.float())
+    return True
+
+
+def _bwd_gff(x: _Bwd) -> bool:
+    g, sv, F, nb = x.g, x.sv, x.g.F, x.g.NB
+    _wgrad(sv.xloc(nb), F, Sl(x.dg), x.G, "gff.0.weight", "gff.0.bias", x.wq, 3, math=sv.math)
+    if "gff" not in x.plan.dx:    # (the centre features' share, dfeat_up, only matters when the extractor is trained)
+        return False
+    # gradient buffers of the dense blocks, layout [gout(F) | dy_4 | dy_3 | dy_2 | dy_1 | dy_0] (ping-pong)
+    x.dcats = [K.CatBuf(x.dev, g.B, g.H, g.W, F, LAYERS, g.CATLD, sv.act_dtype, sv.planar) for _ in range(2)] if nb else []
+    x.dagg = _new(x.dev, g.B, g.H, g.W, F, dtype=sv.cbam_dtype)
+    gout = x.dcats[(nb - 1) & 1].x() if nb else Sl(x.dagg)
+    K.conv_forward(Sl(x.dg), x.packs.get("gff.0.weight", True, F, F), None, gout, 3, math=sv.math)
+    _capture("dfused", lambda: x.dfeat_up.t.float())
+    _capture("dres", lambda: gout.t[..., :F].float())
+    return True
+
+
+def _bwd_rdb(x: _Bwd) -> bool:
+    """residual dense blocks, last to first, in mirror form (see nvq_rdb_backward_weights)"""
+    g, sv, P, G, plan, math = x.g, x.sv, x.P, x.G, x.plan, x.sv.math
+    F, nb = g.F, g.NB
+    K.TIMER_TAG = "rdb"
+    # the gout channels of the mirror-form convs only carry the 1x1 lff^T term: the bf16 kernels skip their other taps
+    ctr = F if (math == K.MATH_BF16 and F % 32 == 0) else 0
+    # blocks whose backward runs: a suffix k0 .. nb-1 (an upstream need of block k is one of block k + 1)
+    ran = [k for k in range(nb) if f"rdb.{k}" in plan.run]
+    assert ran == list(range(nb - len(ran), nb))
+    # the combined weights of those blocks, then their 6 packs each in one launch
+    reqs = []
+    for k in ran:
+        pre = f"residual_blocks.{k}."
+        wb, wbx = K.rdb_backward_weights(P[pre + "lff.weight"], [P[pre + f"layers.{i}.0.weight"] for i in range(LAYERS)], F)
+        reqs += [(wb[j], False, F + GROWTH * j, None) for j in range(LAYERS)] + [(wbx, False, g.CAT, None)]
+    mirror = K.conv_pack_many(reqs, math)
+    for j, k in reversed(list(enumerate(ran))):
+        cat, dcat = sv.cats[k], x.dcats[k & 1]
+        pre = f"residual_blocks.{k}."
+        gout = dcat.x()
+        _capture(f"drdb{k}", lambda: gout.t[..., :F].float())
+        _wgrad(cat.inp(g.CAT), g.CAT, gout, G, pre + "lff.weight", pre + "lff.bias", x.wq, 1, alpha=0.2, math=math)
+        wpb = mirror[j * (LAYERS + 1):(j + 1) * (LAYERS + 1)]     # packs of Wb_4 .. Wb_0, Wb_x
+        # dy_i is needed for the block's own input gradient or for the weight gradient of layer i or a layer below it
+        lowest = 0 if f"rdb.{k}" in plan.dx else min(
+            [i for i in range(LAYERS) if pre + f"layers.{i}.0.weight" in plan.wgrad or pre + f"layers.{i}.0.bias" in plan.wgrad],
+            default=LAYERS)
+        for i in range(LAYERS - 1, lowest - 1, -1):
+            cinb = F + GROWTH * (LAYERS - 1 - i)            # channels [0, cinb) = gout, dy_4 .. dy_{i+1}
+            dy = dcat.y(LAYERS - 1 - i)                      # slot of dy_i (channels [cinb, cinb + 32) of the buffer)
+            if sv.bits is not None:
+                K.conv_forward(dcat.inp(cinb), wpb[LAYERS - 1 - i], None, dy, 3,
+                               math=math, bits=sv.bits[k][i], bits_mode=2, center_cin=ctr)
+            else:
+                K.conv_forward(dcat.inp(cinb), wpb[LAYERS - 1 - i], None, dy, 3,
+                               mask=cat.y(i), mask_c0=0, mask_c1=GROWTH, math=math, center_cin=ctr)
+            cin = F + GROWTH * i
+            _wgrad(cat.inp(cin), cin, dy, G, pre + f"layers.{i}.0.weight", pre + f"layers.{i}.0.bias", x.wq, 3, math=math)
+        if f"rdb.{k}" not in plan.dx:
+            break
+        nxt = x.dcats[(k - 1) & 1].x() if k > 0 else Sl(x.dagg)
+        K.conv_forward(dcat.inp(g.CAT), wpb[LAYERS], None, nxt, 3, res=gout, math=math, center_cin=ctr)
+    K.TIMER_TAG = ""
+    return "cbam" in plan.run
+
+
+def _bwd_cbam(x: _Bwd) -> bool:
+    g, sv, P, G, dxs = x.g, x.sv, x.P, x.G, x.plan.dx
+    F = g.F
+    dprev = Sl(x.dagg)
+    if x.dinter is not None:
+        # `aggregated` (the CBAM's output, block 0's input): its gradient is complete here
+        K.inject_nchw([(dprev, [x.dinter[2 * g.T]])])
+    _capture("dagg", lambda: dprev.t[..., dprev.coff:dprev.coff + F].float())
+    fc0, fc2 = "temporal_aggregator.refine.channel_attention.fc.0.weight", "temporal_aggregator.refine.channel_attention.fc.2.weight"
+    w7 = "temporal_aggregator.refine.spatial_attention.conv.weight"
+    dpre = _new(x.dev, g.B, g.H, g.W)
+    K.cbam_bwd_spatial_pre(dprev, sv.weighted, sv.ca, sv.sa, dpre)
+    dsm = _new(x.dev, g.B, g.H, g.W, 2)
+    # (frozen CBAM weights: the _ex forms, the same dsm / dgap_pix without the weight gradients)
+    K.cbam_bwd_spatial_conv(dpre, sv.sm, P[w7], dsm, G.get(w7), x.ws)
+    fc_frozen = fc0 not in x.plan.wgrad and fc2 not in x.plan.wgrad
+    if "cbam" not in dxs and fc_frozen:
+        return False
+    x.dweighted = _new(x.dev, g.B, g.H, g.W, F, dtype=sv.cbam_dtype)
+    dca_partial = _new(x.dev, g.B, sv.nblk, F)
+    K.cbam_bwd_scale(dprev, sv.weighted, sv.ca, sv.sa, dsm, sv.amax, x.dweighted, dca_partial)
+    x.dgap_pix = _new(x.dev, g.B, F)
+    dw1, dw2 = (None, None) if fc_frozen else (G.sink(fc0), G.sink(fc2))   # (one frozen: the full form, the other into a sink)
+    K.cbam_bwd_channel(dca_partial, sv.nblk, F, g.R, g.B, g.H * g.W, P[fc0], P[fc2], sv.gap, sv.hid, sv.ca, dw1, dw2, x.dgap_pix)
+    _capture("dgap_pix", lambda: x.dgap_pix)
+    return "cbam" in dxs
+
+
+def _bwd_attention(x: _Bwd) -> bool:
+    """softmax-weighted sum and the three attention convs -> daligned (with the intermediates' gradients injected)"""
+    g, sv, G, dxs, packs, math = x.g, x.sv, x.G, x.plan.dx, x.packs, x.sv.math
+    F, T, c = g.F, g.T, g.c
+    x.daligned = _new(x.dev, g.B, g.H, g.W, T * F, dtype=sv.aligned.dtype)   # stored like `aligned` (bf16 in the bf16 mode)
+    x.dlogits = _new(x.dev, g.B, g.H, g.W, g.Tp)
+    K.tsum_backward(x.dweighted, x.dgap_pix, sv.aligned, sv.attn, T, F, x.daligned, x.dlogits)
+    pre = "temporal_aggregator.attention."
+    _wgrad(Sl(sv.a2), F, Sl(x.dlogits, T), G, pre + "4.weight", pre + "4.bias", x.wq, 3, math=math)
+    if "att.4" in dxs:
+        da2 = _new(x.dev, g.B, g.H, g.W, F, dtype=sv.act_dtype)
+        K.conv_forward(Sl(x.dlogits), packs.get(pre + "4.weight", True, g.Tp, F), None, Sl(da2), 3,
+                       mask=Sl(sv.a2), mask_c0=0, mask_c1=F, math=math)
+        _capture("da2", lambda: da2.float())
+        _wgrad(Sl(sv.a1), F, Sl(da2), G, pre + "2.weight", pre + "2.bias", x.wq, 3, math=math)
+    if "att.2" in dxs:
+        da1 = _new(x.dev, g.B, g.H, g.W, F, dtype=sv.act_dtype)
+        if sv.a1_bits is not None:
+            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3, math=math, bits=sv.a1_bits, bits_mode=2)
+        else:
+            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3,
+                           mask=Sl(sv.a1), mask_c0=0, mask_c1=F, math=math)
+        _capture("da1", lambda: da1.float())
+        _wgrad(Sl(sv.aligned), T * F, Sl(da1), G, pre + "0.weight", pre + "0.bias", x.wq, 3, math=math)
+    if "att.0" not in dxs:
+        # nothing before the attention convs needs a gradient: no motion or extractor backward
+        return False
+    K.conv_forward(Sl(da1), packs.get(pre + "0.weight", True, F, T * F), None, Sl(x.daligned), 3, accumulate=True, math=math)
+    if x.dinter is not None:
+        # `aligned[t]` into slice t; `features[c]` (the same tensor in the reference) into slice c too, which reaches the centre
+        # frame's feature gradient in both forms of _bwd_motion (axpy_slice / the correlation gradient's addend)
+        K.inject_nchw([(Sl(x.daligned, F, t * F), [x.dinter[T + t]] + ([x.dinter[c]] if t == c else [])) for t in range(T)])
+    return True
+
+
+def _bwd_motion(x: _Bwd) -> bool:
+    """the rest of the feature gradient (fp32 dfeat_all or bf16 dfeat16, _Bwd.feat16): warp, flow net, correlation"""
+    g, sv, math, feat16 = x.g, x.sv, x.sv.math, x.feat16
+    B, T, F, c, NO = g.B, g.T, g.F, g.c, g.NO
+    daligned = x.daligned
+    if not feat16:
+        K.axpy_slice(Sl(x.dfeat_c), Sl(daligned, F, c * F))
+    _capture("dweighted", lambda: x.dweighted.float())
+    _capture("dlogits", x.dlogits)
+    _capture("daligned", daligned)
+    if not NO:
+        return True
+    # (feat16: the reference frames' term from the warp leaves as bf16 too and is an addend of the correlation gradient's pass)
+    dfeat_oth = _new(x.dev, NO, g.H, g.W, F, dtype=torch.bfloat16) if feat16 else x.dfeat_all[B:]
+    dflow = _new(x.dev, NO, g.H, g.W, 4)
+    for j in range(1, T):
+        lo, hi = (j - 1) * B, j * B
+        K.warp_backward(Sl(daligned, F, g.slots[j] * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
+                        Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True, deterministic=bool(x.deterministic))
+    acts = sv.flow_acts          # [corr(96), f1(128), f2(64), f3(32), flow(4)]
+    chans = [81, 128, 64, 32, 2]
+    dy_t, dy_c = dflow, 2
+    for li, idx in reversed(list(enumerate((0, 2, 4, 6)))):
+        x_t = acts[li]
+        name = f"motion_estimator.flow_net.{idx}."
+        x_sl = Sl(x_t) if li > 0 else Sl(x_t, CORR_LD, 0)
+        _wgrad(x_sl, chans[li], Sl(dy_t, dy_c), x.G, name + "weight", name + "bias", x.wq, 3, math=math)
+        if f"flow.{idx}" not in x.plan.dx:
+            break
+        wp = x.packs.get(name + "weight", True, dy_t.shape[-1], chans[li])
+        dx_t = _new(x.dev, NO, g.H, g.W, x_t.shape[-1], dtype=sv.act_dtype if li > 0 else x_t.dtype)
+        if li > 0 and sv.flow_bits[li] is not None:
+            K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, math=math, bits=sv.flow_bits[li], bits_mode=2)
+        elif li > 0:
+            K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, mask=Sl(x_t), mask_c0=0,
+                           mask_c1=chans[li], math=math)
+        else:
+            # gradient of the correlation volume: the bf16 volume's 96-channel rows are written whole (zeros behind the
+            # 81 real channels) - a row of 84 channels would leave lines half written (fill reads)
+            full = dx_t.shape[-1] if dx_t.dtype == torch.bfloat16 else K.pad4(chans[li])
+            K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, cout_store=full, math=math)
+        _capture(f"dflow_x{li}", lambda: dx_t.float())
+        dy_t, dy_c = dx_t, chans[li]
+    dcorr = dy_t
+    _capture("f1", acts[1])
+    _capture("dflow", dflow)
+    if "flow.0" not in x.plan.dx:
+        # a trained flow net in front of a frozen extractor (and frames without a gradient): the pass ends here
+        return False
+    _capture("dcorr", dcorr)
+    if x.dinter is not None:
+        # `features[t]`, t != c: the warp gradient has written its slot; the correlation gradients add to it / read it next
+        K.inject_nchw([(Sl(dfeat_oth).images((j - 1) * B, j * B), [x.dinter[g.slots[j]]]) for j in range(1, T)])
+    center = Sl(sv.aligned, F, c * F)
+    # The two correlation gradients are the LAST terms of the feature gradient.  bf16 activation mode: they write the finished
+    # sum as bf16 (dfeat16) instead of back into the fp32 accumulator - the extractor's backward reads it three times
+    # (BatchNorm sums, pointwise backward, the skip add of the first depthwise layer) at half the bytes, like every other
+    # gradient it consumes.  The second one is the gradient w.r.t. the centre frame's features: the T - 1 reference frames in
+    # one pass.
+    if feat16:
+        dfeat16 = _new(x.dev, g.NI, g.H, g.W, F, dtype=torch.bfloat16)
+        K.correlation_backward(1, dcorr, center, Sl(x.dfeat_c), False, math=math, out16=dfeat16[B:], addends=(Sl(dfeat_oth),))
+        K.correlation_backward(2, dcorr, Sl(sv.feat_oth), Sl(x.dfeat_c), False, math=math, groups=T - 1, out16=dfeat16[:B],
+                               addends=(Sl(x.dfeat_c16), Sl(daligned, F, c * F)))
+        x.dfeat_all = dfeat16
+    else:
+        K.correlation_backward(1, dcorr, center, Sl(dfeat_oth), True, math=math)
+        K.correlation_backward(2, dcorr, Sl(sv.feat_oth), Sl(x.dfeat_c), True, math=math, groups=T - 1)
+    return True
+
+
+def _bn_relu_bwd(P, G: _Grads, pre: str, dy, p, B: int, mean, invstd, training: bool, sync, ws) -> torch.Tensor:
+    """BatchNorm + ReLU backward of the plain (unfused) block `pre` -> dp, the gradient at the pointwise conv's output.
+    sync = (process group, forward stats buffer): the sums of every rank, dp from them and the forward's global count."""
+    gamma, beta = P[pre + "bn.weight"], P[pre + "bn.bias"]
+    dp = torch.empty_like(p)
+    if sync is None:
+        K.bn_relu_backward(dy, p, B, mean, invstd, gamma, beta, training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
+        return dp
+    bsums = _new(p.device, mean.numel() * 2, dtype=torch.float64)
+    K.bn_relu_backward_reduce(dy, p, B, mean, invstd, gamma, beta, bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
+    _allreduce_sum_(bsums, sync[0])
+    K.bn_relu_backward_finish(dy, p, B, mean, invstd, gamma, beta, bsums, K.bn_counts(sync[1], *mean.shape), dp)
+    return dp
+
+
+def _bwd_body(x: _Bwd) -> bool:
+    """feature extractor body (all frames batched), layers 2, 1, 0 -> dcur, the gradient at the head conv's output"""
+    g, sv, P, G, ws, run = x.g, x.sv, x.P, x.G, x.ws, x.plan.run
+    B, T, F, math, act = g.B, g.T, g.F, sv.math, sv.act_dtype
+    if "body.2" not in run:                     # (T = 1: no motion path, the attention convs' need decides)
+        return False
+    _capture("dfeat_all", lambda: x.dfeat_all.float())
+    dcur = x.dcur = x.dfeat_all
+    # (built and measured, off by default: with the sums in it the depthwise backward only fits its registers with two instead
+    # of five unrolled rows, and the step is 0.2 ms SLOWER than with the separate 0.54 ms reduce passes it replaces; never with
+    # a synchronised layer, whose sums are all-reduced between its reduce and finish phases)
+    fuse_sums = _on("NVQ_FUSED_BN_SUMS", "0") and not any(sv.bn_sync)
+    sums = None      # (BatchNorm-backward sums, dgamma, dbeta) of layer k, when the depthwise backward of layer k + 1 left them
+    for k in (2, 1, 0):
+        pre = f"feature_extractor.body.{k}."
+        if f"body.{k}" not in run:                # the layers below need nothing either
+            break
+        need_dx = f"body.{k}" in x.plan.dx
+        p, d, mean, invstd, bsync = sv.pws[k], sv.dws[k], sv.bn_mean[k], sv.bn_invstd[k], sv.bn_sync[k]
+        gamma, beta, wpw = P[pre + "bn.weight"], P[pre + "bn.bias"], P[pre + "pointwise.weight"]
+        fused = math == K.MATH_BF16 and act == p.dtype == d.dtype == torch.bfloat16 and F == 64
+        dd = torch.empty_like(p)
+        # the pass behind the BatchNorm sums forms p again from the d tile it stages anyway (one tensor pass fewer, the
+        # same bits) when the forward made p from this d and this weight in the fused pass
+        recompute = fused and sv.pw_from_dwpw and _on("NVQ_PW_RECOMPUTE")
+        if not (fused and _on("NVQ_FUSED_PW_BWD")):
+            dp = _bn_relu_bwd(P, G, pre, dcur, p, B, mean, invstd, sv.training, bsync, ws)
+            _wgrad(Sl(d), F, Sl(dp), G, pre + "pointwise.weight", None, x.wq, 1, math=math)
+            # (also when nothing reads dd: frozen depthwise weight, no input gradient needed)
+            K.conv_forward(Sl(dp), K.conv_pack(wpw, True, F, F, math=math), None, Sl(dd), 1, math=math)
+        elif bsync is not None:
+            # synchronised BatchNorm: {sum g, sum g xhat} of every rank, dx from the global sums and the forward's global count
+            bsums = _new(dd.device, T * 2 * F, dtype=torch.float64)
+            K.pw_bn_backward_reduce(dcur, p, B, mean, invstd, gamma, beta, bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
+            _allreduce_sum_(bsums, bsync[0])
+            K.pw_bn_backward_finish(dcur, p, d, B, mean, invstd, gamma, beta, wpw, dd, G.get(pre + "pointwise.weight"), bsums,
+                                    K.bn_counts(bsync[1], T, F), ws, recompute=recompute)
+        else:
+            # BatchNorm backward + the pointwise conv's input and weight gradients in one pass behind the BatchNorm sums: dp is
+            # formed in LDS and never stored (nvq_pw_bn_backward; a frozen pointwise weight or BatchNorm affine: the _ex form)
+            bn_sums, dgam, dbet = sums or (None, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"))
+            K.pw_bn_backward(dcur, p, d, B, mean, invstd, gamma, beta, sv.training, wpw, dd, dgam, dbet,
+                             G.get(pre + "pointwise.weight"), ws, sums_in=bn_sums, recompute=recompute)
+        _capture(f"dd{k}", lambda: dd.float())
+        xin, xin_bn = sv.dw_in[k]
+        dww, sums = G.get(pre + "depthwise.weight"), None
+        if fused and k > 0 and xin.dtype == torch.bfloat16 and _on("NVQ_FUSED_DW_BWD"):
+            # the depthwise conv's input gradient and weight gradient from one staged tile (nvq_dwconv_backward).  Not for the
+            # first layer: with the skip-path add and the head's ReLU mask in its epilogue the one-tile kernel takes as long as
+            # the two launches below (2.53 vs 2.54 ms: the epilogue operands are loaded where they are used, by 8 waves per CU).
+            # A frozen depthwise weight: dx alone (dweight None -> the _ex form)
+            if not need_dx and dww is None:
+                break
+            dx = torch.empty_like(dd)
+            if fuse_sums and sv.training and need_dx and _on("NVQ_FUSED_PW_BWD"):
+                # ... and the backward sums of layer k - 1's BatchNorm: this kernel holds its input (xin) and the gradient of
+                # its activation (dx), so the next pw_bn_backward needs no reduce pass of its own
+                prev = f"feature_extractor.body.{k - 1}."
+                sums = (_new(dd.device, T, 2, F), G.sink(prev + "bn.weight"), G.sink(prev + "bn.bias"))
+            bn_sums, dgam, dbet = sums or (None, None, None)
+            K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws, bn_sums=bn_sums, bn_dgamma=dgam, bn_dbeta=dbet)
+        else:
+            if dww is not None:
+                K.dwconv_wgrad(xin, dd, dww, ws, bn=xin_bn)
+            if not need_dx:
+                break
+            # first layer, bf16 mode: dx + skip path, ReLU-masked by the head features: the gradient of the head conv, as bf16
+            add, mask = (x.dfeat_all, sv.feat0) if (k == 0 and sv.img8 is not None) else (None, None)
+            dx = torch.empty_like(dd, dtype=act if (k > 0 or add is not None) else torch.float32)
+            K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True, add=add, mask=mask)
+        _capture(f"dx{k}", lambda: dx.float())
+        dcur = x.dcur = dx
+    return True
+
+
+def _bwd_head(x: _Bwd) -> bool:
+    g, sv, bname = x.g, x.sv, "feature_extractor.head.0.bias"
+    hw = x.G.pair("feature_extractor.head.0.weight", bname) if "head" in x.plan.run else None
+    if hw is not None and sv.img8 is not None:
+        K.conv_wgrad(Sl(sv.img8), g.Cimg, Sl(x.dcur), hw[0], hw[1], x.ws, 3, math=sv.math)
+    elif hw is not None:
+        # the skip path of  feat = body(h) + h  is summed inside the head kernel (dout2)
+        K.head_wgrad(sv.frames, g.slots, x.dcur, sv.feat0, hw[0], hw[1] if hw[1] is not None else x.G.sink(bname), x.ws,
+                     dout2=x.dfeat_all)
+    return True
+
+
+# reverse sr_stages order; each returns whether the pass continues upstream (False: nothing further is needed)
+_BWD_STAGES = (_bwd_up, _bwd_gff, _bwd_rdb, _bwd_cbam, _bwd_attention, _bwd_motion, _bwd_body, _bwd_head)
 
 
 def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[str, torch.Tensor],
@@ -539,387 +914,36 @@ def backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G: Dict[
     if plan is None:
         plan = backward_plan(G.keys(), dframes is not None, g.NB, g.T)
     assert plan.frames == (dframes is not None), "backward: dframes and the plan disagree"
-    run, dxs = plan.run, plan.dx
-    G = _Grads(G, plan, P)
-    dev = dout.device
-    B, T, H, W, NI, NO, c, F = g.B, g.T, g.H, g.W, g.NI, g.NO, g.c, g.F
-    math, act_dtype = sv.math, sv.act_dtype
-    ws = workspace(dev)
-    # Launch-bound steps (small frames: the 64x64 continual-learning step is ~330 dependent launches of a few microseconds): the
-    # conv weight gradients leave their partial sums in workspaces of their own and one launch per eight of them does the reduces
-    # (nvq_wgrad_reduce_batch; same sums, same order) - ~50 launches less per step.  Large frames keep the reduce behind each
-    # kernel, where its partial slabs (up to 56 MB) are still in the last-level cache.
-    small = g.B * g.H * g.W <= SMALL_STEP_PIXELS and K.TIMER is None
-    wq = _ReduceQueue(dev) if small else ws
-    nb = g.NB
+    x = _Bwd(P, sv, dout, G, plan, deterministic, dinter)
     # the transposed packs of the input-gradient convs outside the dense blocks in one launch (the blocks' mirror-form packs
-    # have a batched launch of their own below)
-    packs = _Packs(P, math)
-    pre_a = "temporal_aggregator.attention."
-    # (only the packs of the input-gradient convs that run)
+    # have a batched launch of their own, _bwd_rdb); only the packs of the convs that run
+    F, T, dxs, pre_a = g.F, g.T, plan.dx, "temporal_aggregator.attention."
     reqs = [r for st, r in (("up", ("upsampler.conv.weight", True, g.Up, F)), ("gff", ("gff.0.weight", True, F, F)),
                             ("att.4", (pre_a + "4.weight", True, g.Tp, F)), ("att.2", (pre_a + "2.weight", True, F, F)),
                             ("att.0", (pre_a + "0.weight", True, F, T * F))) if st in dxs]
-    if NO:
+    if g.NO:
         reqs += [(f"motion_estimator.flow_net.{idx}.weight", True, cs, keep)
                  for idx, cs, keep in zip((6, 4, 2, 0), (4, K.pad4(32), K.pad4(64), K.pad4(128)), (32, 64, 128, 81))
                  if f"flow.{idx}" in dxs]
     if reqs:
-        packs.prefetch(reqs)
-
-    # ---- upsampler tail
-    du = _new(dev, B, H, W, g.Up)
-    K.shuffle_clamp_backward(dout, sv.passmask, g.s, du)
-    _capture("du", lambda: du)
-    _wgrad(Sl(sv.fused), F, Sl(du, g.U), G, "upsampler.conv.weight", "upsampler.conv.bias", wq, 3, math=math)
-    # Frozen layers: the stages below run while something upstream of them, or one of their own parameters, needs a gradient
-    # (plan.run); past the last such stage the pass ends.
-    if dinter is not None and all(d is None for d in dinter):
-        dinter = None
-    head = _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinter)
-    if small:
-        wq.flush()
-    G.check()
+        x.packs.prefetch(reqs)
+    # Frozen layers: a stage runs while something upstream of it, or one of its own parameters, needs a gradient (plan.run);
+    # past the last such stage the pass ends.
+    for stage in _BWD_STAGES:
+        if not stage(x):
+            break
+    if x.small:
+        x.wq.flush()
+    x.G.check()
     if dframes is not None:
-        # the head conv's input gradient for all T frames (same operands as its weight gradient above), then the bicubic
+        # the head conv's input gradient for all T frames (same operands as its weight gradient), then the bicubic
         # skip's adjoint onto the centre frame, masked by the clamp
-        dcur, dfeat_all = head
         wh = P["feature_extractor.head.0.weight"]
         if sv.img8 is not None:
-            K.head_dgrad(dcur, wh, B, g.slots, dframes)
+            K.head_dgrad(x.dcur, wh, g.B, g.slots, dframes)
         else:
-            K.head_dgrad(dcur, wh, B, g.slots, dframes, act=sv.feat0, dout2=dfeat_all)
-        K.bicubic_adjoint(dout, sv.passmask, g.s, c, 1.0, dframes, accumulate=True)
-
-
-def _backward_body(P, sv, dout, G, deterministic, plan, packs, du, wq, ws, dinter):
-    """backward() behind the upsampler's weight gradient -> (gradient at the head conv's output, feature gradient) when the
-    extractor's backward ran, else None"""
-    g = sv.g
-    dev = dout.device
-    B, T, H, W, NI, NO, c, F = g.B, g.T, g.H, g.W, g.NI, g.NO, g.c, g.F
-    math, act_dtype = sv.math, sv.act_dtype
-    nb = g.NB
-    run, dxs = plan.run, plan.dx
-    if "up" not in dxs:
-        return None
-    # bf16 activation mode with reference frames: the feature gradient is FINISHED by the two correlation gradients, which write it
-    # as bf16 (dfeat16, below).  Its terms then never meet in an fp32 accumulator: the upsampler input-gradient conv's second
-    # output, the attention path's slice of daligned and the warp gradient are bf16 addends of those last passes (no fp32
-    # gradient tensor, no axpy kernel, no read-modify-write).
-    feat16 = (math == K.MATH_BF16 and act_dtype == torch.bfloat16 and F in (32, 64) and sv.img8 is not None and NO > 0
-              and sv.aligned.dtype == torch.bfloat16 and os.environ.get("NVQ_BF16_FEATURE_GRAD", "1") != "0")
-    # fp32 form: gradient w.r.t. the features of every frame (slot order); the centre frames' part is first written by the
-    # upsampler's input-gradient conv (out2 below), the other frames' by the warp backward (overwrite mode), the rest added
-    dfeat_all = _new(dev, B if feat16 else NI, 1 if feat16 else H, 1 if feat16 else W, F)   # (feat16: only a pointer for unused arguments)
-    dfeat_c = dfeat_all[:B]
-    dfeat_c16 = _new(dev, B, H, W, F, dtype=torch.bfloat16) if feat16 else None
-    dg = _new(dev, B, H, W, F, dtype=act_dtype)
-    K.conv_forward(Sl(du), packs.get("upsampler.conv.weight", True, g.Up, F), None, Sl(dg), 3,
-                   out2=Sl(dfeat_c16) if feat16 else Sl(dfeat_c), mask=Sl(sv.gr), mask_c0=0, mask_c1=F, math=math)
-    _capture("dg", lambda: dg.float())
-    # ---- gff
-    xN = sv.xloc(nb)
-    _wgrad(xN, F, Sl(dg), G, "gff.0.weight", "gff.0.bias", wq, 3, math=math)
-    if "gff" not in dxs:          # (the centre features' share, dfeat_c above, only matters when the extractor is trained)
-        return None
-    # gradient buffers of the dense blocks, layout [gout(F) | dy_4 | dy_3 | dy_2 | dy_1 | dy_0] (ping-pong)
-    dcats = [K.CatBuf(dev, B, H, W, F, LAYERS, g.CATLD, act_dtype, sv.planar) for _ in range(2)] if nb else []
-    dagg = _new(dev, B, H, W, F, dtype=sv.cbam_dtype)
-    gout = dcats[(nb - 1) & 1].x() if nb else Sl(dagg)
-    K.conv_forward(Sl(dg), packs.get("gff.0.weight", True, F, F), None, gout, 3, math=math)
-    _capture("dfused", (lambda: dfeat_c16.float()) if feat16 else dfeat_c)
-    _capture("dres", lambda: gout.t[..., :F].float())
-
-    # ---- residual dense blocks, last to first, in mirror form (see nvq_rdb_backward_weights)
-    K.TIMER_TAG = "rdb"
-    # the gout channels of the mirror-form convs only carry the 1x1 lff^T term: the bf16 kernels skip their other taps
-    ctr = F if (math == K.MATH_BF16 and F % 32 == 0) else 0
-    # the combined weights of all blocks, then their 6 * nb packs in one launch
-    reqs = []
-    for k in range(nb):
-        pre = f"residual_blocks.{k}."
-        if f"rdb.{k}" not in run:
-            continue
-        wb, wbx = K.rdb_backward_weights(P[pre + "lff.weight"], [P[pre + f"layers.{i}.0.weight"] for i in range(LAYERS)], F)
-        reqs += [(wb[j], False, F + GROWTH * j, None) for j in range(LAYERS)] + [(wbx, False, g.CAT, None)]
-    mirror = K.conv_pack_many(reqs, math)
-    # blocks whose backward runs: a suffix k0 .. nb-1 (an upstream need of block k is one of block k + 1)
-    ran = [k for k in range(nb) if f"rdb.{k}" in run]
-    for k in range(nb - 1, -1, -1):
-        if k not in ran:
-            break
-        cat = sv.cats[k]
-        dcat = dcats[k & 1]
-        pre = f"residual_blocks.{k}."
-        gout = dcat.x()
-        _capture(f"drdb{k}", lambda: gout.t[..., :F].float())
-        _wgrad(cat.inp(g.CAT), g.CAT, gout, G, pre + "lff.weight", pre + "lff.bias", wq, 1, alpha=0.2, math=math)
-        j = ran.index(k)
-        wpb = mirror[j * (LAYERS + 1):(j + 1) * (LAYERS + 1)]     # packs of Wb_4 .. Wb_0, Wb_x
-        # dy_i is needed for the block's own input gradient or for the weight gradient of layer i or a layer below it
-        lowest = 0 if f"rdb.{k}" in dxs else min(
-            [i for i in range(LAYERS) if pre + f"layers.{i}.0.weight" in G.plan.wgrad or pre + f"layers.{i}.0.bias" in G.plan.wgrad],
-            default=LAYERS)
-        for i in range(LAYERS - 1, lowest - 1, -1):
-            cinb = F + GROWTH * (LAYERS - 1 - i)            # channels [0, cinb) = gout, dy_4 .. dy_{i+1}
-            dy = dcat.y(LAYERS - 1 - i)                      # slot of dy_i (channels [cinb, cinb + 32) of the buffer)
-            if sv.bits is not None:
-                K.conv_forward(dcat.inp(cinb), wpb[LAYERS - 1 - i], None, dy, 3,
-                               math=math, bits=sv.bits[k][i], bits_mode=2, center_cin=ctr)
-            else:
-                K.conv_forward(dcat.inp(cinb), wpb[LAYERS - 1 - i], None, dy, 3,
-                               mask=cat.y(i), mask_c0=0, mask_c1=GROWTH, math=math, center_cin=ctr)
-            cin = F + GROWTH * i
-            _wgrad(cat.inp(cin), cin, dy, G, pre + f"layers.{i}.0.weight", pre + f"layers.{i}.0.bias", wq, 3,
-                   math=math)
-        if f"rdb.{k}" not in dxs:
-            break
-        nxt = dcats[(k - 1) & 1].x() if k > 0 else Sl(dagg)
-        K.conv_forward(dcat.inp(g.CAT), wpb[LAYERS], None, nxt, 3, res=gout, math=math, center_cin=ctr)
-    K.TIMER_TAG = ""
-    if "cbam" not in run:
-        return None
-    dprev = Sl(dagg)
-    if dinter is not None:
-        # `aggregated` (the CBAM's output, block 0's input): its gradient is complete here
-        K.inject_nchw([(dprev, [dinter[2 * T]])])
-
-    _capture("dagg", lambda: dprev.t[..., dprev.coff:dprev.coff + F].float())
-    # ---- CBAM
-    w1 = P["temporal_aggregator.refine.channel_attention.fc.0.weight"]
-    w2 = P["temporal_aggregator.refine.channel_attention.fc.2.weight"]
-    w7 = P["temporal_aggregator.refine.spatial_attention.conv.weight"]
-    dpre = _new(dev, B, H, W)
-    K.cbam_bwd_spatial_pre(dprev, sv.weighted, sv.ca, sv.sa, dpre)
-    dsm = _new(dev, B, H, W, 2)
-    # (frozen CBAM weights: the _ex forms, the same dsm / dgap_pix without the weight gradients)
-    K.cbam_bwd_spatial_conv(dpre, sv.sm, w7, dsm, G.get("temporal_aggregator.refine.spatial_attention.conv.weight"), ws)
-    fc0, fc2 = "temporal_aggregator.refine.channel_attention.fc.0.weight", "temporal_aggregator.refine.channel_attention.fc.2.weight"
-    if "cbam" not in dxs and fc0 not in G.plan.wgrad and fc2 not in G.plan.wgrad:
-        return None
-    dweighted = _new(dev, B, H, W, F, dtype=sv.cbam_dtype)
-    dca_partial = _new(dev, B, sv.nblk, F)
-    K.cbam_bwd_scale(dprev, sv.weighted, sv.ca, sv.sa, dsm, sv.amax, dweighted, dca_partial)
-    dgap_pix = _new(dev, B, F)
-    dw1, dw2 = G.get(fc0), G.get(fc2)
-    if (dw1 is None) != (dw2 is None):                     # one of the two frozen: the full form, the other into a sink
-        dw1, dw2 = (dw1 if dw1 is not None else torch.empty_like(P[fc0])), (dw2 if dw2 is not None else torch.empty_like(P[fc2]))
-    K.cbam_bwd_channel(dca_partial, sv.nblk, F, g.R, B, H * W, w1, w2, sv.gap, sv.hid, sv.ca, dw1, dw2, dgap_pix)
-    _capture("dgap_pix", lambda: dgap_pix)
-    if "cbam" not in dxs:
-        return None
-
-    # ---- softmax-weighted sum and the attention convs
-    daligned = _new(dev, B, H, W, T * F, dtype=sv.aligned.dtype)   # stored like `aligned` (bf16 in the bf16 activation mode)
-    dlogits = _new(dev, B, H, W, g.Tp)
-    K.tsum_backward(dweighted, dgap_pix, sv.aligned, sv.attn, T, F, daligned, dlogits)
-    pre = "temporal_aggregator.attention."
-    _wgrad(Sl(sv.a2), F, Sl(dlogits, T), G, pre + "4.weight", pre + "4.bias", wq, 3, math=math)
-    if "att.4" in dxs:
-        da2 = _new(dev, B, H, W, F, dtype=act_dtype)
-        K.conv_forward(Sl(dlogits), packs.get(pre + "4.weight", True, g.Tp, F), None, Sl(da2), 3,
-                       mask=Sl(sv.a2), mask_c0=0, mask_c1=F, math=math)
-        _capture("da2", lambda: da2.float())
-        _wgrad(Sl(sv.a1), F, Sl(da2), G, pre + "2.weight", pre + "2.bias", wq, 3, math=math)
-    if "att.2" in dxs:
-        da1 = _new(dev, B, H, W, F, dtype=act_dtype)
-        if sv.a1_bits is not None:
-            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3, math=math, bits=sv.a1_bits, bits_mode=2)
-        else:
-            K.conv_forward(Sl(da2), packs.get(pre + "2.weight", True, F, F), None, Sl(da1), 3,
-                           mask=Sl(sv.a1), mask_c0=0, mask_c1=F, math=math)
-        _capture("da1", lambda: da1.float())
-        _wgrad(Sl(sv.aligned), T * F, Sl(da1), G, pre + "0.weight", pre + "0.bias", wq, 3, math=math)
-    if "att.0" not in dxs:
-        # nothing before the attention convs needs a gradient: no motion or extractor backward
-        return None
-    K.conv_forward(Sl(da1), packs.get(pre + "0.weight", True, F, T * F), None, Sl(daligned), 3,
-                   accumulate=True, math=math)
-    if dinter is not None:
-        # `aligned[t]` into slice t; `features[c]` (the same tensor in the reference) into slice c too, which reaches the centre
-        # frame's feature gradient in both forms below (axpy_slice / the correlation gradient's addend)
-        K.inject_nchw([(Sl(daligned, F, t * F), [dinter[T + t]] + ([dinter[c]] if t == c else [])) for t in range(T)])
-    if not feat16:
-        K.axpy_slice(Sl(dfeat_c), Sl(daligned, F, c * F))
-    _capture("dweighted", lambda: dweighted.float())
-    _capture("dlogits", dlogits)
-    _capture("daligned", daligned)
-
-    # ---- motion: warp, flow net, correlation
-    if NO:
-        # (feat16: the reference frames' term from the warp leaves as bf16 too and is an addend of the correlation gradient's pass)
-        dfeat_oth = _new(dev, NO, H, W, F, dtype=torch.bfloat16) if feat16 else dfeat_all[B:]
-        dflow = _new(dev, NO, H, W, 4)
-        for j in range(1, T):
-            t = g.slots[j]
-            lo, hi = (j - 1) * B, j * B
-            if deterministic:
-                K.warp_backward(Sl(daligned, F, t * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
-                                Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True, deterministic=True)
-            else:
-                K.warp_backward(Sl(daligned, F, t * F), Sl(sv.feat_oth).images(lo, hi), sv.flow[lo:hi],
-                                Sl(dfeat_oth).images(lo, hi), dflow[lo:hi], overwrite=True)
-        acts = sv.flow_acts          # [corr(96), f1(128), f2(64), f3(32), flow(4)]
-        chans = [81, 128, 64, 32, 2]
-        dy_t, dy_c = dflow, 2
-        for li, idx in reversed(list(enumerate((0, 2, 4, 6)))):
-            x_t = acts[li]
-            name = f"motion_estimator.flow_net.{idx}."
-            x_sl = Sl(x_t) if li > 0 else Sl(x_t, CORR_LD, 0)
-            _wgrad(x_sl, chans[li], Sl(dy_t, dy_c), G, name + "weight", name + "bias", wq, 3, math=math)
-            if f"flow.{idx}" not in dxs:
-                break
-            cin_store = dy_t.shape[-1]
-            wp = packs.get(name + "weight", True, cin_store, chans[li])
-            dx_t = _new(dev, NO, H, W, x_t.shape[-1], dtype=act_dtype if li > 0 else x_t.dtype)
-            if li > 0 and sv.flow_bits[li] is not None:
-                K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, math=math, bits=sv.flow_bits[li], bits_mode=2)
-            elif li > 0:
-                K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, mask=Sl(x_t), mask_c0=0,
-                               mask_c1=chans[li], math=math)
-            else:
-                # gradient of the correlation volume: the bf16 volume's 96-channel rows are written whole (zeros behind the
-                # 81 real channels) - a row of 84 channels would leave lines half written (fill reads)
-                full = dx_t.shape[-1] if dx_t.dtype == torch.bfloat16 else K.pad4(chans[li])
-                K.conv_forward(Sl(dy_t), wp, None, Sl(dx_t, chans[li]), 3, cout_store=full, math=math)
-            _capture(f"dflow_x{li}", lambda: dx_t.float())
-            dy_t, dy_c = dx_t, chans[li]
-        dcorr = dy_t
-        _capture("f1", acts[1])
-        _capture("dflow", dflow)
-        if "flow.0" not in dxs:
-            # a trained flow net in front of a frozen extractor (and frames without a gradient): the pass ends here
-            return None
-        _capture("dcorr", dcorr)
-        if dinter is not None:
-            # `features[t]`, t != c: the warp gradient has written its slot; the correlation gradients add to it / read it next
-            K.inject_nchw([(Sl(dfeat_oth).images((j - 1) * B, j * B), [dinter[g.slots[j]]]) for j in range(1, T)])
-        center = Sl(sv.aligned, F, c * F)
-        # The two correlation gradients are the LAST terms of the feature gradient.  bf16 activation mode: they write the finished
-        # sum as bf16 (dfeat16) instead of back into the fp32 accumulator - the extractor's backward reads it three times
-        # (BatchNorm sums, pointwise backward, the skip add of the first depthwise layer) at half the bytes, like every other
-        # gradient it consumes.
-        dfeat16 = _new(dev, NI, H, W, F, dtype=torch.bfloat16) if feat16 else None
-        if feat16:
-            K.correlation_backward(1, dcorr, center, Sl(dfeat_c), False, math=math, out16=dfeat16[B:], addends=(Sl(dfeat_oth),))
-        else:
-            K.correlation_backward(1, dcorr, center, Sl(dfeat_oth), True, math=math)
-        # gradient w.r.t. the centre frame's features: the T - 1 reference frames in one pass
-        if feat16:
-            K.correlation_backward(2, dcorr, Sl(sv.feat_oth), Sl(dfeat_c), False, math=math, groups=T - 1, out16=dfeat16[:B],
-                                   addends=(Sl(dfeat_c16), Sl(daligned, F, c * F)))
-            dfeat_all = dfeat16
-        else:
-            K.correlation_backward(2, dcorr, Sl(sv.feat_oth), Sl(dfeat_c), True, math=math, groups=T - 1)
-
-    # ---- feature extractor (all frames batched)
-    if "body.2" not in run:                     # (T = 1: no motion path, the attention convs' need decides)
-        return None
-    _capture("dfeat_all", lambda: dfeat_all.float())
-    dcur = dfeat_all
-    bn_sums = None                    # BatchNorm-backward sums of layer k, when the depthwise backward of layer k + 1 left them
-    bn_targets = None                 # ... and the dgamma / dbeta that call wrote
-    # (built and measured, off by default: with the sums in it the depthwise backward only fits its registers with two instead
-    # of five unrolled rows, and the step is 0.2 ms SLOWER than with the separate 0.54 ms reduce passes it replaces)
-    fuse_sums = os.environ.get("NVQ_FUSED_BN_SUMS", "0") != "0"
-    bn_sync = getattr(sv, "bn_sync", None) or [None, None, None]
-    if any(bn_sync):
-        fuse_sums = False             # a synchronised layer's sums are all-reduced between its reduce and finish phases
-    for k in (2, 1, 0):
-        pre = f"feature_extractor.body.{k}."
-        if f"body.{k}" not in run:                # the layers below need nothing either
-            break
-        need_dx = f"body.{k}" in dxs
-        dd = _new(dev, NI, H, W, F, dtype=act_dtype)
-        fused_bwd = (math == K.MATH_BF16 and act_dtype == torch.bfloat16 and F == 64 and sv.pws[k].dtype == torch.bfloat16
-                     and sv.dws[k].dtype == torch.bfloat16)
-        # the pass behind the BatchNorm sums forms p again from the d tile it stages anyway (one tensor pass fewer, the
-        # same bits) when the forward made p from this d and this weight in the fused pass
-        recompute = fused_bwd and getattr(sv, "pw_from_dwpw", False) and os.environ.get("NVQ_PW_RECOMPUTE", "1") != "0"
-        if bn_sync[k] is not None:
-            # synchronised BatchNorm: {sum g, sum g xhat} of every rank, dx from the global sums and the forward's global count
-            grp, st = bn_sync[k]
-            bsums = _new(dev, T * 2 * F, dtype=torch.float64)
-            cnt = K.bn_counts(st, T, F)
-            if fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
-                K.pw_bn_backward_reduce(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                                        bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
-                _allreduce_sum_(bsums, grp)
-                K.pw_bn_backward_finish(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                                        P[pre + "bn.bias"], P[pre + "pointwise.weight"], dd, G.get(pre + "pointwise.weight"), bsums,
-                                        cnt, ws, recompute=recompute)
-            else:
-                dp = _new(dev, NI, H, W, F, dtype=act_dtype)
-                K.bn_relu_backward_reduce(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                                          P[pre + "bn.bias"], bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
-                _allreduce_sum_(bsums, grp)
-                K.bn_relu_backward_finish(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                                          P[pre + "bn.bias"], bsums, cnt, dp)
-                _wgrad(Sl(sv.dws[k]), F, Sl(dp), G, pre + "pointwise.weight", None, wq, 1, math=math)
-                K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
-        elif fused_bwd and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
-            # BatchNorm backward + the pointwise conv's input and weight gradients in one pass behind the BatchNorm sums: dp is
-            # formed in LDS and never stored (nvq_pw_bn_backward; a frozen pointwise weight or BatchNorm affine: the _ex form)
-            dgam, dbet = bn_targets if bn_sums is not None else (G.get(pre + "bn.weight"), G.get(pre + "bn.bias"))
-            K.pw_bn_backward(dcur, sv.pws[k], sv.dws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                             P[pre + "bn.bias"], sv.training, P[pre + "pointwise.weight"], dd, dgam, dbet,
-                             G.get(pre + "pointwise.weight"), ws, sums_in=bn_sums, recompute=recompute)
-            bn_sums = None
-        else:
-            dp = _new(dev, NI, H, W, F, dtype=act_dtype)
-            K.bn_relu_backward(dcur, sv.pws[k], B, sv.bn_mean[k], sv.bn_invstd[k], P[pre + "bn.weight"],
-                               P[pre + "bn.bias"], sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
-            _wgrad(Sl(sv.dws[k]), F, Sl(dp), G, pre + "pointwise.weight", None, wq, 1, math=math)
-            K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
-        _capture(f"dd{k}", lambda: dd.float())
-        xin, xin_bn = sv.dw_in[k]
-        dww = G.get(pre + "depthwise.weight")
-        if fused_bwd and k > 0 and xin.dtype == torch.bfloat16 and os.environ.get("NVQ_FUSED_DW_BWD", "1") != "0":
-            # the depthwise conv's input gradient and weight gradient from one staged tile (nvq_dwconv_backward).  Not for the
-            # first layer: with the skip-path add and the head's ReLU mask in its epilogue the one-tile kernel takes as long as
-            # the two launches below (2.53 vs 2.54 ms: the epilogue operands are loaded where they are used, by 8 waves per CU).
-            # A frozen depthwise weight: dx alone (dweight None -> the _ex form)
-            if not need_dx and dww is None:
-                break
-            dx = _new(dev, NI, H, W, F, dtype=act_dtype)
-            prev = f"feature_extractor.body.{k - 1}."
-            if fuse_sums and sv.training and need_dx and os.environ.get("NVQ_FUSED_PW_BWD", "1") != "0":
-                # ... and the backward sums of layer k - 1's BatchNorm: this kernel holds its input (xin) and the gradient of
-                # its activation (dx), so the next pw_bn_backward needs no reduce pass of its own
-                bn_sums = _new(dev, T, 2, F)
-                bn_targets = (G.sink(prev + "bn.weight"), G.sink(prev + "bn.bias"))
-                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws,
-                                  bn_sums=bn_sums, bn_dgamma=bn_targets[0], bn_dbeta=bn_targets[1])
-            else:
-                K.dwconv_backward(xin, xin_bn, dd, P[pre + "depthwise.weight"], dx, dww, ws)
-            _capture(f"dx{k}", lambda: dx.float())
-            dcur = dx
-            continue
-        if dww is not None:
-            K.dwconv_wgrad(xin, dd, dww, ws, bn=xin_bn)
-        if not need_dx:
-            break
-        if k == 0 and sv.img8 is not None:
-            # dx + skip path, ReLU-masked by the head features: the gradient of the head conv, as bf16
-            dx = _new(dev, NI, H, W, F, dtype=act_dtype)
-            K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True, add=dfeat_all, mask=sv.feat0)
-        else:
-            dx = _new(dev, NI, H, W, F, dtype=act_dtype if k > 0 else torch.float32)
-            K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
-        _capture(f"dx{k}", lambda: dx.float())
-        dcur = dx
-    if "head" in run:
-        hw, hb = G.get("feature_extractor.head.0.weight"), G.get("feature_extractor.head.0.bias")
-        if hw is not None or hb is not None:
-            hw = hw if hw is not None else torch.empty_like(P["feature_extractor.head.0.weight"])
-            if sv.img8 is not None:
-                K.conv_wgrad(Sl(sv.img8), g.Cimg, Sl(dcur), hw, hb, ws, 3, math=math)
-            else:
-                # the skip path of  feat = body(h) + h  is summed inside the head kernel (dout2)
-                K.head_wgrad(sv.frames, g.slots, dcur, sv.feat0, hw, hb if hb is not None else G.sink("feature_extractor.head.0.bias"),
-                             ws, dout2=dfeat_all)
-    return dcur, dfeat_all
+            K.head_dgrad(x.dcur, wh, g.B, g.slots, dframes, act=sv.feat0, dout2=x.dfeat_all)
+        K.bicubic_adjoint(dout, sv.passmask, g.s, g.c, 1.0, dframes, accumulate=True)
 
 
 # ----------------------------------------------------------------------------- LightweightSuperResolution
@@ -951,19 +975,8 @@ def light_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, scale: int, train
         K.conv_forward(Sl(d), K.conv_pack(P[pre + "pointwise.weight"], False, F, math=math), None, Sl(p), 1, math=math)
         mean, invstd = _new(dev, 1, F), _new(dev, 1, F)
         grp = sync.get(pre + "bn") if (training and sync) else None
-        sv.bn_sync.append(None)
-        if grp is not None:
-            st = K.new_bn_stats(dev, 1, F)
-            K.bn_stats_reduce(p, B, st, ws)
-            _allreduce_sum_(st, grp)
-            K.bn_stats_finish(st, 1, [0], mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], BN_EPS, BN_MOM)
-            P[pre + "bn.num_batches_tracked"].add_(1)
-            sv.bn_sync[-1] = (grp, st)
-        elif training:
-            K.bn_stats(p, B, [0], mean, invstd, P[pre + "bn.running_mean"], P[pre + "bn.running_var"], ws, BN_EPS, BN_MOM)
-            P[pre + "bn.num_batches_tracked"].add_(1)
-        else:
-            K.bn_eval_stats(P[pre + "bn.running_mean"], P[pre + "bn.running_var"], 1, mean, invstd, BN_EPS)
+        sv.bn_sync.append((grp, K.new_bn_stats(dev, 1, F)) if grp is not None else None)
+        _bn_stats(P, pre + "bn.", p, B, [0], mean, invstd, ws, training, sv.bn_sync[-1])
         r = _new(dev, B, H, W, F, dtype=act_dtype)
         K.bn_apply_relu(p, B, mean, invstd, P[pre + "bn.weight"], P[pre + "bn.bias"], None, Sl(r), B)
         sv.dws.append(d); sv.pws.append(p); sv.acts.append(r); sv.bn_mean.append(mean); sv.bn_invstd.append(invstd)
@@ -998,8 +1011,7 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
     ws = workspace(dev)
     du = _new(dev, B, H, W, sv.Up)
     K.shuffle_clamp_backward(dout, sv.passmask, sv.scale, du)
-    last = sv.acts[-1]
-    _wgrad(Sl(last), F, Sl(du, sv.U), G, "net.6.weight", "net.6.bias", ws, 3, math=math)
+    _wgrad(Sl(sv.acts[-1]), F, Sl(du, sv.U), G, "net.6.weight", "net.6.bias", ws, 3, math=math)
     dcur = None
     if "up" in dxs:
         dcur = _new(dev, B, H, W, F)
@@ -1008,38 +1020,23 @@ def light_backward(P: Dict[str, torch.Tensor], sv: Saved, dout: torch.Tensor, G:
         if f"block.{j}" not in run:             # (nor any block below it)
             break
         pre = f"net.{LIGHT_BLOCKS[j]}."
-        dp = _new(dev, B, H, W, F, dtype=act_dtype)
-        bsync = sv.bn_sync[j] if getattr(sv, "bn_sync", None) else None
-        if bsync is not None:
-            # synchronised BatchNorm (see backward())
-            bsums = _new(dev, 2 * F, dtype=torch.float64)
-            K.bn_relu_backward_reduce(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                                      bsums, G.get(pre + "bn.weight"), G.get(pre + "bn.bias"), ws)
-            _allreduce_sum_(bsums, bsync[0])
-            K.bn_relu_backward_finish(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                                      bsums, K.bn_counts(bsync[1], 1, F), dp)
-        else:
-            K.bn_relu_backward(dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], P[pre + "bn.weight"], P[pre + "bn.bias"],
-                               sv.training, dp, G.sink(pre + "bn.weight"), G.sink(pre + "bn.bias"), ws)
+        dp = _bn_relu_bwd(P, G, pre, dcur, sv.pws[j], B, sv.bn_mean[j], sv.bn_invstd[j], sv.training, sv.bn_sync[j], ws)
         _wgrad(Sl(sv.dws[j]), F, Sl(dp), G, pre + "pointwise.weight", None, ws, 1, math=math)
         dww = G.get(pre + "depthwise.weight")
         if dww is None and f"block.{j}" not in dxs:
             break
-        dd = _new(dev, B, H, W, F, dtype=act_dtype)
+        dd = torch.empty_like(dp)
         K.conv_forward(Sl(dp), K.conv_pack(P[pre + "pointwise.weight"], True, F, F, math=math), None, Sl(dd), 1, math=math)
         xin = sv.feat0 if j == 0 else sv.acts[j - 1]
         if dww is not None:
             K.dwconv_wgrad(xin, dd, dww, ws)
         if f"block.{j}" not in dxs:
             break
-        dx = _new(dev, B, H, W, F, dtype=act_dtype if j > 0 else torch.float32)
-        K.dwconv_forward(dd, P[pre + "depthwise.weight"], dx, flip=True)
-        dcur = dx
-    if "head" in run:
-        hw, hb = G.get("net.0.weight"), G.get("net.0.bias")
-        if hw is not None or hb is not None:
-            K.head_wgrad(sv.frames, [0], dcur, sv.feat0, hw if hw is not None else torch.empty_like(P["net.0.weight"]),
-                         hb if hb is not None else torch.empty_like(P["net.0.bias"]), ws)
+        dcur = torch.empty_like(dd, dtype=act_dtype if j > 0 else torch.float32)
+        K.dwconv_forward(dd, P[pre + "depthwise.weight"], dcur, flip=True)
+    hw = G.pair("net.0.weight", "net.0.bias") if "head" in run else None
+    if hw is not None:
+        K.head_wgrad(sv.frames, [0], dcur, sv.feat0, hw[0], hw[1] if hw[1] is not None else torch.empty_like(P["net.0.bias"]), ws)
     G.check()
     if dframes is not None:
         K.head_dgrad(dcur, P["net.0.weight"], B, [0], dframes, act=sv.feat0)

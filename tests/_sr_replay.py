@@ -368,7 +368,7 @@ def walk_backward(S, P, q, emit):
     top = f"drdb.{NB - 1}" if NB else "dagg"
     emit("gff.dgrad", top, conv_dgrad(S["dg"], P["gff.0.weight"], q), grad=True)
     # ---- dense blocks: LAYERS + 1 stored roundings on the way to the block's input gradient (dy_4 .. dy_0 and the result:
-    # _engine._backward_body, the `dy = dcat.y(...)` convs and the `nxt` conv), LAYERS inner ones for a weight gradient
+    # _engine._bwd_rdb, the `dy = dcat.y(...)` convs and the `nxt` conv), LAYERS inner ones for a weight gradient
     for k in range(NB - 1, -1, -1):
         pre = f"residual_blocks.{k}."
         ys = [S[f"rdb.{k}.y.{i}"] for i in range(LAYERS)]
