@@ -264,6 +264,9 @@ SIGNATURES = {
     # federated optimisation: FedOpt server rules, the FedProx gradient (csrc/fedopt.hip)
     "nvq_fed_server_opt": (ci, [vp, cl, ci, vp, vp, vp, cf, ci, cf, cf, cf, cf, vp, vp, cf, cl, cl, cl, vp, vp]),
     "nvq_fed_prox_grad": (ci, [vp, vp, vp, cl, cf, vp]),
+    # compressed client updates: top-k with error feedback, QSGD quantisation (csrc/compress.hip)
+    "nvq_fed_compress_workspace_bytes": (sz, [ci, cl]),
+    "nvq_fed_compress": (ci, [vp, cl, ci, vp, cl, cl, ci, vp, cl, vp, cl, cl, vp, vp, sz, vp]),
     # ABR agent: vectorised environment, fused act, GAE, PPO loss (csrc/abr.hip)
     "nvq_abr_env_reset": (ci, [vp, vp, vp, vp, ci, ci, cl, ci, vp]),
     "nvq_abr_env_step": (ci, [vp, vp, vp, _IP, ci, ci, ci, vp, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -1735,6 +1738,34 @@ def fed_prox_grad(grad: torch.Tensor, theta: torch.Tensor, anchor: torch.Tensor,
     n = grad.numel()
     assert all(t.dtype == torch.float32 and t.numel() >= n for t in (grad, theta, anchor)), "grad / theta / anchor: fp32, n floats"
     check(lib().nvq_fed_prox_grad(ptr(grad), ptr(theta), ptr(anchor), n, float(mu), stream()), "nvq_fed_prox_grad")
+
+
+# ----------------------------------------------------------------------------- compressed client updates (csrc/compress.hip)
+FED_COMPRESS_MAX_LEVELS = 32767
+FED_COMPRESS_BLOCK_FLOATS = 8192    # floats of a row per workgroup of the compression passes (kCompressQuads quads)
+
+
+def fed_compress_workspace_bytes(K: int, n: int) -> int:
+    return int(lib().nvq_fed_compress_workspace_bytes(int(K), int(n)))
+
+
+def fed_compress(clients: torch.Tensor, n: int, base: Optional[torch.Tensor], k: int, levels: int, residual: Optional[torch.Tensor],
+                 slots: Optional[torch.Tensor], kept: Optional[torch.Tensor], ws: torch.Tensor, *, seed: int = 0,
+                 offset: int = 0) -> None:
+    """In place per row: a = (x - base) + residual row; the k largest |a| are kept (ties too; k = 0: all), quantised to ``levels``
+    steps of the row maximum with the Philox stream (seed, offset + row) (0: not); x' = base + c or base, the residual row receives
+    a - (x' - base) (nvq_fed_compress).  ``slots``: K int32 on the device, the residual row of every matrix row (None: the same
+    row); ``kept``: K int32."""
+    K, stride = _fed_rows(clients, n)
+    _fed_vectors(K, n, base=base)
+    residual_stride = 0
+    if residual is not None:
+        residual_stride = _rows_stride(residual, n, "residual")
+    assert slots is None or (residual is not None and slots.dtype == torch.int32 and slots.numel() >= K), "slots: K int32 values"
+    assert kept is None or (kept.dtype == torch.int32 and kept.numel() >= K), "kept: K int32 values"
+    check(lib().nvq_fed_compress(clients.data_ptr(), stride, K, ptr(base), n, int(k), int(levels),
+                                 None if residual is None else residual.data_ptr(), residual_stride, ptr(slots), int(seed),
+                                 int(offset), ptr(kept), ptr(ws), ws.numel() * ws.element_size(), stream()), "nvq_fed_compress")
 
 
 # ----------------------------------------------------------------------------- ABR agent (csrc/abr.hip)

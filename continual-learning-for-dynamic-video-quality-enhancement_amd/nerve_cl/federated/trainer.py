@@ -21,6 +21,7 @@ import torch.nn as nn
 from nerve_cl import _engine, _nvq
 from nerve_cl._bucket import segments_of
 from nerve_cl.federated._flat import check_clients, device_weights, finish_cpu, host_weights
+from nerve_cl.federated.compression import COMPRESSIONS, compress_updates_, topk_count
 from nerve_cl.federated.fedopt import ServerOptimizer
 from nerve_cl.federated.privacy import DPOptimizer, PrivacyConfig, _Seg
 
@@ -153,7 +154,7 @@ class FederatedTrainer:
     """``FederatedTrainer(model, num_clients=10, clients_per_round=5, local_epochs=5, *, lr=1e-4, batch_size=16, loss=None,
     privacy=None, update_clip=None, update_noise=0.0, server_lr=1.0, optimizer_impl="torch", seed=None, aggregator="fedavg",
     trim_ratio=0.1, num_byzantine=0, num_selected=None, after_client=None, server_optimizer=None, server_betas=(0.9, 0.99),
-    server_tau=1e-3, prox_mu=0.0)``
+    server_tau=1e-3, prox_mu=0.0, compression=None, compress_ratio=0.01, compress_levels=127, error_feedback=True)``
 
     ``model(inputs) -> outputs`` is trained on every client's ``(inputs, targets)`` (``set_client_data``) with a fresh
     ``AdamW(lr)`` for ``local_epochs`` passes in batches of ``batch_size``, taken in order; ``loss`` defaults to ``nn.MSELoss()``
@@ -200,6 +201,19 @@ class FederatedTrainer:
     cluster's model).  A bucketed network whose gradients are its bucket takes one ``nvq_fed_prox_grad``; loose parameters,
     networks with frozen layers and CPU modules one ``add_`` per parameter.  ``prox_mu = 0`` launches nothing.
 
+    ``compression``: one of ``COMPRESSIONS`` (``nerve_cl.federated.compression``; no clusters).  After the last
+    client of a round and before the aggregation, every HIP-backed network's rows take one ``nvq_fed_compress`` against the round
+    snapshot: ``"topk"`` keeps the ``topk_count(n, compress_ratio)`` largest coordinates of every client's update, ``"quant"``
+    quantises the update to ``compress_levels`` levels of its largest magnitude (QSGD), ``"topk_quant"`` does both.  With
+    ``error_feedback`` what a client did not send is kept in its row of a persistent ``[num_clients, n]`` residual matrix per
+    network (a client takes the next free row when it is first selected) and added to its next update;
+    ``compression_state_dict()`` / ``load_compression_state_dict()`` carry these.  The rules above see only the compressed rows, so
+    every one of them works unchanged.  BatchNorm statistics, the rest matrix next to HIP-backed networks and integer buffers are
+    never compressed; for a model without HIP-backed networks the floating parameters are packed first (as with
+    ``server_optimizer``) and only their columns are.  The Philox seed is the second draw of ``random.Random(seed)``, network j in
+    round g (counted from 0) uses the streams ``(g * (len(nets) + 1) + j) * 64 + row``.  The round dict gains ``"kept"``: per
+    compressed matrix the kept coordinates of every row (int32 on the device; ``train_round`` gives lists).
+
     On the GPU the weights of every HIP-backed network inside ``model`` are one flat buffer: the clients' results are the rows of a
     persistent ``[clients_per_round, n]`` matrix and a round ends with one ``nvq_fed_delta_norms`` (only with ``update_clip``) and
     one ``nvq_fed_aggregate`` writing into ``flat_theta()``.  Everything else in the state dict (BatchNorm statistics, loose
@@ -213,7 +227,8 @@ class FederatedTrainer:
                  optimizer_impl: str = "torch", seed: Optional[int] = None, num_clusters: int = 1, cluster_after: int = 0,
                  aggregator: str = "fedavg", trim_ratio: float = 0.1, num_byzantine: int = 0, num_selected: Optional[int] = None,
                  after_client=None, server_optimizer: Optional[str] = None, server_betas: Sequence[float] = (0.9, 0.99),
-                 server_tau: float = 1e-3, prox_mu: float = 0.0):
+                 server_tau: float = 1e-3, prox_mu: float = 0.0, compression: Optional[str] = None, compress_ratio: float = 0.01,
+                 compress_levels: int = 127, error_feedback: bool = True):
         if not 1 <= num_clusters <= _nvq.CLUSTER_MAX:
             raise ValueError(f"num_clusters: 1 .. {_nvq.CLUSTER_MAX}")
         if server_optimizer is not None:
@@ -222,6 +237,16 @@ class FederatedTrainer:
                 raise NotImplementedError("server_optimizer with num_clusters > 1: there are no per-cluster server moments")
         if not prox_mu >= 0.0:
             raise ValueError(f"invalid prox_mu: {prox_mu}")
+        if compression is not None:
+            if compression not in COMPRESSIONS:
+                raise ValueError(f"compression {compression!r}: one of {', '.join(COMPRESSIONS)}")
+            if not 0.0 < compress_ratio <= 1.0:
+                raise ValueError(f"invalid compress_ratio: {compress_ratio}")
+            if int(compress_levels) != compress_levels or not 1 <= compress_levels <= _nvq.FED_COMPRESS_MAX_LEVELS:
+                raise ValueError(f"compress_levels: 1 .. {_nvq.FED_COMPRESS_MAX_LEVELS}, got {compress_levels}")
+            if num_clusters > 1:
+                raise NotImplementedError("compression with num_clusters > 1: every cluster's clients start from another model, "
+                                          "so there is no single base their rows are updates of")
         if cluster_after < 0:
             raise ValueError(f"invalid cluster_after: {cluster_after}")
         if num_clusters > 1 and num_clients > _nvq.FED_MAX_CLIENTS:
@@ -267,6 +292,16 @@ class FederatedTrainer:
         self.seed = seed
         self._rng = random.Random(seed) if seed is not None else random
         self._noise_seed = random.Random(seed).getrandbits(62) if seed is not None else random.getrandbits(62)
+        self.compression, self.compress_ratio = compression, float(compress_ratio)
+        self.compress_levels, self.error_feedback = int(compress_levels), bool(error_feedback)
+        self._compress_seed = 0
+        if compression is not None:                    # a stream of its own: the second draw, the first is the noise seed
+            draws = random.Random(seed) if seed is not None else random
+            if seed is not None:
+                draws.getrandbits(62)
+            self._compress_seed = draws.getrandbits(62)
+        self._residuals: Optional[List[torch.Tensor]] = None   # per compressed matrix [num_clients, n], made with the plan
+        self._residual_slot: Dict[int, int] = {}              # client id -> its row of the residual matrices
         self.client_data: Dict[int, Tuple] = {}
         self.global_round = 0
         self.last_selected: List[int] = []
@@ -291,7 +326,8 @@ class FederatedTrainer:
         rest_names = [k for k, t in sd.items() if k not in flat_names and _is_float(t)]
         params = dict(model.named_parameters())
         n_params = 0
-        if self.server_optimizer is not None and not nets:     # the server optimizer steps parameters only: they come first
+        if (self.server_optimizer is not None or self.compression is not None) and not nets:
+            # the server optimizer steps, and the compression sparsifies, parameters only: they come first
             first = [k for k in rest_names if k in params]
             rest_names = first + [k for k in rest_names if k not in params]
             n_params = _Pack([sd[k] for k in first]).total
@@ -312,6 +348,9 @@ class FederatedTrainer:
         plan["rest_snap"] = torch.zeros(max(p.total, 4), dtype=torch.float32, device=dev)
         plan["int_rows"] = [torch.zeros((K,) + tuple(t.shape), dtype=t.dtype, device=t.device) for t in rest_i]
         plan["int_snap"] = [torch.zeros_like(t) for t in rest_i]
+        if self.compression is not None and self.error_feedback and self._residuals is None:
+            sizes = [r.shape[1] for r in plan["rows"]] if nets else ([n_params] if n_params else [])
+            self._residuals = [torch.zeros(self.num_clients, n, dtype=torch.float32, device=dev) for n in sizes]
         return plan
 
     def _make_optimizer(self):
@@ -464,6 +503,54 @@ class FederatedTrainer:
                 _nvq.fed_aggregate(rows, n, base, w, sq, out, **kw)
 
         self._aggregate(plan, K, w, step)
+
+    # ------------------------------------------------------------------ compressed updates
+    @torch.no_grad()
+    def _compress(self, plan, selected: List[int], K: int) -> List[torch.Tensor]:
+        """Every HIP-backed network's rows, or without one the parameter columns of the rest matrix, take one ``compress_updates_``
+        against the round snapshot; returns the kept counts per matrix."""
+        nets, mode = plan["nets"], self.compression
+        if nets:
+            mats = [(rows[:K], snap) for rows, snap in zip(plan["rows"], plan["snaps"])]
+        else:
+            n_p = plan["n_params"]
+            mats = [(plan["rest_rows"][:K, :n_p], plan["rest_snap"][:n_p])] if n_p else []
+        slots = None
+        if self.error_feedback and mats:
+            for cid in selected:
+                if cid not in self._residual_slot:
+                    if len(self._residual_slot) >= self.num_clients:
+                        raise ValueError(f"client {cid} is client number {len(self._residual_slot) + 1}, but num_clients = "
+                                         f"{self.num_clients}: the residual matrices have one row per client")
+                    self._residual_slot[cid] = len(self._residual_slot)
+            slots = [self._residual_slot[cid] for cid in selected]
+        kept = []
+        for j, (rows, snap) in enumerate(mats):
+            n = rows.shape[1]
+            kept.append(compress_updates_(rows, snap, k=topk_count(n, self.compress_ratio) if mode.startswith("topk") else None,
+                                          levels=self.compress_levels if mode.endswith("quant") else 0,
+                                          residual=self._residuals[j] if slots is not None else None, slots=slots,
+                                          seed=self._compress_seed, offset=(self.global_round * (len(nets) + 1) + j) * 64))
+        return kept
+
+    def compression_state_dict(self) -> Dict[str, object]:
+        """the error-feedback state: the mode, every client's row and one residual matrix per compressed matrix (none before the
+        first round, or without ``error_feedback``)"""
+        return {"compression": self.compression, "slots": dict(self._residual_slot),
+                "residuals": [r.clone() for r in self._residuals or []]}
+
+    def load_compression_state_dict(self, state: Dict[str, object]) -> None:
+        if state["compression"] != self.compression:
+            raise ValueError(f"the state is {state['compression']!r}'s, this trainer runs {self.compression!r}")
+        if self._plan is None:
+            self._plan = self._build_plan()
+        mine = self._residuals or []
+        theirs = state["residuals"] or [torch.zeros_like(b) for b in mine]      # saved before the first round: still zero
+        if len(theirs) != len(mine) or any(a.shape != b.shape for a, b in zip(theirs, mine)):
+            raise ValueError("the residual matrices of the state do not fit this trainer's model and num_clients")
+        for a, b in zip(theirs, mine):
+            b.copy_(a)
+        self._residual_slot = {int(c): int(s) for c, s in state["slots"].items()}
 
     # ------------------------------------------------------------------ robust rounds
     def _robust_plan(self, counts: List[int]) -> Tuple[int, int]:
@@ -669,6 +756,7 @@ class FederatedTrainer:
                     rows[k].copy_(t)
                 plan["weights"][k].fill_(float(cnt))
         selection = None
+        kept = self._compress(plan, selected, K) if K and self.compression is not None else None
         if K and clustered:
             self._aggregate_clusters(plan, selected, counts, K, split)
         elif K and robust is not None:
@@ -683,6 +771,8 @@ class FederatedTrainer:
             out["clusters"] = self.cluster_sizes()
         if selection is not None:
             out["selected_weights"] = selection
+        if kept is not None:
+            out["kept"] = kept
         return out
 
     def train_round(self) -> Dict[str, float]:
@@ -692,4 +782,6 @@ class FederatedTrainer:
         out["train_loss"] = float(out["train_loss"])
         if "selected_weights" in out:
             out["selected_weights"] = out["selected_weights"].tolist()
+        if "kept" in out:
+            out["kept"] = [t.tolist() for t in out["kept"]]
         return out

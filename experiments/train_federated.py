@@ -17,7 +17,12 @@ weights.  With either option the evaluation loss of the global model over all cl
 breaks under ``--poison 1``, the robust rules hold.  ``--server-opt`` runs a FedOpt server optimizer on the aggregated update
 (``fedavgm``, ``fedadagrad``, ``fedadam``, ``fedyogi`` with ``--server-beta1`` / ``--server-beta2`` / ``--server-tau``; ``--server-lr``
 is its learning rate, and 1.0 is far too large for the adaptive ones) and ``--prox-mu`` adds FedProx's proximal term to the local
-steps (csrc/fedopt.hip); ``--eval`` prints the evaluation loss after every round.  The ``server`` and ``client`` modes need the flwr transport and exit saying so.
+steps (csrc/fedopt.hip); ``--eval`` prints the evaluation loss after every round.  ``--compress`` compresses
+every client's update before the aggregation (csrc/compress.hip): ``topk`` keeps the ``--compress-ratio``
+largest coordinates, ``quant`` quantises to ``--compress-levels`` levels (QSGD), ``topk_quant`` does both; what is not sent stays in
+the client's residual for the next round unless ``--no-error-feedback``.  Every round then prints the mean kept share and the
+modelled bytes sent as a fraction of dense fp32 (``wire_bytes``: a model, nothing is serialised).  The ``server`` and ``client``
+modes need the flwr transport and exit saying so.
 """
 import argparse
 from pathlib import Path
@@ -27,7 +32,7 @@ import torch
 
 from _common import OPTIMIZER_IMPLS, pick_device
 from nerve_cl import ops
-from nerve_cl.federated import SERVER_OPTIMIZERS, FederatedTrainer, PrivacyConfig
+from nerve_cl.federated import COMPRESSIONS, SERVER_OPTIMIZERS, FederatedTrainer, PrivacyConfig, wire_bytes
 from nerve_cl.federated.trainer import AGGREGATORS
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 from train_continual import _ClipAdapter, configure_precision
@@ -65,6 +70,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--server-tau", type=float, default=1e-3, help="--server-opt: adaptivity, the floor of the denominator")
     ap.add_argument("--prox-mu", type=float, default=0.0, metavar="MU",
                     help="FedProx: add MU / 2 |theta - theta_round|^2 to every client's objective (default 0: off)")
+    ap.add_argument("--compress", choices=COMPRESSIONS, default=None,
+                    help="compress every client's update before the aggregation: top-k sparsification, QSGD quantisation or both "
+                         "(no --clusters)")
+    ap.add_argument("--compress-ratio", type=float, default=0.01, metavar="R", help="--compress topk*: the share of coordinates kept")
+    ap.add_argument("--compress-levels", type=int, default=127, metavar="S", help="--compress *quant: quantisation levels, 1 .. 32767")
+    ap.add_argument("--no-error-feedback", action="store_true",
+                    help="--compress: drop what a client did not send instead of adding it to its next update")
     ap.add_argument("--clusters", type=int, default=1, metavar="C",
                     help="cluster the clients by their updates into C groups with one model each (default 1: plain FedAvg)")
     ap.add_argument("--cluster-after", type=int, default=0, metavar="R", help="plain FedAvg rounds before the round that clusters")
@@ -137,7 +149,8 @@ def main() -> None:
                                aggregator=args.aggregator, trim_ratio=args.trim_ratio, num_byzantine=args.num_byzantine,
                                after_client=after_client if args.poison > 0 else None, server_optimizer=args.server_opt,
                                server_betas=(args.server_beta1, args.server_beta2), server_tau=args.server_tau,
-                               prox_mu=args.prox_mu)
+                               prox_mu=args.prox_mu, compression=args.compress, compress_ratio=args.compress_ratio,
+                               compress_levels=args.compress_levels, error_feedback=not args.no_error_feedback)
     for cid in range(args.num_clients):
         lr, hr = create_client_data(cid, args.samples)
         trainer.set_client_data(cid, (lr.to(device), hr.to(device)))          # on the device: a round copies nothing from the host
@@ -150,6 +163,13 @@ def main() -> None:
         if args.eval or args.poison > 0 or args.aggregator != "fedavg":
             chosen = f", selected {[int(w) for w in m['selected_weights']]}" if "selected_weights" in m else ""
             print(f"  evaluation loss of the global model {evaluate(trainer):.4f}{chosen}")
+        if "kept" in m:
+            levels = args.compress_levels if args.compress.endswith("quant") else 0
+            sizes = [r.shape[1] for r in trainer._plan["rows"]] or [trainer._plan["n_params"]]
+            share = sum(sum(ks) / (len(ks) * n) for ks, n in zip(m["kept"], sizes)) / len(sizes)
+            sent = sum(wire_bytes(n, k, levels) for ks, n in zip(m["kept"], sizes) for k in ks)
+            dense = sum(4 * n * len(ks) for ks, n in zip(m["kept"], sizes))
+            print(f"  compressed updates: kept {share:.4f} of the coordinates, modelled {sent / dense:.4f} of the dense bytes")
         if args.clusters > 1 and m["round"] == args.cluster_after + 1:
             print(f"  clusters after the split: sizes {m['clusters']}, clients {trainer.client_cluster}")
     if trainer.cluster_models is not None:

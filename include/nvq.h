@@ -1094,6 +1094,37 @@ int nvq_fed_server_opt(const float* clients, long stride, int K, const float* ba
                        float noise_std, long seed, long offset, long n, float* out, void* stream);
 int nvq_fed_prox_grad(float* grad, const float* theta, const float* anchor, long n, float mu, void* stream);
 
+/* ------------------------------------------------------------------ Compressed client updates: top-k sparsification with error
+ * feedback and QSGD stochastic quantisation (csrc/compress.hip).  The same client matrix, changed in place
+ * row by row, so every rule above works on the compressed rows unchanged.  Integer counters only (LDS histograms merged by integer
+ * atomics), no float atomics: the same bits on every call and at every pointer alignment.
+ *
+ * nvq_fed_compress: x = row r of clients, b = base (NULL: zeros), e = row slots[r] of residual (an [M][residual_stride] matrix;
+ * slots = K device ints, distinct and in range, which is the caller's to guarantee; NULL: row r; residual == NULL: no e).  Per
+ * coordinate i, every step one correctly rounded IEEE operation or exact:
+ *   1. a_i = (float) (((double) x_i - (double) b_i) + (double) e_i); without a residual there is no + e_i.
+ *   2. key_i = the 31 magnitude bits of a_i as an unsigned integer; every NaN has the largest key, after inf.
+ *   3. 1 <= k < n: T = the k-th largest key of the row, i is kept iff key_i >= T; ties at T are all kept, so kept[r] >= k, and
+ *      kept[r] == k when the k-th and (k + 1)-th magnitudes differ.  k == 0 or k >= n: everything is kept, kept[r] = n.  The
+ *      selection is exact (a radix select on the keys).
+ *   4. levels = s in 1 .. 32767 (0: off): scale = the float whose key is the row's largest key.  scale 0, inf or NaN: the row is
+ *      not quantised, c_i = a_i.  Else for a kept i: u_i = ((w_i >> 8) + 0.5) 2^-24 with w_i word i & 3 of Philox quad i >> 2 of
+ *      the stream (seed, offset + r) ("Noise" above), t = (double) |a_i| * s / (double) scale (the product, then the quotient),
+ *      xi_i = floor(t + u_i), c_i = (float) (sgn(a_i) xi_i (double) scale / s) (the product, then the quotient).  E[xi] = t.
+ *      levels == 0: c_i = a_i.
+ *   5. kept: x'_i = (float) ((double) b_i + (double) c_i); dropped: x'_i = b_i.
+ *   6. e'_i = (float) ((double) a_i - ((double) x'_i - (double) b_i)), stored as 0 when it is not finite.
+ * clients receives x', the residual row e' (rows that slots does not name are not touched), kept (K device ints, may be NULL)
+ * the number of kept coordinates per row.  1 <= K <= 64, stride >= n, residual_stride >= n, k >= 0, n < 2^31.  Launches: with
+ * top-k three counting passes (digits of 11, 10 and 10 bits; the first stores a into the residual row, so the later ones read
+ * one stream) and the sweep; without it one pass for the row maxima (only with levels > 0) and the sweep.  The workspace
+ * (nvq_fed_compress_workspace_bytes, 4-byte aligned; NVQ_EWORKSPACE when short) is cleared on the stream.  k == 0 && levels == 0
+ * && residual == NULL changes nothing and fills kept with n.  base, residual and workspace must not alias clients. */
+size_t nvq_fed_compress_workspace_bytes(int K, long n);
+int nvq_fed_compress(float* clients, long stride, int K, const float* base, long n, long k, int levels, float* residual,
+                     long residual_stride, const int* slots, long seed, long offset, int* kept, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ ABR agent: vectorised streaming environment, fused act,
  * GAE and the PPO loss (csrc/abr.hip).  No atomics; sums in double in a fixed order; plain vector stores.
  *
