@@ -276,6 +276,10 @@ SIGNATURES = {
     "nvq_abr_adv_stats": (ci, [vp, cl, vp, vp]),
     "nvq_ppo_loss_workspace_bytes": (sz, [cl]),
     "nvq_ppo_loss": (ci, [vp, vp, vp, vp, vp, vp, cl, _IP, ci, cf, cf, cf, vp, vp, vp, sz, vp]),
+    # Gradient Episodic Memory: Gram of the references and the gradient, the QP, the projection (csrc/gem.hip)
+    "nvq_gem_gram": (ci, [vp, cl, ci, vp, cl, vp, ci, vp, sz, vp]),
+    "nvq_gem_solve": (ci, [vp, ci, cf, cf, ci, vp, vp, vp]),
+    "nvq_gem_project": (ci, [vp, vp, cl, ci, cl, vp, vp]),
 }
 
 
@@ -1356,6 +1360,41 @@ def bucket_project(g: torch.Tensor, r: torch.Tensor, acc: torch.Tensor):
     """g -= acc[3] * r in place (untouched when acc[3] == 0)"""
     assert g.dtype == torch.float32 and r.dtype == torch.float32 and r.numel() == g.numel()
     check(lib().nvq_bucket_project(ptr(g), ptr(r), g.numel(), _bucket_acc(acc), stream()), "nvq_bucket_project")
+
+
+GEM_MAX_TASKS = 15
+
+
+def _gem_rows(refs: torch.Tensor, T: int, g: torch.Tensor, what: str) -> int:
+    """row stride of the [rows >= T][stride] fp32 reference matrix whose first T rows go with the flat fp32 gradient g"""
+    assert 1 <= T <= GEM_MAX_TASKS and refs.dim() == 2 and refs.shape[0] >= T, f"{what}: 1 .. {GEM_MAX_TASKS} reference rows"
+    assert g.dtype == torch.float32 and g.dim() == 1, f"{what}: g is a flat fp32 tensor"
+    return _rows_stride(refs, g.numel(), what)
+
+
+def gem_gram(refs: torch.Tensor, T: int, g: torch.Tensor, gram: torch.Tensor, ws: torch.Tensor, accumulate: bool = False) -> None:
+    """gram[i, j] (+)= row_i . row_j for the first T rows of refs and g as row T; 16 x 16 float64, symmetric bit for bit, zero
+    outside (T + 1)^2 (nvq_gem_gram)"""
+    stride = _gem_rows(refs, T, g, "gem_gram")
+    assert gram.dtype == torch.float64 and gram.numel() == 256, "gram: 16 x 16 float64"
+    check(lib().nvq_gem_gram(refs.data_ptr(), stride, int(T), ptr(g), g.numel(), ptr(gram), int(accumulate), ptr(ws),
+                             ws.numel() * ws.element_size(), stream()), "nvq_gem_gram")
+
+
+def gem_solve(gram: torch.Tensor, T: int, margin: float, eps: float, eps_relative: bool, v: torch.Tensor, stats: torch.Tensor) -> None:
+    """v (16 float64) = GEM's multipliers from the Gram, zeros when nothing is violated; stats: the 8 float64 slots (nvq_gem_solve)"""
+    assert gram.dtype == torch.float64 and gram.numel() == 256, "gram: 16 x 16 float64"
+    assert v.dtype == torch.float64 and v.numel() >= 16 and stats.dtype == torch.float64 and stats.numel() >= 8, \
+        "v: 16 float64, stats: 8 float64 slots"
+    check(lib().nvq_gem_solve(ptr(gram), int(T), float(margin), float(eps), int(eps_relative), ptr(v), ptr(stats), stream()),
+          "nvq_gem_solve")
+
+
+def gem_project(g: torch.Tensor, refs: torch.Tensor, T: int, v: torch.Tensor) -> None:
+    """g += sum_t v[t] refs[t] in place, in double, rounded once; untouched when v == 0 (nvq_gem_project)"""
+    stride = _gem_rows(refs, T, g, "gem_project")
+    assert v.dtype == torch.float64 and v.numel() >= 16, "v: 16 float64"
+    check(lib().nvq_gem_project(ptr(g), refs.data_ptr(), stride, int(T), g.numel(), ptr(v), stream()), "nvq_gem_project")
 
 
 def bucket_clip(g: torch.Tensor, acc: torch.Tensor, max_norm: float, norm_out: Optional[torch.Tensor]):

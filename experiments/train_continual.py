@@ -18,6 +18,9 @@ output and cosine feature distillation terms of csrc/distill.hip (DESIGN.md sect
 ``--strategy agem`` (with ``--agem-ref-batch``; the memory flags of the replay strategy apply) is A-GEM: before every step the
 gradient on a batch from the memory is taken as the reference, and a conflicting step gradient is projected onto its orthogonal
 complement in place in the gradient bucket, decision included on the device (csrc/bucket_ops.hip).
+``--strategy gem`` (with ``--gem-ref-batch`` / ``--gem-margin`` / ``--gem-eps`` / ``--gem-eps-relative`` / ``--gem-refresh``; the
+memory flags apply) is GEM: one reference gradient per earlier task, drawn from the memory by content type, and the step gradient
+is moved by the solution of a small quadratic program so that it opposes none of them (csrc/gem.hip).
 ``--clip-grad-norm X`` clips the global gradient norm before every optimizer step of any strategy with the same kernels.
 ``--drift {mmd,psi}`` (with ``--drift-grid G``) reports, before every task but the first, whether the task's LR frames have drifted
 from the previous task's: nerve_cl.drift.DriftDetector on per-cell mean / deviation descriptors of the frames (csrc/drift.hip,
@@ -33,7 +36,7 @@ from torch.utils.data import DataLoader, TensorDataset
 from _common import (LOSS_CHOICES, add_optimizer_arguments, ema_weights, make_optimizer, optimizer_impl, pick_device, resolve_loss,
                      shard)
 from nerve_cl import drift, metrics, ops, parallel
-from nerve_cl.continual import AGEM, EWC, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
+from nerve_cl.continual import AGEM, EWC, GEM, DeviceEpisodicMemory, EpisodicMemory, FOMAML, ContinualDistillation  # noqa: F401
 from nerve_cl.models import EnhancementConfig, EnhancementEngine
 
 OFFSETS = {"sports": 0.2, "animation": -0.2, "movie": 0.0, "news": 0.1}
@@ -260,6 +263,48 @@ def train_with_agem(model, tasks, memory, config, rank=0, epochs=5, optimizer=No
     return model
 
 
+def train_with_gem(model, tasks, memory, config, rank=0, epochs=5, optimizer=None):
+    """train_with_agem with one constraint per earlier task: every --gem-refresh-th step the references are taken again."""
+    device = next(model.parameters()).device
+    if optimizer is None:
+        optimizer = build_optimizer(model, config)
+    criterion = make_criterion(config)
+    adapter = _ClipAdapter(model)
+    gem = GEM(adapter, memory, ref_batch_size=config.get("gem_ref_batch", 8), margin=config.get("gem_margin", 0.5),
+              eps=config.get("gem_eps", 1e-3), eps_relative=config.get("gem_eps_relative", False))
+    refresh = max(int(config.get("gem_refresh", 1)), 1)
+    say = print if rank == 0 else (lambda *a, **k: None)
+    step = 0
+    for task_id, (task_name, (lr, hr)) in enumerate(tasks):
+        report_drift(config, task_id, lr, say)
+        say(f"\n=== Training on Task {task_id}: {task_name} ===")
+        for epoch in range(epochs):
+            model.train()
+            idx = torch.randperm(len(lr))[:16]
+            lr_b, hr_b = lr[idx].to(device), hr[idx].to(device)
+            if step % refresh == 0:
+                gem.compute_references(criterion)                   # 0 rows (and no constraint) during the first task
+            step += 1
+            optimizer.zero_grad()
+            out = adapter(lr_b)
+            loss = criterion(out, hr_b)
+            loss.backward()
+            gem.project()
+            clip_gradients(model, config)
+            optimizer.step()
+            meter = None
+            if config.get("metrics"):
+                meter = metrics.QualityMeter()
+                meter.update(out, hr_b)
+            st = gem.stats.tolist()                                 # one host read per printed line
+            say(f"  Epoch {epoch + 1}: Loss={loss.item():.4f} min cos(g,r_t)={st[7]:+.4f} active={int(st[1])} |g|={st[5] ** 0.5:.3e}"
+                f"{metrics_suffix(meter)}")
+        store_task(memory, lr, hr, task_name)
+        gem.add_task(task_name)
+        say(f"  Memory size: {len(memory)}  projections so far: {gem.num_projections()}")
+    return model
+
+
 def train_with_distill(model, tasks, config, rank=0, epochs=5, optimizer=None):
     """Single process, unsharded.  With the MSE criterion the task term is folded into the distillation kernel (fold_task)."""
     device = next(model.parameters()).device
@@ -299,9 +344,18 @@ def train_with_distill(model, tasks, config, rank=0, epochs=5, optimizer=None):
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--strategy", choices=["ewc", "replay", "maml", "distill", "agem"], default="ewc")
+    ap.add_argument("--strategy", choices=["ewc", "replay", "maml", "distill", "agem", "gem"], default="ewc")
     ap.add_argument("--agem-ref-batch", type=int, default=8,
                     help="agem strategy: samples drawn from the memory for the reference gradient of every step")
+    ap.add_argument("--gem-ref-batch", type=int, default=8,
+                    help="gem strategy: samples drawn from the memory per earlier task for its reference gradient")
+    ap.add_argument("--gem-margin", type=float, default=0.5,
+                    help="gem strategy: lower bound of the multipliers (the published 'memory strength')")
+    ap.add_argument("--gem-eps", type=float, default=1e-3, help="gem strategy: ridge added to the references' Gram matrix")
+    ap.add_argument("--gem-eps-relative", action="store_true",
+                    help="gem strategy: the ridge is --gem-eps times the largest squared reference norm")
+    ap.add_argument("--gem-refresh", type=int, default=1, metavar="K",
+                    help="gem strategy: take the reference gradients again every K-th step (1: every step, the published method)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global 2-norm of the gradient to X before every optimizer step (any strategy; default: no clipping)")
     ap.add_argument("--distill-alpha", type=float, default=0.5,
@@ -350,6 +404,9 @@ def main() -> None:
     if args.strategy == "maml" and (args.ema_decay is not None or args.optimizer_impl != "torch"):
         ap.error("--strategy maml trains nothing: --optimizer-impl / --ema-decay have no effect there")
 
+    if args.strategy == "gem" and args.tasks - 1 > 15:
+        ap.error("--strategy gem keeps at most 15 earlier tasks")
+
     device, rank, world = pick_device()
     torch.manual_seed(0)
     model = EnhancementEngine(EnhancementConfig(frame_recovery_enabled=False, super_resolution_enabled=True,
@@ -361,19 +418,21 @@ def main() -> None:
     tasks = [(ct, create_task_data(ct, args.samples)) for ct in list(OFFSETS)[:args.tasks]]
     config = {"ewc_lambda": args.ewc_lambda, "loss": args.loss, "metrics": args.metrics, "prioritized": args.prioritized,
               "distill_alpha": args.distill_alpha, "feature_distill": args.feature_distill,
-              "agem_ref_batch": args.agem_ref_batch, "clip_grad_norm": args.clip_grad_norm,
+              "agem_ref_batch": args.agem_ref_batch, "gem_ref_batch": args.gem_ref_batch, "gem_margin": args.gem_margin,
+              "gem_eps": args.gem_eps, "gem_eps_relative": args.gem_eps_relative, "gem_refresh": args.gem_refresh,
+              "clip_grad_norm": args.clip_grad_norm,
               "optimizer_impl": optimizer_impl(args), "ema_decay": args.ema_decay,
               "drift": DriftReport(args.drift, args.drift_grid, device) if args.drift != "off" else None}
     optimizer = build_optimizer(model, config)      # (the reference loops each build their own; the steps are the same)
     if args.strategy == "ewc":
         model = train_with_ewc(model, tasks, config, rank, world, args.epochs, optimizer=optimizer)
-    elif args.strategy in ("replay", "agem"):
+    elif args.strategy in ("replay", "agem", "gem"):
         if args.device_memory:
             memory = DeviceEpisodicMemory(capacity=args.memory_size, strategy="stratified", device=device,
                                           storage=args.memory_storage)
         else:
             memory = EpisodicMemory(capacity=args.memory_size, strategy="stratified")
-        train = train_with_replay if args.strategy == "replay" else train_with_agem
+        train = {"replay": train_with_replay, "agem": train_with_agem, "gem": train_with_gem}[args.strategy]
         model = train(model, tasks, memory, config, rank, args.epochs, optimizer=optimizer)
     elif args.strategy == "distill":
         if world > 1:

@@ -1183,6 +1183,32 @@ int nvq_ppo_loss(const float* head_outputs, const int* actions, const float* old
                  float value_coef, float entropy_coef, float* grad, double* out, double* workspace, size_t workspace_bytes,
                  void* stream);
 
+/* ------------------------------------------------------------------ Gradient Episodic Memory (csrc/gem.hip, DESIGN.md
+ * section 32).  GEM (Lopez-Paz & Ranzato 2017) keeps one reference gradient per earlier task: refs is a [T][stride] fp32 matrix,
+ * 1 <= T <= 15, stride >= n, and g the step's gradient, n floats.  The flat-buffer rule holds: no atomics, size-only grids, sums
+ * in double in a fixed order, the same bits on every call and at every pointer alignment (4-byte aligned pointers suffice).
+ *
+ * nvq_gem_gram: gram = 16 x 16 device doubles; gram[i * 16 + j], i, j <= T, = the inner product of rows i and j, index T standing
+ * for g.  Every factor is widened to double before the product (v_mfma_f64_16x16x4_f64); block partials go to the workspace
+ * (flat blocks x 256 doubles, <= 2 MiB, 8-byte aligned; NVQ_EWORKSPACE when short) and a finishing launch adds them in block
+ * order and mirrors: gram is symmetric bit for bit, and zero outside (T + 1) x (T + 1).  `accumulate` adds to the entries that are
+ * there (the next segment of the same model).
+ *
+ * nvq_gem_solve: q = gram[.][T], P = gram[0..T)[0..T) + ridge I with ridge = eps, or eps * max_t gram[t][t] with eps_relative.
+ * When some q_t < 0: v = argmin 1/2 v'Pv + q'v subject to v >= margin, by a primal active-set method in double on one
+ * workgroup, at most 64 Cholesky solves.  v = 16 device doubles, all zero when no q_t < 0 (a NaN compares false), when T == 0 or
+ * when a used gram entry is not finite.  stats = 8 device doubles: [0] number of q_t < 0, [1] number of v_t > margin, [2] solves,
+ * [3] status (0 solved, 1 cap reached: the last feasible iterate is used, 2 non-finite input: no projection), [4] += 1 when this
+ * call projects (the caller zeroes it once), [5] g.g, [6] g'.g' of the projected gradient from the Gram alone, [7] min_t cos(g,
+ * r_t) (a zero row counts as 0).
+ *
+ * nvq_gem_project: g[i] = (float)((double)g[i] + sum_t v[t] (double)refs[t][i]), t ascending, every term one fma in double.  v all
+ * zero leaves g untouched (bit-identical); a row with v[t] == 0 is not read. */
+int nvq_gem_gram(const float* refs, long stride, int T, const float* g, long n, double* gram, int accumulate, float* workspace,
+                 size_t workspace_bytes, void* stream);
+int nvq_gem_solve(const double* gram, int T, float margin, float eps, int eps_relative, double* v, double* stats, void* stream);
+int nvq_gem_project(float* g, const float* refs, long stride, int T, long n, const double* v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
